@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- chain-updates/s of the DEMCz hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A *step* is what the boundary is crossed per: ONE AUTOSTOP SLAB of the reference's driver loop
@@ -16,8 +16,12 @@ untimed slab of exactly the timed shape always runs first.  Workload at N=1: BAS
 
 Prints ONE JSON line (rank 0).  `value` = N_total * generations / seconds with inputs resident in HBM.
 `roofline` prices the window kernel (the dominant kernel) against HBM from HIP events recorded by the
-library on the kernel's own stream; `cpu_baseline` is the CPU oracle ("port": this repo's C
-restatement of src/demcz.jl, NOT the Julia package) timed on one host core on the same workload.
+library on the kernel's own stream during the timed steps.  A plain run measures the headline and
+nothing else; `--full` adds what takes runs of its own: the chain-count sweep, the other BASELINE
+configs (`configs`: C3, C4's shard, C5, C1 on the HIP path, the dimension sweep, the host-closure
+mode), `cpu_baseline` -- the CPU oracle ("port": this repo's C restatement of src/demcz.jl, NOT the
+Julia package) timed on one host core on the same workload -- and, sharded, the deferred schedule
+(`value_deferred`).  `--dump-outputs DIR` writes what the last timed step computed as .npy files.
 """
 import argparse
 import json
@@ -440,6 +444,39 @@ def tune_append_lag(dist, torch, n_loc, d, K, every, device):
     return chosen, rows
 
 
+DUMP_LIMIT = 64 << 20           # bytes of all --dump-outputs files together
+
+
+def dump_outputs(out_dir, runner, g_last, every, K, n_total, rhat_trace, rhat_last, suffix=""):
+    """`--dump-outputs`: what the timed path hands its caller after its last step (generations g_last - every + 1 .. g_last), as
+    float64 .npy files -- the step's history (chain: chains x d x generations, log_obj: chains x generations), the chains'
+    current positions and log-densities (X, logp), the archive rows appended in the step (Z_appended), the R-hat vector of the
+    step's check (rhat) and the max R-hat of every timed step (rhat_max).  Beyond DUMP_LIMIT the arrays are cut to a fixed
+    sample: the step's latest generations and archive rows, and for very large populations a subset of the chains drawn from a
+    fixed seed.  Returns {name: shape}."""
+    e = runner.engines[0]
+    n, d = e.N, e.d
+    X, logp, Z, M = runner.state()
+    chains = np.arange(n)
+    if n * (2 * d + 2) * 8 > (15 << 20):                           # X, logp and one generation of history: at most 15 MB
+        keep = (15 << 20) // ((2 * d + 2) * 8)
+        chains = np.sort(np.random.default_rng(20240611).choice(n, keep, replace=False))
+    gens = max(1, min(every, (48 << 20) // (len(chains) * (d + 1) * 8)))       # history: at most 48 MB (C2: all 1000)
+    chain, log_obj = runner.history(g_last - gens + 1, g_last)
+    rows = max(0, min(int(M), n_total * every // K, (7 << 20) // (d * 8)))    # archive: at most 7 MB
+    out = {"chain": chain[chains], "log_obj": log_obj[chains], "X": X[chains], "logp": logp[chains],
+           "Z_appended": np.asarray(Z)[int(M) - rows:int(M)], "rhat": np.asarray(rhat_last),
+           "rhat_max": np.asarray(rhat_trace)[-((1 << 20) // 8):]}
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for name, a in out.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+        shapes[name + suffix] = list(a.shape)
+    assert sum(int(np.prod(s)) * 8 for s in shapes.values()) <= DUMP_LIMIT
+    return shapes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -448,14 +485,22 @@ def main():
     ap.add_argument("--slab-generations", type=int, default=1000, help="generations per step: autostop_every (DEMC.jl:41)")
     ap.add_argument("--chains-per-gpu", type=int, default=1024)
     ap.add_argument("--dim", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sweep", action="store_true", help="skip the chain-count sweep object")
-    ap.add_argument("--no-configs", action="store_true", help="skip the `configs` object (C3, C4's shard, C5, C1 on the HIP path)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the chain-count sweep, the `configs` object, the CPU "
+                         "baseline and, sharded, the tuned deferred schedule (`value_deferred`); the --no-* switches below leave "
+                         "parts of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (history, positions, archive rows, R-hat) "
+                         "as float64 DIR/<name>.npy, at most 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-sweep", action="store_true", help="with --full: skip the chain-count sweep object")
+    ap.add_argument("--no-configs", action="store_true",
+                    help="with --full: skip the `configs` object (C3, C4's shard, C5, C1 on the HIP path, d sweep, closure)")
     ap.add_argument("--lanes-per-chain", type=int, default=0)
     ap.add_argument("--append-lag", type=int, default=-1,
                     help="demcz_set_append_lag batches for `value`.  Default: 0 (rows visible from the next generation on -- the "
-                         "reference's schedule with a synchronous exchange); when sharded the tuned deferred schedule is measured "
-                         "as well and reported as `value_deferred`")
+                         "reference's schedule with a synchronous exchange); when sharded, --full measures the tuned deferred "
+                         "schedule as well and reports it as `value_deferred`")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend of the rendezvous (nccl = RCCL; gloo with --dry-run)")
     ap.add_argument("--dry-run", action="store_true",
                     help="everything up to the first GPU call: arguments, rendezvous, sharding plan, the exchange of the 128-byte "
@@ -490,12 +535,13 @@ def main():
         sharding = torch_sharding(mode="rccl")
 
     # sharded default: boundaries per all-gather chosen by tune_append_lag (25 if the probe fails): a batch's compute
-    # (23.5 us per 100 generations) has to outlast a latency-bound all-gather over the node's links
+    # (23.5 us per 100 generations) has to outlast a latency-bound all-gather over the node's links.  Only the deferred
+    # measurement of --full (and the dry run's plan) uses it; `value` runs with 0.
     d, K, n_loc = args.dim, 10, args.chains_per_gpu
     lag_probe = None
     if args.append_lag >= 0:
         lag = args.append_lag
-    elif world == 1:
+    elif world == 1 or not (args.full or args.dry_run):
         lag = 0
     else:
         lag = 25 if (args.slab_generations // K) % 25 == 0 else 10
@@ -578,9 +624,10 @@ def main():
             sys.exit(4)
     X, logp = demc.initial_state(w["target"], w["Zinit"], N, G, K, None, "last_rows")
 
-    def measure(lag_m):
+    def measure(lag_m, dump=None):
         """One complete measurement with `lag_m` boundaries per exchange (0: the north star's schedule -- rows visible from the
-        next generation on): runner, W untimed slabs, the fenced timed region of S slabs.  Returns a dict."""
+        next generation on): runner, W untimed slabs, the fenced timed region of S slabs; `dump`: the directory the last timed
+        slab's results go to (dump_outputs).  Returns a dict."""
         runner = demc.make_runner(w["target"], w["Zinit"], N, K, G, [range(d)], w["eps_scale"], X, logp, seed=seed,
                                   sharding=sharding, device_id=local_rank, engine_factory=None,
                                   lanes_per_chain=args.lanes_per_chain, stream=stream.cuda_stream, append_lag=lag_m)
@@ -590,8 +637,8 @@ def main():
         def advance(g_from, g_to, timed):
             """Generations g_from..g_to with the R-hat check every `every` generations: one library call
             (demcz_run_checked = the driver loop demcz.jl:30-55 without its stop), the window kernels timed by
-            HIP events on their own stream inside the library.  Returns (ms spent in window kernels, launches)."""
-            _, trace, _ = runner.run_checked(g_from, g_to, w["gamma"], every, 0.0)      # (returns with the streams drained)
+            HIP events on their own stream inside the library.  Returns the max R-hat of every check."""
+            _, trace, res["rhat_last"] = runner.run_checked(g_from, g_to, w["gamma"], every, 0.0)      # (returns with the streams drained)
             return trace
 
         def note(trace, g_from):
@@ -655,6 +702,9 @@ def main():
                             "peer_status": list(res["peer"]), "peer_ping": list(eng.peer_ping()) if hasattr(eng, "peer_ping") else None,
                             "window_launches_timed": int(launches), "rendezvous_arrive_s": stamps.get("pre_arrive"),
                             "rendezvous_leave_s": stamps.get("pre_leave"), "own_timed_call_ms": (stamps["timed_done"] - t0) * 1e3}
+        if dump:
+            res["dumped"] = dump_outputs(dump, runner, G, every, K, N, trace, res["rhat_last"],
+                                         suffix=f"_rank{rank}" if world > 1 else "")
         runner.close()        # (frees the device's LIVE slot for the next measurement / the sweep's handles)
         return res
 
@@ -662,9 +712,9 @@ def main():
     try:
         # N > 1: `value` is the north star's schedule ("all-gather ... every K steps": synchronous exchange, rows visible in the
         # next generation, the sampler the N = 1 line runs); the tuned deferred schedule is measured right after it and reported
-        # beside it as `value_deferred` -- a different sampler (rows visible lag..2 lag windows late), so it never is `value`.
-        both = world > 1 and args.append_lag < 0
-        m = measure(0 if both else lag)
+        # beside it as `value_deferred` (--full) -- a different sampler (rows visible lag..2 lag windows late), so it never is `value`.
+        both = world > 1 and args.append_lag < 0 and args.full
+        m = measure(0 if both else lag, dump=args.dump_outputs)
         md = measure(lag) if both else None
     except DemczError as e:
         if e.code == ERR_COMM:
@@ -749,17 +799,20 @@ def main():
                                "what": f"the same run with the K-boundary rows of {lag} boundaries travelling in one all-gather on a side "
                                        f"stream and becoming visible {lag}..{2 * lag} windows later (demcz_set_append_lag): a different "
                                        "sampler from `value`'s -- compare its gens_to_rhat_1p05; `--gpus 1 --append-lag E` is its N = 1 point"}
-        if world == 1 and not args.no_sweep and (n_loc, d) == (1024, 5):
+        if args.dump_outputs:
+            out["outputs_dumped"] = m["dumped"]
+        # everything below: --full only
+        if world == 1 and args.full and not args.no_sweep and (n_loc, d) == (1024, 5):
             try:     # reporting only: throughput regime of the same path
                 out["chain_count_sweep"] = [throughput_point(demc, n, d, K, seed, g, local_rank, reps)
                                             for n, g, reps in ((2048, 1000, 5), (4096, 1000, 5), (16384, 400, 5), (131072, 200, 2), (1048576, 100, 1))]
             except Exception as e:
                 out["chain_count_sweep"] = f"failed: {e}"
-        if world == 1 and not args.no_configs:
+        if world == 1 and args.full and not args.no_configs:
             out["configs"] = config_rows(demc, seed, local_rank)
             out["configs"]["d_sweep"] = d_sweep_rows(demc, seed, local_rank)
             out["configs"]["closure"] = closure_row(demc, seed, local_rank)
-        if not args.no_cpu_baseline and world == 1:      # (the contract: rank 0 at N = 1 only)
+        if args.full and not args.no_cpu_baseline and world == 1:      # (the contract: rank 0 at N = 1 only)
             try:
                 out["cpu_baseline"] = cpu_baseline(demc.workloads.mvnormal_problem(d, n_loc), n_loc, d, K, seed, 8.0e7, w["Zinit"].shape[0] + N * (G // K))
             except Exception as e:   # the baseline is reporting only; never fail the bench on it

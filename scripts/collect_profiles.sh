@@ -12,7 +12,7 @@ R=$PWD
 if [ "$1" = "cfg" ]; then
   prog="$R/scripts/run_cfg.py $2 ${3:-400}"
 else
-  prog="$R/bench.py --no-cpu-baseline --no-sweep $*"
+  prog="$R/bench.py --full --no-cpu-baseline --no-sweep $*"
 fi
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/${tag}_trace -- python3 $prog > $R/gpurun_out/${tag}_trace.log 2>&1

@@ -307,6 +307,36 @@ def test_bench_under_torchrun_single_rank(tmp_path):
     assert set(("bound", "achieved", "peak", "unit", "frac", "traffic")) <= set(d["roofline"])
 
 
+def test_bench_dump_outputs_equal_oracle(demc, oracle, tmp_path):
+    """`bench.py --dump-outputs DIR`: a plain run (the headline and nothing else) writes what its last timed step computed --
+    float64 files, 64 MB at most -- and those are the oracle's results for the same seeded inputs, bit for bit: the step's
+    history, the chains' positions and log-densities, the archive rows appended in it; its R-hat check to rounding."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parent.parent
+    cmd = [sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, check=True).stdout
+    line = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert not {"configs", "chain_count_sweep", "cpu_baseline", "value_deferred"} & set(line)
+    files = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert set(files) == {"chain", "log_obj", "X", "logp", "Z_appended", "rhat", "rhat_max"}
+    assert all(a.dtype == np.float64 for a in files.values())
+    assert sum(p.stat().st_size for p in tmp_path.glob("*.npy")) <= 64 << 20
+    d, N, K, every, G = 5, 1024, 10, 1000, 3000
+    w = demc.workloads.mvnormal_problem(d, N)
+    ref = oracle_sample(oracle, w["target"], w["Zinit"], N, K, G, None, w["eps_scale"], w["gamma"], 31953150)
+    assert np.array_equal(files["chain"], ref["chain"][:, :, G - every:])
+    assert np.array_equal(files["log_obj"], ref["log_obj"][:, G - every:])
+    assert np.array_equal(files["X"], ref["X"]) and np.array_equal(files["logp"], ref["logp"])
+    assert np.array_equal(files["Z_appended"], ref["Z"][-N * every // K:])
+    rh = demc.Rhat_gelman(ref["chain"][:, :, G - every:])
+    assert np.allclose(files["rhat"], rh, rtol=1e-9, atol=0) and files["rhat_max"].shape == (2,)
+    assert files["rhat_max"][-1] == np.max(files["rhat"])
+
+
 @pytest.mark.parametrize("first,second", [(None, "4x5"), ("4x5", None), (None, "10-3-7")])
 def test_prevrun_carried_into_a_run_with_other_blocks_equals_oracle(demc, oracle, first, second):
     """demcz.jl:18-22: a `prevrun` hands X AND log_objcurrent to the next run.  The MvNormal sums are cut at the run's block

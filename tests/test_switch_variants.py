@@ -18,18 +18,22 @@ FLIPPED = ROOT / "build_ab" / "flipped.so"
 SWITCHES = ["-DPW_WDPP=0", "-DPW_DDPP=0", "-DMLB_DPP_RECORD=1", "-DPS2_DDPP=1", "-DPS2_HRING_ONE=1", "-DML_LRDPP=0"]
 
 
-def test_flipped_switches_build():
-    if shutil.which("hipcc") is None:
-        pytest.skip("no hipcc")
+def _build_flipped():
     r = subprocess.run([sys.executable, str(ROOT / "scripts" / "build_variant.py"), "flipped"] + SWITCHES, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     assert FLIPPED.exists()
 
 
+def test_flipped_switches_build():
+    if shutil.which("hipcc") is None:
+        pytest.skip("no hipcc")
+    _build_flipped()
+
+
 @pytest.mark.gpu
 def test_flipped_switches_are_bit_identical_to_the_oracle():
-    if not FLIPPED.exists():
-        pytest.skip("build_ab/flipped.so not built (the CPU tier builds it)")
+    if not FLIPPED.exists():            # (a checkout where only the GPU tier runs: build it here, as the CPU tier does)
+        _build_flipped()
     env = dict(os.environ, DEMCZ_LIB=str(FLIPPED))
     sel = ["tests/test_gpu_long_oracle.py::test_wave_per_chain_regular_launches_equal_oracle",
            "tests/test_gpu_long_oracle.py::test_c3_block_updates_long_run_equals_oracle",
