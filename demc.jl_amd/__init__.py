@@ -11,7 +11,7 @@ C ABI of ``include/demcz.h``; there is no CPU fallback.
 """
 from ._lib import DemczError, build, LIB_PATH, SYMBOLS, LAYOUT_SPLIT, LAYOUT_SPLIT_WAVE          # noqa: F401
 from .engine import HipEngine, selftest_draws, pool_trim                   # noqa: F401
-from .targets import MvNormalTarget, IsoQuadTarget, LinRegSSETarget, is_device_target   # noqa: F401
+from .targets import MvNormalTarget, IsoQuadTarget, LinRegSSETarget, ProgramTarget, is_device_target   # noqa: F401
 from .sampler import (MC, DEMCopt, demcopt, demcz_sample, demcz_anneal, tempbaseline,   # noqa: F401
                       make_runner, initial_state,
                       Sharding, DEFAULT_ADAPT)

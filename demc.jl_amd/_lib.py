@@ -22,7 +22,7 @@ ABI_VERSION = 1
 LAYOUT_SPLIT = 100          # producer / consumer split, eight replicated (d <= 10) or sixteen cooperating lanes per chain
 LAYOUT_SPLIT_WAVE = 164     # the split with one wavefront per chain, five generations per pass (MvNormal, d = 2..5, 8, 10, 20)
 
-TARGET_MVNORMAL, TARGET_ISO_QUAD, TARGET_LINREG_SSE, TARGET_HOST_CALLBACK = 0, 1, 2, 3
+TARGET_MVNORMAL, TARGET_ISO_QUAD, TARGET_LINREG_SSE, TARGET_HOST_CALLBACK, TARGET_PROGRAM = 0, 1, 2, 3, 4
 OK, ERR_INVALID_ARGUMENT, ERR_HIP, ERR_CAPACITY, ERR_STATE, ERR_NO_DEVICE, ERR_COMM = range(7)
 
 _dp = C.POINTER(C.c_double)
@@ -45,7 +45,7 @@ SYMBOLS = [
     "demcz_history_stream", "demcz_get_history_view", "demcz_detach_history", "demcz_release_host_buffer", "demcz_get_archive_pinned",
     "demcz_debug_kernel_counts", "demcz_pool_trim", "demcz_debug_kernel_name", "demcz_peer_group", "demcz_get_peer_status", "demcz_peer_export", "demcz_peer_attach",
     "demcz_peer_detach", "demcz_get_peer_ping", "demcz_set_live_rearms", "demcz_get_live_rearms",
-    "demcz_closure_buffers",
+    "demcz_closure_buffers", "demcz_program_check", "demcz_set_program",
 ]
 
 
@@ -73,16 +73,18 @@ HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-W
 
 def sources() -> list:
     """The library's translation units: the C ABI with most kernels (demcz_capi.hip), the eight units that instantiate
-    window_kernel_pw for every dimension from 6 to 32 (demcz_pw_inst_<g>.hip, csrc/demcz_pw_dispatch.h) and the two with the
-    sixteen-lane regression kernels for every dimension from 2 to 28 (demcz_mlr_inst_<g>.hip, csrc/demcz_mlr_dispatch.h)."""
+    window_kernel_pw for every dimension from 6 to 32 (demcz_pw_inst_<g>.hip, csrc/demcz_pw_dispatch.h), the two with the
+    sixteen-lane regression kernels for every dimension from 2 to 28 (demcz_mlr_inst_<g>.hip, csrc/demcz_mlr_dispatch.h) and the
+    host code of program targets (demcz_program.hip: hipRTC, the kernel headers embedded as text)."""
     csrc = PKG_DIR / "csrc"
-    return [csrc / "demcz_capi.hip"] + sorted(csrc.glob("demcz_pw_inst_*.hip")) + sorted(csrc.glob("demcz_mlr_inst_*.hip"))
+    return ([csrc / "demcz_capi.hip"] + sorted(csrc.glob("demcz_pw_inst_*.hip")) + sorted(csrc.glob("demcz_mlr_inst_*.hip"))
+            + [csrc / "demcz_program.hip"])
 
 
 def build_command(out: Path = LIB_PATH) -> list:
     """The build as ONE command (what a Makefile-less integrator would type; compiles the units one after the other: ~4 min).
     build() below runs the same compiler with the same flags on every unit in parallel and links the objects."""
-    return ["hipcc"] + HIPCC_FLAGS + ["-shared", "-o", str(out)] + [str(p) for p in sources()] + ["-lrccl"]
+    return ["hipcc"] + HIPCC_FLAGS + ["-shared", "-o", str(out)] + [str(p) for p in sources()] + ["-lrccl", "-lhiprtc"]
 
 
 def build_lib(out: Path = LIB_PATH, extra: list = (), jobs: int = 0) -> Path:
@@ -103,7 +105,7 @@ def build_lib(out: Path = LIB_PATH, extra: list = (), jobs: int = 0) -> Path:
 
     with ThreadPoolExecutor(max_workers=jobs) as ex:
         objs = list(ex.map(compile_one, srcs))
-    subprocess.run(["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(out)] + [str(o) for o in objs] + ["-lrccl"], check=True)
+    subprocess.run(["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(out)] + [str(o) for o in objs] + ["-lrccl", "-lhiprtc"], check=True)
     return Path(out)
 
 
@@ -184,6 +186,8 @@ def load():
     L.demcz_set_live_rearms.argtypes = [C.c_void_p, C.c_int32]
     L.demcz_get_live_rearms.argtypes = [C.c_void_p, _ip, _ip]
     L.demcz_debug_kernel_name.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
+    L.demcz_program_check.argtypes = [C.c_int32, C.c_char_p, C.c_char_p]
+    L.demcz_set_program.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, _dp, C.c_int64]
     L.demcz_get_archive_pinned.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), _lp]
     L.demcz_get_kernel_time_series.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _ip]
     L.demcz_set_comm_timeout.argtypes = [C.c_void_p, C.c_int64]

@@ -12,6 +12,7 @@
 #include "demcz_kernels_ps2d.h"
 #include "demcz_pw_dispatch.h"
 #include "demcz_mlr_dispatch.h"
+#include "demcz_program.h"
 
 #include <rccl/rccl.h>
 
@@ -363,6 +364,10 @@ struct demcz_handle {
     bool comm_dead = false;
     int* stall_flag = nullptr;         // device word; demcz_debug_stall_exchange: the stall kernel spins until it is set
     int32_t stall_next_ms = 0;
+    // program target (demcz_set_program): the loaded module of the program's kernels; its data live in d_design, ndata in
+    // cfg.nobs (the TargetParams slots only the regression reads)
+    bool prog_ready = false;
+    demcz_prog::Module prog;
 };
 
 #define HIPCHK(h, expr)                                                                          \
@@ -734,6 +739,14 @@ extern "C" int32_t demcz_create(demcz_handle** out, const demcz_config* cfg)
             return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, "LINREG_SSE needs design, yobs, nobs>=1");
         break;
     case DEMCZ_TARGET_HOST_CALLBACK: break;
+    case DEMCZ_TARGET_PROGRAM:
+        // (the program is compiled into the one-lane window kernel only: the split, wave-per-chain and cooperating-lane layouts
+        //  are not built for it)
+        if (cfg->lanes_per_chain != 0 && cfg->lanes_per_chain != 1)
+            return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_create: a program target runs one lane per chain: lanes_per_chain must be 0 or 1");
+        if (cfg->d > demcz_prog::MAX_PROGRAM_D)
+            return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_create: a program target needs 1 <= d <= 32");
+        break;
     default: return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, "unknown target_kind");
     }
     int ndev = 0;
@@ -904,6 +917,7 @@ extern "C" int32_t demcz_create(demcz_handle** out, const demcz_config* cfg)
     // no pointer of the caller's survives create
     h->cfg.block_offsets = nullptr; h->cfg.block_indices = nullptr; h->cfg.eps_scale = nullptr;
     h->cfg.mu = nullptr; h->cfg.W = nullptr; h->cfg.design = nullptr; h->cfg.yobs = nullptr; h->cfg.stream = nullptr;
+    if (cfg->target_kind == DEMCZ_TARGET_PROGRAM) h->cfg.nobs = 0;      // (ndata, once demcz_set_program has run)
 
     const int64_t N = cfg->N;
     const int64_t N_for_arena = cfg->N;
@@ -1114,6 +1128,14 @@ static int32_t launch_logp(demcz_handle* h, const double* X, int64_t ldX, int64_
         hipLaunchKernelGGL(logp_kernel<TARGET_ISO_QUAD>, grid, dim3(bs), 0, h->stream, tp, h->cfg.d, X, ldX, n, out); break;
     case DEMCZ_TARGET_LINREG_SSE:
         hipLaunchKernelGGL(logp_kernel<TARGET_LINREG_SSE>, grid, dim3(bs), 0, h->stream, tp, h->cfg.d, X, ldX, n, out); break;
+    case DEMCZ_TARGET_PROGRAM: {
+        if (!h->prog_ready) return fail(h, DEMCZ_ERR_STATE, "program target: call demcz_set_program first");
+        TargetParams tpv = tp;
+        int dv = h->cfg.d;
+        void* args[] = {&tpv, &dv, &X, &ldX, &n, &out};
+        HIPCHK(h, hipModuleLaunchKernel(h->prog.logp, grid.x, 1, 1, bs, 1, 1, 0, h->stream, args, nullptr));
+        break;
+    }
     default: return fail(h, DEMCZ_ERR_STATE, "host-callback target: pass logp explicitly");
     }
     HIPCHK(h, hipGetLastError());
@@ -1130,6 +1152,8 @@ extern "C" int32_t demcz_set_state(demcz_handle* h, const double* X, const doubl
     if (M0 > h->cfg.Mcap || ldZ < M0) return fail(h, DEMCZ_ERR_CAPACITY, "demcz_set_state: M0 exceeds Mcap or ldZ < M0");
     if (!logp && h->cfg.target_kind == DEMCZ_TARGET_HOST_CALLBACK)
         return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_state: host-callback target needs logp");
+    if (h->cfg.target_kind == DEMCZ_TARGET_PROGRAM && !h->prog_ready)
+        return fail(h, DEMCZ_ERR_STATE, "demcz_set_state: program target: call demcz_set_program first");
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
     const int d = h->cfg.d;
     const int64_t N = h->cfg.N;
@@ -1255,6 +1279,41 @@ extern "C" int32_t demcz_set_history_origin(demcz_handle* h, int64_t g0)
         HIPCHK(h, hipMemcpyAsync(h->dlp_origin, h->dlp, (size_t)h->cfg.N * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     if (h->has_state && h->g_done == h->g0) h->g_done = g0;      // nothing run yet: renumbering only
     h->g0 = g0;
+    return DEMCZ_OK;
+}
+
+// ---- program targets (demcz_program.hip) ---------------------------------------------------------
+extern "C" int32_t demcz_program_check(int32_t d, const char* source, const char* options)
+{
+    std::shared_ptr<const demcz_prog::Code> code;
+    std::string err;
+    if (demcz_prog::get_code(d, source, options, code, err) != 0) return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, err);
+    return DEMCZ_OK;
+}
+
+extern "C" int32_t demcz_set_program(demcz_handle* h, const char* source, const char* options, const double* data, int64_t ndata)
+{
+    if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
+    DEADCHK(h);
+    if (h->cfg.target_kind != DEMCZ_TARGET_PROGRAM)
+        return fail(h, DEMCZ_ERR_STATE, "demcz_set_program: the handle was not created with DEMCZ_TARGET_PROGRAM");
+    if (h->prog_ready || h->has_state)
+        return fail(h, DEMCZ_ERR_STATE, "demcz_set_program: a handle takes its program once, before demcz_set_state");
+    if (ndata < 0 || (ndata > 0 && !data))
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_program: need ndata >= 0 and data for ndata > 0");
+    std::shared_ptr<const demcz_prog::Code> code;
+    std::string err;
+    if (demcz_prog::get_code(h->cfg.d, source, options, code, err) != 0) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, err);
+    demcz_prog::Module mod;
+    if (demcz_prog::get_module(code, h->cfg.device_id, mod, err) != 0) return fail(h, DEMCZ_ERR_HIP, err);
+    HIPCHK(h, hipSetDevice(h->cfg.device_id));
+    double* dd = nullptr;
+    HIPCHK(h, dev_alloc_copy(&dd, data, (size_t)ndata, h->stream, h->cfg.device_id));
+    SYNCCHK(h, h->stream);
+    h->d_design = dd;               // (freed with the handle; TargetParams::design / nobs carry it to the kernels)
+    h->cfg.nobs = ndata;
+    h->prog = mod;
+    h->prog_ready = true;
     return DEMCZ_OK;
 }
 
@@ -1826,6 +1885,15 @@ static int32_t launch_window(demcz_handle* h, const WindowParams& P, bool live =
         default: launch_window_generic<TARGET_LINREG_SSE>(h, P, grid); break;
         }
         break;
+    case DEMCZ_TARGET_PROGRAM: {
+        // the program's own window_kernel<TARGET_PROGRAM, d, FULL> (demcz_program.hip), from its module
+        if (!h->prog_ready) return fail(h, DEMCZ_ERR_STATE, "demcz_run: program target: call demcz_set_program first");
+        WindowParams Pv = P;
+        void* args[] = {&Pv};
+        HIPCHK(h, hipModuleLaunchKernel(h->full_block ? h->prog.window_full : h->prog.window_blocks, grid.x, 1, 1, WINDOW_BS, 1, 1, 0,
+                                        h->stream, args, nullptr));
+        break;
+    }
     default: return fail(h, DEMCZ_ERR_STATE, "demcz_run: host-callback target uses demcz_propose/accept_commit");
     }
     HIPCHK(h, hipGetLastError());
@@ -4207,7 +4275,7 @@ extern "C" int32_t demcz_debug_kernel_name(const demcz_handle* h, char* buf, int
     if (!h || !buf || cap < 1) return DEMCZ_ERR_INVALID_ARGUMENT;
     const int d = h->cfg.d;
     const char* tg = h->cfg.target_kind == DEMCZ_TARGET_MVNORMAL ? "MVNORMAL" : h->cfg.target_kind == DEMCZ_TARGET_ISO_QUAD ? "ISO_QUAD"
-                     : h->cfg.target_kind == DEMCZ_TARGET_LINREG_SSE ? "LINREG_SSE" : "HOST";
+                     : h->cfg.target_kind == DEMCZ_TARGET_LINREG_SSE ? "LINREG_SSE" : h->cfg.target_kind == DEMCZ_TARGET_PROGRAM ? "PROGRAM" : "HOST";
     const char* lv = h->last_live ? "true" : "false";
     const char* tm = h->last_temper ? "true" : "false";
     char tmp[160];
@@ -4228,6 +4296,8 @@ extern "C" int32_t demcz_debug_kernel_name(const demcz_handle* h, char* buf, int
         else if (lr && uses_lr16(h)) snprintf(tmp, sizeof tmp, "window_kernel_lr16<%d, false, false>", d);
         else if (lr && ml_coop(h)) snprintf(tmp, sizeof tmp, "window_kernel_ml<%s, %d, %d, false, false, true>", tg, d, h->lanes);
         else snprintf(tmp, sizeof tmp, "window_kernel_ml<%s, %d, %d>", tg, d, h->lanes);
+    } else if (h->cfg.target_kind == DEMCZ_TARGET_PROGRAM) {
+        snprintf(tmp, sizeof tmp, "window_kernel<%d, %d, %s> (program)", (int)TARGET_PROGRAM, d, h->full_block ? "true" : "false");
     } else {
         snprintf(tmp, sizeof tmp, "window_kernel<%s, %d, %s>", tg, d, h->full_block ? "true" : "false");
     }

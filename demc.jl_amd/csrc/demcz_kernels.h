@@ -25,7 +25,7 @@
 
 namespace demcz {
 
-enum { TARGET_MVNORMAL = 0, TARGET_ISO_QUAD = 1, TARGET_LINREG_SSE = 2, TARGET_HOST_CALLBACK = 3 };
+enum { TARGET_MVNORMAL = 0, TARGET_ISO_QUAD = 1, TARGET_LINREG_SSE = 2, TARGET_HOST_CALLBACK = 3, TARGET_PROGRAM = 4 };
 
 constexpr int MAX_D = 64;        // generic (runtime-d) path keeps x / xprop / normals in LDS
 constexpr int LINREG_PARTIALS = 16;   // interleaved partial sums of the regression SSE (arithmetic spec)
@@ -35,9 +35,9 @@ struct TargetParams {
     const double* mu;        // d
     const double* Wp;        // MVNORMAL: packed row-major lower triangle, row i at i(i+1)/2
     double c0;
-    const double* design;    // LINREG: row-major nobs x d (one observation's regressors contiguous)
-    const double* yobs;
-    int64_t nobs;
+    const double* design;    // LINREG: row-major nobs x d (one observation's regressors contiguous).  PROGRAM: the program's
+    const double* yobs;      // `data` (demcz_set_program), with nobs = ndata -- the slots only the regression reads, so that
+    int64_t nobs;            // WindowParams stays the same struct for every kernel
     // MVNORMAL, round 4: the sums of the quadratic form cut at the block boundaries (oracle: mvn_groups).
     // ngrp > 1 iff the run's blocks, in order, are consecutive index ranges covering 0..d-1; goff = their ngrp + 1 offsets
     // (device memory), gstart = bit j set iff parameter j starts a group.  ngrp <= 1: one group, the order of rounds 1-3.
@@ -266,6 +266,15 @@ __device__ __forceinline__ double target_logp(const TargetParams& tp, int d, XF 
             q = (i == 0) ? r * r : fma(r, r, q);
         }
         return -q;
+#ifdef DEMCZ_PROGRAM_TARGET
+    } else if constexpr (TARGET == TARGET_PROGRAM) {
+        // a program target (demcz_program.hip): only in the translation unit hipRTC compiles for it, which defines DEMCZ_D and
+        // the user's demcz_logobj in front of this header.  x is gathered into registers (every loop over DEMCZ_D unrolls).
+        double xv[DEMCZ_D];
+#pragma unroll
+        for (int j = 0; j < DEMCZ_D; ++j) xv[j] = X(j);
+        return demcz_logobj(xv, tp.design, tp.nobs);
+#endif
     } else {
         // 16 interleaved partial sums (observation o -> partial o mod 16), then the fixed tree
         // (l, l+8), (l, l+4), (l, l+2), (0, 1): the spec's order, shared with the 16-lane layout.

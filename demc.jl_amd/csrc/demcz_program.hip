@@ -1,0 +1,226 @@
+// demcz_program.hip -- program targets (DEMCZ_TARGET_PROGRAM): a log-density the user writes as HIP C++, compiled at run time
+// with hipRTC for gfx950 together with the one-lane window kernel of demcz_kernels.h, and loaded as a module on the handle's
+// device.  Host code only: the kernels of a program live in its code object, not in this library.
+//
+// The composed translation unit (compose):
+//     #define DEMCZ_D <d> / DEMCZ_PROGRAM_TARGET / DEMCZ_NO_AUX_KERNELS
+//     the user's source                      (#line 1 "program": compiler messages carry the user's own line numbers)
+//     #include "demcz_kernels.h"             (its text and demcz_device.h's are embedded into this library at build time)
+//     explicit instantiations of window_kernel<TARGET_PROGRAM, DEMCZ_D, true / false> and logp_kernel<TARGET_PROGRAM>
+// Compile options: --offload-arch=gfx950 -O3 -ffp-contract=off -I<rocm>/include, the library's own layout switches, then the
+// user's.  Code objects are cached per (composed text, options), loaded modules per (code object, device); both for the life of
+// the process.
+#include "demcz_program.h"
+
+#include <hip/hip_runtime.h>
+#include <hip/hiprtc.h>
+
+#include <dlfcn.h>
+#include <sys/stat.h>
+
+#include <cstdlib>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <sstream>
+#include <string>
+#include <utility>
+#include <vector>
+
+namespace {
+
+// The header text the library was built with (C23 #embed, accepted by hipcc as an extension)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wc23-extensions"
+const char k_device_h[] = {
+#embed "demcz_device.h"
+    , 0};
+const char k_kernels_h[] = {
+#embed "demcz_kernels.h"
+    , 0};
+#pragma clang diagnostic pop
+
+// -D switches of the library build that change the layout of WindowParams: the program's kernels must see the same struct
+const char* const k_layout_switches[] = {
+#ifdef DEMCZ_STAMPS
+    "-DDEMCZ_STAMPS",
+#endif
+    nullptr};
+
+constexpr size_t LOG_MAX = 6000;      // bytes of compiler log handed back (the first errors are the useful ones)
+
+std::mutex g_prog_mu;
+std::map<std::string, std::shared_ptr<const demcz_prog::Code>> g_code_cache;                        // composed text + options
+std::map<std::pair<const demcz_prog::Code*, int>, demcz_prog::Module> g_module_cache;               // (code object, device)
+
+std::string compose(int d, const std::string& source)
+{
+    std::ostringstream s;
+    s << "#define DEMCZ_D " << d << "\n#define DEMCZ_PROGRAM_TARGET\n#define DEMCZ_NO_AUX_KERNELS\n"
+      << "#include <hip/hip_runtime.h>\n#include <stdint.h>\n"
+      << "#line 1 \"program\"\n" << source << "\n"
+      << "#line 1 \"demcz_program_unit\"\n#include \"demcz_kernels.h\"\n"
+      << "template __global__ void demcz::window_kernel<demcz::TARGET_PROGRAM, DEMCZ_D, true>(const demcz::WindowParams);\n"
+      << "template __global__ void demcz::window_kernel<demcz::TARGET_PROGRAM, DEMCZ_D, false>(const demcz::WindowParams);\n"
+      << "template __global__ void demcz::logp_kernel<demcz::TARGET_PROGRAM>(demcz::TargetParams, int, const double*, int64_t, "
+         "int64_t, double*);\n";
+    return s.str();
+}
+
+std::vector<std::string> split_options(const char* options)
+{
+    std::vector<std::string> out;
+    std::istringstream in(options ? options : "");
+    std::string w;
+    while (in >> w) out.push_back(w);
+    return out;
+}
+
+bool file_exists(const std::string& p)
+{
+    struct stat st;
+    return stat(p.c_str(), &st) == 0;
+}
+
+// ROCm's include directory (rocRAND's Philox header): ROCM_PATH, else the install libhiprtc was loaded from
+bool rocm_include(std::string& dir, std::string& err)
+{
+    std::string root;
+    if (const char* rp = getenv("ROCM_PATH"); rp && *rp) {
+        root = rp;
+    } else {
+        Dl_info info{};
+        if (dladdr(reinterpret_cast<void*>(&hiprtcCreateProgram), &info) && info.dli_fname) {
+            std::string lib = info.dli_fname;                   // <rocm>/lib/libhiprtc.so.N
+            const size_t a = lib.rfind('/');
+            const size_t b = (a == std::string::npos || a == 0) ? std::string::npos : lib.rfind('/', a - 1);
+            if (b != std::string::npos) root = lib.substr(0, b);
+        }
+    }
+    dir = root + "/include";
+    if (root.empty() || !file_exists(dir + "/rocrand/rocrand_philox4x32_10.h")) {
+        err = "program target: rocRAND's header rocrand/rocrand_philox4x32_10.h was not found under '" + dir +
+              "' (the ROCm install is taken from ROCM_PATH, or else from where libhiprtc was loaded; set ROCM_PATH to the ROCm root)";
+        return false;
+    }
+    return true;
+}
+
+std::string trim_log(std::string log)
+{
+    if (log.size() > LOG_MAX) log = log.substr(0, LOG_MAX) + "\n... (compiler log cut)";
+    return log;
+}
+
+#define RTCCHK(expr)                                                                             \
+    do {                                                                                         \
+        hiprtcResult r_ = (expr);                                                                \
+        if (r_ != HIPRTC_SUCCESS) {                                                              \
+            err = std::string("program target: " #expr ": ") + hiprtcGetErrorString(r_);         \
+            return false;                                                                        \
+        }                                                                                        \
+    } while (0)
+
+bool compile(const std::string& text, const std::vector<std::string>& opts, int d, demcz_prog::Code& code, std::string& err)
+{
+    hiprtcProgram prog = nullptr;
+    const char* headers[] = {k_device_h, k_kernels_h};
+    const char* names[] = {"demcz_device.h", "demcz_kernels.h"};
+    RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_program_unit.hip", 2, headers, names));
+    struct Guard { hiprtcProgram& p; ~Guard() { if (p) (void)hiprtcDestroyProgram(&p); } } guard{prog};
+    const std::string ds = std::to_string(d);
+    const std::string exprs[3] = {"&demcz::window_kernel<4, " + ds + ", true>", "&demcz::window_kernel<4, " + ds + ", false>",
+                                  "&demcz::logp_kernel<4>"};
+    for (const auto& e : exprs) RTCCHK(hiprtcAddNameExpression(prog, e.c_str()));
+    std::vector<const char*> argv;
+    for (const auto& o : opts) argv.push_back(o.c_str());
+    const hiprtcResult rc = hiprtcCompileProgram(prog, (int)argv.size(), argv.data());
+    if (rc != HIPRTC_SUCCESS) {
+        size_t n = 0;
+        std::string log;
+        if (hiprtcGetProgramLogSize(prog, &n) == HIPRTC_SUCCESS && n > 1) {
+            log.resize(n);
+            if (hiprtcGetProgramLog(prog, &log[0]) != HIPRTC_SUCCESS) log.clear();
+            while (!log.empty() && log.back() == '\0') log.pop_back();
+        }
+        err = "program target: compilation failed (" + std::string(hiprtcGetErrorString(rc)) + ")";
+        if (text.find("demcz_logobj") == std::string::npos)          // (the library's own call is in demcz_kernels.h, not in `text`)
+            err += "; the program does not define demcz_logobj -- it must define "
+                   "__device__ double demcz_logobj(const double* x, const double* data, int64_t ndata)";
+        err += ":\n" + trim_log(log);
+        return false;
+    }
+    size_t n = 0;
+    RTCCHK(hiprtcGetCodeSize(prog, &n));
+    code.object.resize(n);
+    RTCCHK(hiprtcGetCode(prog, code.object.data()));
+    std::string* lowered[3] = {&code.window_full, &code.window_blocks, &code.logp};
+    for (int i = 0; i < 3; ++i) {
+        const char* nm = nullptr;
+        RTCCHK(hiprtcGetLoweredName(prog, exprs[i].c_str(), &nm));
+        *lowered[i] = nm;
+    }
+    code.d = d;
+    return true;
+}
+#undef RTCCHK
+
+}  // namespace
+
+namespace demcz_prog {
+
+int32_t get_code(int d, const char* source, const char* options, std::shared_ptr<const Code>& out, std::string& err)
+{
+    if (d < 1 || d > MAX_PROGRAM_D) {
+        err = "program target: d must be in 1.." + std::to_string(MAX_PROGRAM_D);
+        return 1;
+    }
+    if (!source) {
+        err = "program target: source is NULL";
+        return 1;
+    }
+    std::string inc;
+    if (!rocm_include(inc, err)) return 1;
+    std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-I" + inc};
+    for (const char* const* s = k_layout_switches; *s; ++s) opts.push_back(*s);
+    for (auto& o : split_options(options)) opts.push_back(o);
+    const std::string text = compose(d, source);
+    std::string key = text;
+    for (const auto& o : opts) key += '\0' + o;
+    {
+        std::lock_guard<std::mutex> lk(g_prog_mu);
+        auto it = g_code_cache.find(key);
+        if (it != g_code_cache.end()) { out = it->second; return 0; }
+    }
+    auto code = std::make_shared<Code>();
+    if (!compile(text, opts, d, *code, err)) return 1;
+    std::lock_guard<std::mutex> lk(g_prog_mu);
+    auto ins = g_code_cache.emplace(key, code);           // (another thread may have compiled the same program meanwhile)
+    out = ins.first->second;
+    return 0;
+}
+
+int32_t get_module(const std::shared_ptr<const Code>& code, int device, Module& out, std::string& err)
+{
+    std::lock_guard<std::mutex> lk(g_prog_mu);
+    const auto key = std::make_pair(code.get(), device);
+    auto it = g_module_cache.find(key);
+    if (it != g_module_cache.end()) { out = it->second; return 0; }
+    Module m;
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipModuleLoadData(&m.module, code->object.data());
+    if (e == hipSuccess) e = hipModuleGetFunction(&m.window_full, m.module, code->window_full.c_str());
+    if (e == hipSuccess) e = hipModuleGetFunction(&m.window_blocks, m.module, code->window_blocks.c_str());
+    if (e == hipSuccess) e = hipModuleGetFunction(&m.logp, m.module, code->logp.c_str());
+    if (e != hipSuccess) {
+        if (m.module) (void)hipModuleUnload(m.module);
+        err = std::string("program target: loading the code object: ") + hipGetErrorString(e);
+        return 2;
+    }
+    m.code = code;          // (the cache keeps the code object alive with the module)
+    g_module_cache.emplace(key, m);
+    out = m;
+    return 0;
+}
+
+}  // namespace demcz_prog

@@ -79,6 +79,12 @@ class HipEngine:
         rc = self._L.demcz_create(C.byref(self._h), C.byref(cfg))
         if rc != 0:
             raise DemczError(rc, (self._L.demcz_last_error(None) or b"").decode())
+        if cfg.target_kind == _lib.TARGET_PROGRAM:
+            try:
+                self._chk(target.attach(self._L, self._h))
+            except DemczError:
+                self.close()
+                raise
 
     # -- plumbing -----------------------------------------------------------------------------
     def _chk(self, rc):

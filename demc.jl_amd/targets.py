@@ -2,8 +2,10 @@
 
 The reference takes an arbitrary Julia closure ``logobj(x)::Float64`` (src/demcz.jl:189).  The
 three closures its tests and examples build are available as device targets, evaluated inside
-the chain-update kernel; any other Python callable is driven through the host-closure mode
-(``demcz_propose`` / ``demcz_accept_commit``), one batch of N proposals per round trip.
+the chain-update kernel; any other log-density can be written as a small HIP C++ function
+(``ProgramTarget``), which the library compiles at run time into the same kernel; a Python
+callable is driven through the host-closure mode (``demcz_propose`` / ``demcz_accept_commit``),
+one batch of N proposals per round trip.
 """
 from __future__ import annotations
 
@@ -95,5 +97,42 @@ class LinRegSSETarget:
         return dict(kind="linreg_sse", design=self.design, y=self.y)
 
 
+class ProgramTarget:
+    """A log-density written as HIP C++ and compiled for the device at run time (``demcz_set_program``, include/demcz.h).
+
+    ``source`` defines ``__device__ double demcz_logobj(const double* x, const double* data, int64_t ndata)``: ``x`` holds the
+    ``DEMCZ_D`` (= ``d``) values of the proposal, ``data`` the ``ndata`` doubles of ``data`` (device memory, read-only).  The
+    program is compiled with ``--offload-arch=gfx950 -O3 -ffp-contract=off`` followed by ``options`` (e.g. ``["-DNOBS=40"]``):
+    a fused multiply-add happens only where ``fma()`` is written.  ``d`` must be in 1..32.
+    """
+    kind = _lib.TARGET_PROGRAM
+
+    def __init__(self, source: str, d: int, data=None, options=()):
+        self.source = str(source)
+        self.d = int(d)
+        self.data = None if data is None else np.ascontiguousarray(np.ravel(data), dtype=np.float64)
+        self.options = (options,) if isinstance(options, str) else tuple(str(o) for o in options)
+
+    def _args(self):
+        return self.source.encode(), " ".join(self.options).encode()
+
+    def check(self):
+        """Compile the program (no device needed); raises ``DemczError`` with the compiler log if it does not compile."""
+        L = _lib.load()
+        src, opts = self._args()
+        rc = L.demcz_program_check(self.d, src, opts)
+        if rc != 0:
+            raise _lib.DemczError(rc, (L.demcz_last_error(None) or b"").decode())
+
+    def fill(self, cfg, keep):
+        pass                # (the program and its data go to the handle after demcz_create: attach)
+
+    def attach(self, L, h):
+        """``demcz_set_program`` on a freshly created handle; returns the status."""
+        src, opts = self._args()
+        n = 0 if self.data is None else self.data.size
+        return L.demcz_set_program(h, src, opts, _lib.ptr(self.data) if n else None, n)
+
+
 def is_device_target(obj) -> bool:
-    return isinstance(obj, (MvNormalTarget, IsoQuadTarget, LinRegSSETarget))
+    return isinstance(obj, (MvNormalTarget, IsoQuadTarget, LinRegSSETarget, ProgramTarget))

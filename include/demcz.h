@@ -59,7 +59,8 @@ enum demcz_target_kind {
     DEMCZ_TARGET_MVNORMAL = 0,    /* logpdf(MvNormal(mu, Sigma), x)   test/example_normpdf.jl:13-16 */
     DEMCZ_TARGET_ISO_QUAD = 1,    /* -sum((x - mu).^2)                test/test_anneal.jl:10        */
     DEMCZ_TARGET_LINREG_SSE = 2,  /* -0.5*sum((y - X*b).^2)           test/example_linreg.jl:32     */
-    DEMCZ_TARGET_HOST_CALLBACK = 3 /* arbitrary closure on the host: demcz_propose/accept_commit    */
+    DEMCZ_TARGET_HOST_CALLBACK = 3, /* arbitrary closure on the host: demcz_propose/accept_commit   */
+    DEMCZ_TARGET_PROGRAM = 4      /* a log-density written as HIP C++, compiled at run time: demcz_set_program */
 };
 
 /* Mirrors the fields of DEMCopt the hot path reads (src/DEMC.jl:24-39: N, K, Nblocks,
@@ -103,6 +104,26 @@ typedef struct demcz_config {
 
 #define DEMCZ_LAYOUT_SPLIT 100
 #define DEMCZ_LAYOUT_SPLIT_WAVE 164
+
+/* Program targets (DEMCZ_TARGET_PROGRAM): the closure of demcz.jl:189 as a small HIP C++ function the library compiles for
+ * gfx950 at run time (hipRTC) together with its one-lane window kernel, so that it runs on the device like a built-in target
+ * (same Philox streams, draw order, history, archive, R-hat check and annealing; one launch per K-window).  The source defines
+ *     __device__ double demcz_logobj(const double* x, const double* data, int64_t ndata);
+ * x: the DEMCZ_D (= d, a macro the program may use) values of the proposal; data: the ndata doubles given to demcz_set_program
+ * (device memory, read-only).  Compiled with --offload-arch=gfx950 -O3 -ffp-contract=off followed by `options` (space-separated,
+ * e.g. "-DNOBS=1000"; may be NULL): with contraction off a fused multiply-add happens only where fma() is written, so what the
+ * source says is what is computed, bit for bit.  Handles of a program target take lanes_per_chain 0 or 1 (both: one lane per
+ * chain) and 1 <= d <= 32; the target fields of demcz_config are not read.
+ *   demcz_program_check  compiles the program for dimension d and needs no device.  DEMCZ_OK, or DEMCZ_ERR_INVALID_ARGUMENT with
+ *                        the compiler log (user's line numbers, file "program") in demcz_last_error(NULL).
+ *   demcz_set_program    compiles the program (or takes it from the process-wide cache: a second handle with the same program and
+ *                        options does not recompile), loads it on the handle's device and copies data (ndata >= 0 doubles, NULL
+ *                        when 0) to device memory the handle owns.  Once per handle, before the first demcz_set_state; until it
+ *                        has succeeded demcz_set_state and the calls that evaluate the target return DEMCZ_ERR_STATE.  A compile
+ *                        error is DEMCZ_ERR_INVALID_ARGUMENT with the log in demcz_last_error(h); the handle stays usable for a
+ *                        corrected demcz_set_program. */
+int32_t demcz_program_check(int32_t d, const char* source, const char* options);
+int32_t demcz_set_program(demcz_handle* h, const char* source, const char* options, const double* data, int64_t ndata);
 
 /* Version of this header's ABI; demcz_abi_version() must return the same number. */
 #define DEMCZ_ABI_VERSION 1

@@ -38,6 +38,13 @@ function MvNormalTarget(μ, Σ)
 end
 struct IsoQuadTarget <: DeviceTarget; μ::Vector{Float64}; end                       # -sum((x .- μ).^2)
 struct LinRegSSETarget <: DeviceTarget; X::Matrix{Float64}; y::Vector{Float64}; end  # -0.5*sum((y .- X*b).^2)
+# any other log-density as HIP C++, compiled for the device at run time (include/demcz.h: demcz_set_program): `source` defines
+#     __device__ double demcz_logobj(const double* x, const double* data, int64_t ndata)
+# over the DEMCZ_D = d values of x and the doubles of `data`; `options` are extra compiler switches, e.g. ["-DNOBS=40"]
+struct ProgramTarget <: DeviceTarget
+    source::String; d::Int; data::Vector{Float64}; options::Vector{String}
+end
+ProgramTarget(source, d; data=Float64[], options=String[]) = ProgramTarget(String(source), Int(d), Vector{Float64}(data), Vector{String}(options))
 
 # ---- C ABI ----------------------------------------------------------------------------------------------
 struct DemczConfig
@@ -70,13 +77,22 @@ function create(t::LogObj, N, d, K, Mcap, Gcap, blockindex, eps_scale, seed; dev
             t isa MvNormalTarget ? (Int32(0), pointer(t.μ), pointer(t.W), t.c0, Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL), 0) :
             t isa IsoQuadTarget ? (Int32(1), pointer(t.μ), Ptr{Float64}(C_NULL), 0.0, Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL), 0) :
             t isa LinRegSSETarget ? (Int32(2), Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL), 0.0, pointer(t.X), pointer(t.y), size(t.X, 1)) :
+            t isa ProgramTarget ? (Int32(4), Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL), 0.0, Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL), 0) :
             (Int32(3), Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL), 0.0, Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL), 0)   # DEMCZ_TARGET_HOST_CALLBACK
         cfg = DemczConfig(N, chain_id0, d, K, Mcap, Gcap, length(blockindex), pointer(offs), pointer(idx), pointer(eps),
                           UInt64(seed), device_id, kind, mu, W, c0, design, y, nobs, C_NULL, 0, 0)
         chk(ccall((:demcz_create, libdemcz), Int32, (Ref{Ptr{Cvoid}}, Ref{DemczConfig}), h, cfg))   # config is copied
     end
+    if t isa ProgramTarget         # compiled (or taken from the process-wide cache) and loaded before set_state
+        rc = GC.@preserve t ccall((:demcz_set_program, libdemcz), Int32, (Ptr{Cvoid}, Cstring, Cstring, Ptr{Float64}, Int64),
+                                  h[], t.source, join(t.options, " "), isempty(t.data) ? C_NULL : pointer(t.data), length(t.data))
+        rc == 0 || (err = DemczError(rc, lasterr(h[])); destroy(h[]); throw(err))
+    end
     h[]
 end
+# compile a program target without a device: throws DemczError with the compiler log
+check(t::ProgramTarget) = chk(ccall((:demcz_program_check, libdemcz), Int32, (Int32, Cstring, Cstring),
+                                    Int32(t.d), t.source, join(t.options, " ")))
 destroy(h) = ccall((:demcz_destroy, libdemcz), Int32, (Ptr{Cvoid},), h)
 
 set_state(h, X::Matrix{Float64}, logp, Z::Matrix{Float64}) =
