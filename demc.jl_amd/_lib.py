@@ -21,6 +21,7 @@ ABI_VERSION = 1
 # demcz_config.lanes_per_chain beyond 0 / 1 / 8 / 16 (include/demcz.h)
 LAYOUT_SPLIT = 100          # producer / consumer split, eight replicated (d <= 10) or sixteen cooperating lanes per chain
 LAYOUT_SPLIT_WAVE = 164     # the split with one wavefront per chain, five generations per pass (MvNormal, d = 2..5, 8, 10, 20)
+LAYOUT_PROGRAM_WAVE = 264   # a program target on that wave-per-chain layout (opt-in; d = 2..32, N <= 2048, one full block)
 
 TARGET_MVNORMAL, TARGET_ISO_QUAD, TARGET_LINREG_SSE, TARGET_HOST_CALLBACK, TARGET_PROGRAM = 0, 1, 2, 3, 4
 OK, ERR_INVALID_ARGUMENT, ERR_HIP, ERR_CAPACITY, ERR_STATE, ERR_NO_DEVICE, ERR_COMM = range(7)
@@ -46,6 +47,7 @@ SYMBOLS = [
     "demcz_debug_kernel_counts", "demcz_pool_trim", "demcz_debug_kernel_name", "demcz_peer_group", "demcz_get_peer_status", "demcz_peer_export", "demcz_peer_attach",
     "demcz_peer_detach", "demcz_get_peer_ping", "demcz_set_live_rearms", "demcz_get_live_rearms",
     "demcz_closure_buffers", "demcz_program_check", "demcz_set_program",
+    "demcz_program_check_layout",
 ]
 
 
@@ -187,6 +189,7 @@ def load():
     L.demcz_get_live_rearms.argtypes = [C.c_void_p, _ip, _ip]
     L.demcz_debug_kernel_name.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
     L.demcz_program_check.argtypes = [C.c_int32, C.c_char_p, C.c_char_p]
+    L.demcz_program_check_layout.argtypes = [C.c_int32, C.c_char_p, C.c_char_p, C.c_int32]
     L.demcz_set_program.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, _dp, C.c_int64]
     L.demcz_get_archive_pinned.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), _lp]
     L.demcz_get_kernel_time_series.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _ip]

@@ -368,6 +368,9 @@ struct demcz_handle {
     // cfg.nobs (the TargetParams slots only the regression reads)
     bool prog_ready = false;
     demcz_prog::Module prog;
+    // created with DEMCZ_LAYOUT_PROGRAM_WAVE: lanes == DEMCZ_LAYOUT_SPLIT, split_kind == 4, and the consumer is the program's own
+    // window_kernel_ps / _pw<TARGET_PROGRAM, d, LIVE, TEMPER> (prog.wave); records, producer, LIVE machinery: the library's
+    bool prog_wave = false;
 };
 
 #define HIPCHK(h, expr)                                                                          \
@@ -710,9 +713,14 @@ extern "C" int32_t demcz_create(demcz_handle** out, const demcz_config* cfg)
         return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT,
                     "demcz_create: need N>=1, 1<=d<=64, K>=1, Mcap>=2, Gcap>=0, Nblocks>=1 and block/eps tables");
     if (cfg->lanes_per_chain != 0 && cfg->lanes_per_chain != 1 && cfg->lanes_per_chain != 8 && cfg->lanes_per_chain != 16 &&
-        cfg->lanes_per_chain != DEMCZ_LAYOUT_SPLIT && cfg->lanes_per_chain != DEMCZ_LAYOUT_SPLIT_WAVE)
+        cfg->lanes_per_chain != DEMCZ_LAYOUT_SPLIT && cfg->lanes_per_chain != DEMCZ_LAYOUT_SPLIT_WAVE &&
+        cfg->lanes_per_chain != DEMCZ_LAYOUT_PROGRAM_WAVE)
         return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT,
-                    "demcz_create: lanes_per_chain must be 0 (auto), 1, 8, 16, DEMCZ_LAYOUT_SPLIT or DEMCZ_LAYOUT_SPLIT_WAVE");
+                    "demcz_create: lanes_per_chain must be 0 (auto), 1, 8, 16, DEMCZ_LAYOUT_SPLIT, DEMCZ_LAYOUT_SPLIT_WAVE or (program targets) "
+                    "DEMCZ_LAYOUT_PROGRAM_WAVE");
+    if (cfg->lanes_per_chain == DEMCZ_LAYOUT_PROGRAM_WAVE && cfg->target_kind != DEMCZ_TARGET_PROGRAM)
+        return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_create: DEMCZ_LAYOUT_PROGRAM_WAVE is the wave-per-chain layout of program targets: "
+                                                         "target_kind must be DEMCZ_TARGET_PROGRAM (built-in targets: DEMCZ_LAYOUT_SPLIT_WAVE)");
     const int d = cfg->d;
     // validate blocks: offsets ascending, indices within range and unique inside a block
     if (cfg->block_offsets[0] != 0) return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, "block_offsets[0] must be 0");
@@ -740,12 +748,28 @@ extern "C" int32_t demcz_create(demcz_handle** out, const demcz_config* cfg)
         break;
     case DEMCZ_TARGET_HOST_CALLBACK: break;
     case DEMCZ_TARGET_PROGRAM:
-        // (the program is compiled into the one-lane window kernel only: the split, wave-per-chain and cooperating-lane layouts
-        //  are not built for it)
-        if (cfg->lanes_per_chain != 0 && cfg->lanes_per_chain != 1)
-            return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_create: a program target runs one lane per chain: lanes_per_chain must be 0 or 1");
+        // (the program is compiled into the one-lane window kernel or, on request, into the wave-per-chain consumer -- one whole
+        //  candidate per lane; the cooperating-lane layouts split the log-density across lanes, which a user's scalar function
+        //  cannot be)
+        if (cfg->lanes_per_chain != 0 && cfg->lanes_per_chain != 1 && cfg->lanes_per_chain != DEMCZ_LAYOUT_PROGRAM_WAVE)
+            return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_create: a program target runs one lane per chain: lanes_per_chain must be 0 or 1 "
+                                                             "(or DEMCZ_LAYOUT_PROGRAM_WAVE: one wavefront per chain)");
         if (cfg->d > demcz_prog::MAX_PROGRAM_D)
             return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_create: a program target needs 1 <= d <= 32");
+        if (cfg->lanes_per_chain == DEMCZ_LAYOUT_PROGRAM_WAVE) {
+            bool one_block = cfg->Nblocks == 1 && cfg->block_offsets[1] == d;
+            for (int p = 0; one_block && p < d; ++p) one_block = cfg->block_indices[p] == p;
+            if (!one_block)
+                return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_create: DEMCZ_LAYOUT_PROGRAM_WAVE needs one block 0..d-1 in order (block updates run one lane per chain)");
+            if (d < demcz_prog::WAVE_MIN_D)
+                return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_create: DEMCZ_LAYOUT_PROGRAM_WAVE needs 2 <= d <= 32");
+            if (cfg->N > PS_MAX_N)
+                return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_create: DEMCZ_LAYOUT_PROGRAM_WAVE needs N <= " + std::to_string(PS_MAX_N) +
+                                                                 " (one wavefront per chain: PS_MAX_N)");
+            if (!(cfg->Mcap <= 0xffffffffll && (double)cfg->Mcap * 8.0 * (((d + 7) / 8) * 8) < 4294967296.0))
+                return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_create: DEMCZ_LAYOUT_PROGRAM_WAVE needs an archive reachable by 32-bit offsets: "
+                                                                 "Mcap * 8 * (d rounded up to a multiple of 8) < 2^32");
+        }
         break;
     default: return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, "unknown target_kind");
     }
@@ -845,6 +869,15 @@ extern "C" int32_t demcz_create(demcz_handle** out, const demcz_config* cfg)
         const bool ps_ok = idx32 && h->full_block && ps_available(cfg->target_kind, d);
         const int per_wg_default = h->split_per_wg;
         h->split_kind = 0;
+        if (cfg->lanes_per_chain == DEMCZ_LAYOUT_PROGRAM_WAVE) {
+            // (validated above.  How many chains a LIVE launch holds depends on the program's registers and is known once
+            //  demcz_set_program has compiled it: live_wg_capacity.  More than that, up to PS_MAX_N: one launch per K-window.)
+            h->prog_wave = true;
+            h->lanes = DEMCZ_LAYOUT_SPLIT;
+            h->split_kind = 4;
+            h->split_per_wg = PS_CHAINS;
+            h->split_lanes = 0;
+        } else
         if (cfg->lanes_per_chain == DEMCZ_LAYOUT_SPLIT_WAVE || (cfg->lanes_per_chain == 0 && ps_ok && cfg->N <= PS_MAX_N && cfg->K >= 2 && !getenv("DEMCZ_NO_PS"))) {
             // (us per K-window at d=5, one wave per chain / eight replicated lanes: see DESIGN.md, K1g; K = 1 leaves a
             //  pass one generation: 1.05 against 0.99 us per generation, scripts/k_small.py)
@@ -924,7 +957,7 @@ extern "C" int32_t demcz_create(demcz_handle** out, const demcz_config* cfg)
     h->ZS = (d <= 1) ? 2 : (d <= 2) ? 2 : (d <= 4) ? 4 : ((d + 7) / 8) * 8;     // 16-byte aligned rows; d=5 -> one 64-byte line
     {
         size_t zbytes = (size_t)cfg->Mcap * h->ZS * sizeof(double);
-        if (h->lanes == DEMCZ_LAYOUT_SPLIT && h->split_kind == 4 && d <= 5 && !getenv("DEMCZ_NO_PS2")) {
+        if (h->lanes == DEMCZ_LAYOUT_SPLIT && h->split_kind == 4 && d <= 5 && !h->prog_wave && !getenv("DEMCZ_NO_PS2")) {
             // (record buffers as demcz_run would size them: a LIVE launch's span, bounded by the history window; a caller that
             //  outruns the arena gets separate buffers and the general kernel)
             const int64_t per_gen = (int64_t)(d + 2) * N_for_arena * (int64_t)sizeof(double);
@@ -1287,7 +1320,19 @@ extern "C" int32_t demcz_program_check(int32_t d, const char* source, const char
 {
     std::shared_ptr<const demcz_prog::Code> code;
     std::string err;
-    if (demcz_prog::get_code(d, source, options, code, err) != 0) return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, err);
+    if (demcz_prog::get_code(d, source, options, demcz_prog::UNIT_ONE_LANE, code, err) != 0) return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, err);
+    return DEMCZ_OK;
+}
+
+extern "C" int32_t demcz_program_check_layout(int32_t d, const char* source, const char* options, int32_t lanes_per_chain)
+{
+    if (lanes_per_chain != 0 && lanes_per_chain != 1 && lanes_per_chain != DEMCZ_LAYOUT_PROGRAM_WAVE)
+        return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_program_check_layout: a program target runs one lane per chain: lanes_per_chain must be 0 or 1 "
+                                                         "(or DEMCZ_LAYOUT_PROGRAM_WAVE: one wavefront per chain)");
+    std::shared_ptr<const demcz_prog::Code> code;
+    std::string err;
+    const int unit = (lanes_per_chain == DEMCZ_LAYOUT_PROGRAM_WAVE) ? demcz_prog::UNIT_WAVE : demcz_prog::UNIT_ONE_LANE;
+    if (demcz_prog::get_code(d, source, options, unit, code, err) != 0) return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, err);
     return DEMCZ_OK;
 }
 
@@ -1303,7 +1348,9 @@ extern "C" int32_t demcz_set_program(demcz_handle* h, const char* source, const 
         return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_program: need ndata >= 0 and data for ndata > 0");
     std::shared_ptr<const demcz_prog::Code> code;
     std::string err;
-    if (demcz_prog::get_code(h->cfg.d, source, options, code, err) != 0) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, err);
+    // (a handle compiles the unit of ITS layout only: the wave unit is never built for a one-lane handle, nor the reverse)
+    if (demcz_prog::get_code(h->cfg.d, source, options, h->prog_wave ? demcz_prog::UNIT_WAVE : demcz_prog::UNIT_ONE_LANE, code, err) != 0)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, err);
     demcz_prog::Module mod;
     if (demcz_prog::get_module(code, h->cfg.device_id, mod, err) != 0) return fail(h, DEMCZ_ERR_HIP, err);
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
@@ -1314,6 +1361,7 @@ extern "C" int32_t demcz_set_program(demcz_handle* h, const char* source, const 
     h->cfg.nobs = ndata;
     h->prog = mod;
     h->prog_ready = true;
+    h->live_wg_cap = -1;            // (wave layout: residency is the program's own kernel's)
     return DEMCZ_OK;
 }
 
@@ -1553,7 +1601,10 @@ static int32_t launch_window_pc(demcz_handle* h, const WindowParams& P, bool liv
             // (wave-per-chain consumers at d > 20 take 70-110 KB of a CU's LDS themselves: the producers' allocation is what is left)
             size_t big_d = throttle_env;
             if (h->split_kind == 4 && P.d > 20) {
-                const size_t clds = (size_t)pw_query(h->cfg.target_kind == DEMCZ_TARGET_ISO_QUAD ? TARGET_ISO_QUAD : TARGET_MVNORMAL, P.d, PW_QUERY_LIVE_LDS_BYTES);
+                int plds = 0;       // (program: its own LIVE kernel's static LDS)
+                if (h->prog_wave && (!h->prog_ready || hipFuncGetAttribute(&plds, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, h->prog.wave[1][0]) != hipSuccess)) plds = (int)ML_MAX_DYNAMIC_LDS;
+                const size_t clds = h->prog_wave ? (size_t)plds :
+                                    (size_t)pw_query(h->cfg.target_kind == DEMCZ_TARGET_ISO_QUAD ? TARGET_ISO_QUAD : TARGET_MVNORMAL, P.d, PW_QUERY_LIVE_LDS_BYTES);
                 const size_t room = (clds + 4096 < ML_MAX_DYNAMIC_LDS) ? ML_MAX_DYNAMIC_LDS - clds - 4096 : 8192;
                 big_d = std::max<size_t>(8192, std::min<size_t>(throttle_env, room));
             }
@@ -1597,6 +1648,14 @@ static int32_t launch_window_pc(demcz_handle* h, const WindowParams& P, bool liv
                 const dim3 g((unsigned)grid), wgl(64 * LR16_WAVES);
                 if (live) hipLaunchKernelGGL((window_kernel_lr8s<10, true>), g, wgl, dynl, h->stream, P);
                 else hipLaunchKernelGGL((window_kernel_lr8s<10, false>), g, wgl, dynl, h->stream, P);
+            } else if (h->prog_wave) {
+                // the program's own wave-per-chain consumer (demcz_program.hip, UNIT_WAVE), with the grid and workgroup shape of
+                // the built-in one (its LDS is static)
+                if (!h->prog_ready) return fail(h, DEMCZ_ERR_STATE, "demcz_run: program target: call demcz_set_program first");
+                WindowParams Pv = P;
+                void* args[] = {&Pv};
+                HIPCHK(h, hipModuleLaunchKernel(h->prog.wave[live ? 1 : 0][P.temperature ? 1 : 0], (unsigned)grid, 1, 1,
+                                                64 * (PS_CHAINS + (live ? 1 : 0)), 1, 1, 0, h->stream, args, nullptr));
             } else
             switch (P.d) {
             case 2: launch_ps<TARGET_MVNORMAL, 2>(h, P, grid, live); break;
@@ -1704,7 +1763,7 @@ static int32_t rec_reserve(demcz_handle* h, int64_t gens)
 static bool ps2_applicable(const demcz_handle* h, const WindowParams& P)
 {
     static const bool off = getenv("DEMCZ_NO_PS2") != nullptr;
-    if (off || h->split_kind != 4 || P.d < 2 || P.d > 5 || !h->arena || !h->rec_in_arena) return false;
+    if (off || h->split_kind != 4 || h->prog_wave || P.d < 2 || P.d > 5 || !h->arena || !h->rec_in_arena) return false;
     if (P.temperature && (P.temperature < h->arena_temp || P.temperature >= h->arena_temp + h->arena_gens)) return false;
     if (P.K % PS2_R != 0 || P.to_boundary % PS2_R != 0 || P.ngen % PS2_R != 0 || P.ngen < PS2_R) return false;
     if (P.chain && (!h->hist_joint || (double)h->cfg.N * (h->cfg.d + 1) * (double)h->cfg.Gcap * 8.0 >= 4293918720.0)) return false;
@@ -1831,7 +1890,7 @@ static int32_t launch_window(demcz_handle* h, const WindowParams& P, bool live =
         h->last_temper = P.temperature ? 1 : 0;
         h->last_ps2 = (h->lanes == DEMCZ_LAYOUT_SPLIT && h->split_kind == 4 && !h->lr_spec && ps2_applicable(h, P) && (!h->ps_dual || h->dual_now)) ? 1 : 0;
         h->last_dual = h->dual_now ? 1 : 0;
-        h->last_pw_reg = (h->lanes == DEMCZ_LAYOUT_SPLIT && h->split_kind == 4 && P.d > 5 && !pw_matrix_form(h) && pw_regular(P, live)) ? 1 : 0;
+        h->last_pw_reg = (h->lanes == DEMCZ_LAYOUT_SPLIT && h->split_kind == 4 && !h->prog_wave && P.d > 5 && !pw_matrix_form(h) && pw_regular(P, live)) ? 1 : 0;
     }
     if (h->snap_pending) {
         // the redo snapshot of the state (demcz_run): window_kernel_ps2 writes it as it loads the state -- two 5 us copy launches
@@ -2350,6 +2409,15 @@ static int64_t live_wg_capacity(demcz_handle* h)
         case 5: per_cu = ps2d_live_blocks_per_cu<5>(); break;
         default: per_cu = 0;
         }
+    } else if (h->split_kind == 4 && h->prog_wave) {
+        // the program's own LIVE kernels: a register-hungry user function lowers what fits a CU (nothing is known, and nothing
+        // is remembered, before demcz_set_program)
+        if (!h->prog_ready) return 0;
+        int a = 0, b = 0;
+        if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&a, h->prog.wave[1][0], 64 * (PS_CHAINS + 1), 0) != hipSuccess) a = 0;
+        if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&b, h->prog.wave[1][1], 64 * (PS_CHAINS + 1), 0) != hipSuccess) b = 0;
+        per_cu = std::min(a, b);
+        if (h->cfg.d > 20 && per_cu == 1) per_cu = 2;      // (one workgroup per CU, every CU: as for the built-in kernel below)
     } else if (h->split_kind == 4) {
         switch (h->cfg.d) {
         case 2: per_cu = std::min(ps_live_blocks_per_cu<2>(), ps2_live_blocks_per_cu<2>()); break;
@@ -3495,6 +3563,10 @@ extern "C" int32_t demcz_comm_init(demcz_handle* h, const void* unique_id_128B, 
 {
     if (!h || !unique_id_128B || nranks < 1 || rank < 0 || rank >= nranks) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (h->comm) return fail(h, DEMCZ_ERR_STATE, "demcz_comm_init: communicator already initialised");
+    if (h->prog_wave)
+        return fail(h, DEMCZ_ERR_STATE, "demcz_comm_init: a program target on DEMCZ_LAYOUT_PROGRAM_WAVE does not join a communicator (sharded in-launch "
+                                        "hand-off is not built for programs): shard it from the host (demcz_set_external_append, demcz_append_rows) "
+                                        "or use the one-lane layout");
     if (!h->live_log.empty()) { int32_t rcv = live_verify(h); if (rcv) return rcv; }
     if (h->cfg.chain_id0 != (int64_t)rank * h->cfg.N)
         return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_comm_init: chain_id0 must be rank * N (equal shards in rank order)");
@@ -3520,6 +3592,9 @@ extern "C" int32_t demcz_peer_group(demcz_handle** handles, int32_t R)
         if (!m) return DEMCZ_ERR_INVALID_ARGUMENT;
         for (int q = 0; q < r; ++q) if (handles[q] == m) return fail(m, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_peer_group: a handle appears twice");
         if (m->comm || m->peer_mode != 0) return fail(m, DEMCZ_ERR_STATE, "demcz_peer_group: handle is already sharded");
+        if (m->prog_wave)
+            return fail(m, DEMCZ_ERR_STATE, "demcz_peer_group: a program target on DEMCZ_LAYOUT_PROGRAM_WAVE does not join a replica group (sharded "
+                                            "in-launch hand-off is not built for programs): shard it from the host or use the one-lane layout");
         if (m->lag != 0 || m->external_append) return fail(m, DEMCZ_ERR_STATE, "demcz_peer_group: append lag 0 and library-owned appends only");
         if (!m->live_log.empty()) { int32_t rcv = live_verify(m); if (rcv) return rcv; }
         if (m->cfg.device_id != h0->cfg.device_id || m->cfg.N != h0->cfg.N || m->cfg.d != h0->cfg.d || m->cfg.K != h0->cfg.K ||
@@ -4008,7 +4083,7 @@ extern "C" int32_t demcz_get_info(const demcz_handle* h, int64_t* M, int64_t* la
     if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (M) *M = h->M_app;
     if (launches_window) *launches_window = h->launches;
-    if (lanes_per_chain) *lanes_per_chain = (h->split_kind == 4) ? DEMCZ_LAYOUT_SPLIT_WAVE : h->lanes;
+    if (lanes_per_chain) *lanes_per_chain = h->prog_wave ? DEMCZ_LAYOUT_PROGRAM_WAVE : (h->split_kind == 4) ? DEMCZ_LAYOUT_SPLIT_WAVE : h->lanes;
     return DEMCZ_OK;
 }
 
@@ -4282,6 +4357,7 @@ extern "C" int32_t demcz_debug_kernel_name(const demcz_handle* h, char* buf, int
     const bool lr = h->cfg.target_kind == DEMCZ_TARGET_LINREG_SSE;
     if (h->lanes == DEMCZ_LAYOUT_SPLIT) {
         if (h->lr_spec) snprintf(tmp, sizeof tmp, "window_kernel_lr8s<%d, %s>", d, lv);
+        else if (h->prog_wave) snprintf(tmp, sizeof tmp, "%s<%d, %d, %s, %s> (program)", d <= 5 ? "window_kernel_ps" : "window_kernel_pw", (int)TARGET_PROGRAM, d, lv, tm);
         else if (h->split_kind == 4 && d <= 5) snprintf(tmp, sizeof tmp, "%s<%s, %d, %s, %s>", (h->last_ps2 && h->last_dual) ? "window_kernel_ps2d" : h->last_ps2 ? "window_kernel_ps2" : "window_kernel_ps", tg, d, lv, tm);
         else if (h->split_kind == 4 && h->last_live && pw_matrix_form(h)) snprintf(tmp, sizeof tmp, "window_kernel_pw<%s, %d, %s, %s, true>", tg, d, lv, tm);
         else if (h->split_kind == 4 && h->last_pw_reg) snprintf(tmp, sizeof tmp, "window_kernel_pw<%s, %d, %s, %s, false, true>", tg, d, lv, tm);

@@ -74,8 +74,15 @@ __global__ void __launch_bounds__(64 * PRODUCE_WAVES) produce_kernel(const Windo
 template <int TARGET, int D, bool LIVE, bool TEMPER>
 __global__ void __launch_bounds__(64 * (PS_CHAINS + (LIVE ? 1 : 0)), 3) window_kernel_ps(const WindowParams P)
 {
+#ifdef DEMCZ_PROGRAM_TARGET
+    // (the unit hipRTC compiles for a program target on this layout, demcz_program.hip: lane n calls the user's demcz_logobj on
+    //  candidate n -- the one place of the kernel that knows the target)
+    static_assert(TARGET == TARGET_MVNORMAL || TARGET == TARGET_ISO_QUAD || TARGET == TARGET_PROGRAM, "split layout: MvNormal / isotropic / program targets");
+#else
     static_assert(TARGET == TARGET_MVNORMAL || TARGET == TARGET_ISO_QUAD, "split layout: MvNormal / isotropic targets");
+#endif
     static_assert(D >= 2 && D <= 5, "a pass's rows, normals, log u and indices are one 64-lane DMA");
+    constexpr bool PROG = (TARGET == TARGET_PROGRAM);      // no target constants: the program has its own (TargetParams::design / nobs)
     constexpr int HW = (D + 1) / 2;                        // 16-byte pieces of an archive row
     constexpr int ZSC = (D <= 2) ? 2 : (D <= 4) ? 4 : 8;   // archive row stride in doubles (demcz_create: ZS)
     constexpr int ZSH = (ZSC == 2) ? 4 : (ZSC == 4) ? 5 : 6;      // log2 of the row stride in bytes
@@ -230,14 +237,16 @@ __global__ void __launch_bounds__(64 * (PS_CHAINS + (LIVE ? 1 : 0)), 3) window_k
     const bool hist = P.chain != nullptr;
 
     // target constants (the arithmetic is window_kernel_pc8's)
-    double muc[D], Wc[(TARGET == TARGET_MVNORMAL) ? D * (D + 1) / 2 : 1];
+    [[maybe_unused]] double muc[D], Wc[(TARGET == TARGET_MVNORMAL) ? D * (D + 1) / 2 : 1];
+    if constexpr (!PROG) {
 #pragma unroll
-    for (int p = 0; p < D; ++p) muc[p] = P.tp.mu[p];
+        for (int p = 0; p < D; ++p) muc[p] = P.tp.mu[p];
+    }
     if constexpr (TARGET == TARGET_MVNORMAL) {
 #pragma unroll
         for (int i = 0; i < D * (D + 1) / 2; ++i) Wc[i] = P.tp.Wp[i];
     }
-    double c0v = P.tp.c0;          // (kept in a vector register: see the W entries below)
+    [[maybe_unused]] double c0v = PROG ? 0.0 : P.tp.c0;          // (kept in a vector register: see the W entries below)
 
     // ---- passes of the launch.  A pass ends at a K boundary, at the launch's end or after PS_R generations.  The current
     //      pass and the five after it are a queue of nibbles (bits 0-2 length, bit 3 "ends on a boundary", entry k at bits
@@ -311,12 +320,15 @@ __global__ void __launch_bounds__(64 * (PS_CHAINS + (LIVE ? 1 : 0)), 3) window_k
         // would wait for the DMAs in flight as well -- every pass.  (The W entries stay in vector registers: as scalars
         // they and the state crowd the scalar file into spills.)
 #pragma unroll
-        for (int p = 0; p < D; ++p) asm volatile("" :: "v"(x[p]), "v"(muc[p]));
+        for (int p = 0; p < D; ++p) {
+            if constexpr (PROG) asm volatile("" :: "v"(x[p]));
+            else asm volatile("" :: "v"(x[p]), "v"(muc[p]));
+        }
         if constexpr (TARGET == TARGET_MVNORMAL) {
 #pragma unroll
             for (int i = 0; i < D * (D + 1) / 2; ++i) asm volatile("" : "+v"(Wc[i]));
         }
-        asm volatile("" : "+v"(c0v));
+        if constexpr (!PROG) asm volatile("" : "+v"(c0v));
         asm volatile("" :: "v"(lp), "v"(eps_p));
 #pragma unroll
         for (int k = 0; k < PS_AHEAD; ++k) asm volatile("" :: "v"(ixq[k]), "v"(pp[k]));
@@ -489,6 +501,22 @@ __global__ void __launch_bounds__(64 * (PS_CHAINS + (LIVE ? 1 : 0)), 3) window_k
         store_history();
         const bool bad_n = front(slot, qR(1), qR(1 + PS_AHEAD), g3, g5, true);
         double lpp;
+#ifdef DEMCZ_PROGRAM_TARGET
+        if constexpr (PROG) {
+            // The user's function, once per node, on the node lanes only (EXEC): lanes 0 and 32..63 hold no candidate of their
+            // own (the state / a shadow of node 1) and nothing of theirs is ever selected -- they take the state's log-density
+            // and issue none of the call's memory operations.
+            // The call brings vector-memory operations this kernel does not count (loads of `data`, scratch traffic of spills
+            // and of dynamically indexed local arrays), so the counted waits no longer prove anything by counting.  The drain
+            // behind the call does: every DMA is issued by front() above, in front of the call of ITS pass, and consumed by the
+            // counted wait of a LATER pass -- with this drain in between nothing issued before it is still in flight, whatever
+            // order loads, stores and scratch operations complete in.  The price: PS_AHEAD buys no
+            // overlap here -- a DMA's latency is exposed in the pass that issues it unless the call is long enough to cover it.
+            lpp = lp;
+            if (nodel) lpp = demcz_logobj(cand, P.tp.design, P.tp.nobs);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        } else
+#endif
         if constexpr (TARGET == TARGET_MVNORMAL) {
             double q = 0.0;
 #pragma unroll

@@ -58,7 +58,13 @@ template <int TARGET, int D, bool LIVE, bool TEMPER, bool MF = false, bool REG =
 __global__ void __launch_bounds__(64 * (PS_CHAINS + (LIVE ? 1 : 0)), pw_min_waves(D)) window_kernel_pw(const WindowParams P)
 {
     static_assert(!REG || (LIVE && PS_R == 5), "regular launches: LIVE, five generations a pass");
+#ifdef DEMCZ_PROGRAM_TARGET
+    static_assert(TARGET == TARGET_MVNORMAL || TARGET == TARGET_ISO_QUAD || TARGET == TARGET_PROGRAM, "split layout: MvNormal / isotropic / program targets");
+    static_assert(TARGET != TARGET_PROGRAM || (!MF && !REG), "program targets: the general form");
+#else
     static_assert(TARGET == TARGET_MVNORMAL || TARGET == TARGET_ISO_QUAD, "split layout: MvNormal / isotropic targets");
+#endif
+    constexpr bool PROG = (TARGET == TARGET_PROGRAM);      // (demcz_kernels_ps.h: no target constants, the user's function per node)
     static_assert(D >= 6 && D <= 32, "d <= 5: window_kernel_ps");
     static_assert(!MF || (LIVE && TARGET == TARGET_MVNORMAL && D > 16 && D <= 20 && PS_R == 5), "matrix form: MvNormal, 16 < d <= 20, LIVE");
     constexpr int HW = (D + 1) / 2;                        // 16-byte pieces of an archive row
@@ -94,6 +100,9 @@ __global__ void __launch_bounds__(64 * (PS_CHAINS + (LIVE ? 1 : 0)), pw_min_wave
 #ifndef PW_DDPP
 #define PW_DDPP 1
 #endif
+#if defined(DEMCZ_PROGRAM_TARGET) && PW_DDPP
+#error "the program unit is compiled with PW_DDPP = 0 (the generated texts are not embedded)"
+#endif
     constexpr bool DDPP = (PW_DDPP != 0) && !MF && PS_R == 5;
     // per generation of the pass: positions of a 16-lane row that take it in every row with takers, and the register pairs that
     // then hold its D increments (the generator's numbers; checked against each other in the generated text)
@@ -106,7 +115,9 @@ __global__ void __launch_bounds__(64 * (PS_CHAINS + (LIVE ? 1 : 0)), pw_min_wave
     }
     __shared__ double pub_rows[LIVE ? PS_CHAINS * PS_PUB * D : 1];
     __shared__ unsigned int pub_seq[PS_CHAINS], pub_done[PS_CHAINS], pub_exit[PS_CHAINS];
-    for (int e = threadIdx.x; e < D; e += blockDim.x) mul[e] = P.tp.mu[e];
+    if constexpr (!PROG) {
+        for (int e = threadIdx.x; e < D; e += blockDim.x) mul[e] = P.tp.mu[e];
+    }
     if constexpr (LIVE) {
         if (threadIdx.x < PS_CHAINS) { pub_seq[threadIdx.x] = 0u; pub_done[threadIdx.x] = 0u; pub_exit[threadIdx.x] = 0u; }
     }
@@ -583,7 +594,9 @@ __global__ void __launch_bounds__(64 * (PS_CHAINS + (LIVE ? 1 : 0)), pw_min_wave
 #pragma unroll
                 for (int q = 0; q < DD_NQMAX; ++q)
                     if (q < DD_NQ[u]) asm volatile("" : "+v"(Dg[u][q]));
+#ifndef DEMCZ_PROGRAM_TARGET        // (the program unit is compiled with PW_DDPP = 0: demcz_program.hip)
 #include "demcz_pw_ddpp_sel.inc"
+#endif
         } else {
 #pragma unroll
         for (int j = 0; j < PS_R; ++j) {
@@ -656,6 +669,16 @@ __global__ void __launch_bounds__(64 * (PS_CHAINS + (LIVE ? 1 : 0)), pw_min_wave
             for (int q = 0; q < D / 2; ++q) reinterpret_cast<double2*>(ct_w + lane * CR)[q] = make_double2(cand[2 * q], cand[2 * q + 1]);
             if constexpr (D & 1) ct_w[lane * CR + D - 1] = cand[D - 1];
         }
+#ifdef DEMCZ_PROGRAM_TARGET
+        if constexpr (PROG) {
+            // the user's function on the node lanes only, the others take the state's log-density; the drain behind the call is
+            // what makes the counted waits safe against the call's own vector-memory operations: this pass's DMAs were issued by
+            // front() above and are consumed two passes on (demcz_kernels_ps.h)
+            lpp = lp;
+            if (nodel) lpp = demcz_logobj(cand, P.tp.design, P.tp.nobs);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        } else
+#endif
         // The log-density: target_logp's operation sequence; mu from the workgroup's LDS copy
         {
             // W by lanes: the register pairs are asked for here, in front of the reads of mu, and pinned behind the subtraction --
@@ -692,7 +715,9 @@ __global__ void __launch_bounds__(64 * (PS_CHAINS + (LIVE ? 1 : 0)), pw_min_wave
                 // (round 4: W by lanes -- see the top of the file; the alternatives above are what it replaced)
 #pragma unroll
                 for (int r = 0; r < NWR; ++r) asm volatile("" : "+v"(Wr[r]));
+#ifndef DEMCZ_PROGRAM_TARGET
 #include "demcz_pw_wdpp_sel.inc"
+#endif
                 lpp = fma(-0.5, q, P.tp.c0);
             } else if constexpr (TARGET == TARGET_MVNORMAL) {
 #pragma unroll

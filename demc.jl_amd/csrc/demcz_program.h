@@ -12,25 +12,34 @@ namespace demcz_prog {
 
 constexpr int MAX_PROGRAM_D = 32;
 
-// One compiled program: the gfx950 code object and the mangled names of its three kernels.
+// The two units a program can be compiled into (demcz_program.hip, compose): the one-lane window kernel, or the wave-per-chain
+// consumers of the split layout (DEMCZ_LAYOUT_PROGRAM_WAVE: window_kernel_ps for d = 2..5, window_kernel_pw for d = 6..32).
+enum { UNIT_ONE_LANE = 0, UNIT_WAVE = 1 };
+constexpr int WAVE_MIN_D = 2;
+
+// One compiled program: the gfx950 code object and the mangled names of its kernels.
 struct Code {
     std::vector<char> object;
     std::string window_full;      // window_kernel<TARGET_PROGRAM, d, true>: one block covering 0..d-1 in order
     std::string window_blocks;    // window_kernel<TARGET_PROGRAM, d, false>: blocks from the CSR tables
-    std::string logp;             // logp_kernel<TARGET_PROGRAM>: the initial log_objcurrent
+    std::string logp;             // logp_kernel<TARGET_PROGRAM>: the initial log_objcurrent (both units)
+    std::string wave[2][2];       // UNIT_WAVE: window_kernel_ps / _pw<TARGET_PROGRAM, d, LIVE, TEMPER>, [LIVE][TEMPER] (the one-lane
+                                  // kernels are not in that unit, and these not in the one-lane unit)
     int d = 0;
+    int unit = UNIT_ONE_LANE;
 };
 
 // A code object loaded on one device (kept until the process exits).
 struct Module {
     hipModule_t module = nullptr;
     hipFunction_t window_full = nullptr, window_blocks = nullptr, logp = nullptr;
+    hipFunction_t wave[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
     std::shared_ptr<const Code> code;
 };
 
-// Compile `source` for dimension d (or take it from the process-wide cache).  Needs no device.  Returns 0, or 1 with the
-// compiler log (or what else went wrong) in err.
-int32_t get_code(int d, const char* source, const char* options, std::shared_ptr<const Code>& out, std::string& err);
+// Compile `source` for dimension d into `unit` (or take it from the process-wide cache, whose key includes the unit).  Needs no
+// device.  Returns 0, or 1 with the compiler log (or what else went wrong) in err.
+int32_t get_code(int d, const char* source, const char* options, int unit, std::shared_ptr<const Code>& out, std::string& err);
 // Load a code object on `device` (or take it from the cache).  Returns 0, or 2 (a HIP error) with the message in err.
 int32_t get_module(const std::shared_ptr<const Code>& code, int device, Module& out, std::string& err);
 

@@ -7,6 +7,15 @@
 //     the user's source                      (#line 1 "program": compiler messages carry the user's own line numbers)
 //     #include "demcz_kernels.h"             (its text and demcz_device.h's are embedded into this library at build time)
 //     explicit instantiations of window_kernel<TARGET_PROGRAM, DEMCZ_D, true / false> and logp_kernel<TARGET_PROGRAM>
+// The wave unit (UNIT_WAVE, handles created with DEMCZ_LAYOUT_PROGRAM_WAVE; composed and compiled only for them, cached under a
+// key of its own) has the same head, then
+//     #define ML_LRDPP 0 / PW_DDPP 0         (the generated DPP texts of the built-in targets are not part of the unit: the
+//                                             candidate adds read their increments from LDS -- the same doubles,
+//                                             tests/test_switch_variants.py -- and 54 generated files stay out of the library's
+//                                             text and out of every first-use compile)
+//     #include "demcz_kernels_pw.h"          (which brings _ps.h, _pc.h with the producer half, _ml.h, _rec.h, demcz_kernels.h)
+//     window_kernel_ps<TARGET_PROGRAM, DEMCZ_D, LIVE, TEMPER> (d <= 5) or window_kernel_pw<TARGET_PROGRAM, DEMCZ_D, LIVE, TEMPER>,
+//     LIVE and TEMPER both ways, and logp_kernel<TARGET_PROGRAM>
 // Compile options: --offload-arch=gfx950 -O3 -ffp-contract=off -I<rocm>/include, the library's own layout switches, then the
 // user's.  Code objects are cached per (composed text, options), loaded modules per (code object, device); both for the life of
 // the process.
@@ -18,7 +27,9 @@
 #include <dlfcn.h>
 #include <sys/stat.h>
 
+#include <cstdio>
 #include <cstdlib>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -38,6 +49,25 @@ const char k_device_h[] = {
 const char k_kernels_h[] = {
 #embed "demcz_kernels.h"
     , 0};
+// the wave unit's headers
+const char k_rec_h[] = {
+#embed "demcz_kernels_rec.h"
+    , 0};
+const char k_ml_h[] = {
+#embed "demcz_kernels_ml.h"
+    , 0};
+const char k_mlb_inc[] = {
+#embed "demcz_mlb_dpp_20_5.inc"
+    , 0};
+const char k_pc_h[] = {
+#embed "demcz_kernels_pc.h"
+    , 0};
+const char k_ps_h[] = {
+#embed "demcz_kernels_ps.h"
+    , 0};
+const char k_pw_h[] = {
+#embed "demcz_kernels_pw.h"
+    , 0};
 #pragma clang diagnostic pop
 
 // -D switches of the library build that change the layout of WindowParams: the program's kernels must see the same struct
@@ -53,9 +83,23 @@ std::mutex g_prog_mu;
 std::map<std::string, std::shared_ptr<const demcz_prog::Code>> g_code_cache;                        // composed text + options
 std::map<std::pair<const demcz_prog::Code*, int>, demcz_prog::Module> g_module_cache;               // (code object, device)
 
-std::string compose(int d, const std::string& source)
+std::string compose(int d, const std::string& source, int unit)
 {
     std::ostringstream s;
+    if (unit == demcz_prog::UNIT_WAVE) {
+        const char* kn = (d <= 5) ? "window_kernel_ps" : "window_kernel_pw";
+        s << "#define DEMCZ_D " << d << "\n#define DEMCZ_PROGRAM_TARGET\n#define DEMCZ_NO_AUX_KERNELS\n#define ML_LRDPP 0\n#define PW_DDPP 0\n"
+          << "#include <hip/hip_runtime.h>\n#include <stdint.h>\n"
+          << "#line 1 \"program\"\n" << source << "\n"
+          << "#line 1 \"demcz_program_wave_unit\"\n#include \"demcz_kernels_pw.h\"\n";
+        for (int live = 0; live < 2; ++live)
+            for (int temper = 0; temper < 2; ++temper)
+                s << "template __global__ void demcz::" << kn << "<demcz::TARGET_PROGRAM, DEMCZ_D, " << (live ? "true" : "false") << ", "
+                  << (temper ? "true" : "false") << ">(const demcz::WindowParams);\n";
+        s << "template __global__ void demcz::logp_kernel<demcz::TARGET_PROGRAM>(demcz::TargetParams, int, const double*, int64_t, "
+             "int64_t, double*);\n";
+        return s.str();
+    }
     s << "#define DEMCZ_D " << d << "\n#define DEMCZ_PROGRAM_TARGET\n#define DEMCZ_NO_AUX_KERNELS\n"
       << "#include <hip/hip_runtime.h>\n#include <stdint.h>\n"
       << "#line 1 \"program\"\n" << source << "\n"
@@ -121,16 +165,26 @@ std::string trim_log(std::string log)
         }                                                                                        \
     } while (0)
 
-bool compile(const std::string& text, const std::vector<std::string>& opts, int d, demcz_prog::Code& code, std::string& err)
+bool compile(const std::string& text, const std::vector<std::string>& opts, int d, int unit, demcz_prog::Code& code, std::string& err)
 {
     hiprtcProgram prog = nullptr;
-    const char* headers[] = {k_device_h, k_kernels_h};
-    const char* names[] = {"demcz_device.h", "demcz_kernels.h"};
-    RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_program_unit.hip", 2, headers, names));
+    const char* headers[] = {k_device_h, k_kernels_h, k_rec_h, k_ml_h, k_mlb_inc, k_pc_h, k_ps_h, k_pw_h};
+    const char* names[] = {"demcz_device.h", "demcz_kernels.h", "demcz_kernels_rec.h", "demcz_kernels_ml.h", "demcz_mlb_dpp_20_5.inc",
+                           "demcz_kernels_pc.h", "demcz_kernels_ps.h", "demcz_kernels_pw.h"};
+    const bool wave = unit == demcz_prog::UNIT_WAVE;
+    RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), wave ? "demcz_program_wave_unit.hip" : "demcz_program_unit.hip", wave ? 8 : 2, headers, names));
     struct Guard { hiprtcProgram& p; ~Guard() { if (p) (void)hiprtcDestroyProgram(&p); } } guard{prog};
     const std::string ds = std::to_string(d);
-    const std::string exprs[3] = {"&demcz::window_kernel<4, " + ds + ", true>", "&demcz::window_kernel<4, " + ds + ", false>",
-                                  "&demcz::logp_kernel<4>"};
+    std::vector<std::string> exprs;
+    if (wave) {
+        const std::string kn = (d <= 5) ? "&demcz::window_kernel_ps<4, " : "&demcz::window_kernel_pw<4, ";
+        for (int live = 0; live < 2; ++live)
+            for (int temper = 0; temper < 2; ++temper)
+                exprs.push_back(kn + ds + (live ? ", true" : ", false") + (temper ? ", true>" : ", false>"));
+    } else {
+        exprs = {"&demcz::window_kernel<4, " + ds + ", true>", "&demcz::window_kernel<4, " + ds + ", false>"};
+    }
+    exprs.push_back("&demcz::logp_kernel<4>");
     for (const auto& e : exprs) RTCCHK(hiprtcAddNameExpression(prog, e.c_str()));
     std::vector<const char*> argv;
     for (const auto& o : opts) argv.push_back(o.c_str());
@@ -154,13 +208,22 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
     RTCCHK(hiprtcGetCodeSize(prog, &n));
     code.object.resize(n);
     RTCCHK(hiprtcGetCode(prog, code.object.data()));
-    std::string* lowered[3] = {&code.window_full, &code.window_blocks, &code.logp};
-    for (int i = 0; i < 3; ++i) {
+    if (const char* dump = getenv("DEMCZ_PROGRAM_DUMP"); dump && *dump) {
+        // diagnosis (scripts/kernel_regs.py, llvm-objdump): the code object as a file in that directory
+        const std::string path = std::string(dump) + "/demcz_program_" + (wave ? "wave" : "lane") + "_d" + ds + "_" +
+                                 std::to_string(std::hash<std::string>{}(text) % 1000000007ull) + ".co";
+        if (FILE* f = fopen(path.c_str(), "wb")) { (void)fwrite(code.object.data(), 1, code.object.size(), f); fclose(f); }
+    }
+    std::vector<std::string*> lowered;
+    if (wave) lowered = {&code.wave[0][0], &code.wave[0][1], &code.wave[1][0], &code.wave[1][1], &code.logp};
+    else lowered = {&code.window_full, &code.window_blocks, &code.logp};
+    for (size_t i = 0; i < lowered.size(); ++i) {
         const char* nm = nullptr;
         RTCCHK(hiprtcGetLoweredName(prog, exprs[i].c_str(), &nm));
         *lowered[i] = nm;
     }
     code.d = d;
+    code.unit = unit;
     return true;
 }
 #undef RTCCHK
@@ -169,10 +232,19 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
 
 namespace demcz_prog {
 
-int32_t get_code(int d, const char* source, const char* options, std::shared_ptr<const Code>& out, std::string& err)
+int32_t get_code(int d, const char* source, const char* options, int unit, std::shared_ptr<const Code>& out, std::string& err)
 {
+    if (unit != UNIT_ONE_LANE && unit != UNIT_WAVE) {
+        err = "program target: lanes_per_chain must be 0, 1 or DEMCZ_LAYOUT_PROGRAM_WAVE";
+        return 1;
+    }
     if (d < 1 || d > MAX_PROGRAM_D) {
         err = "program target: d must be in 1.." + std::to_string(MAX_PROGRAM_D);
+        return 1;
+    }
+    if (unit == UNIT_WAVE && d < WAVE_MIN_D) {
+        err = "program target: the wave-per-chain layout (DEMCZ_LAYOUT_PROGRAM_WAVE) needs d in " + std::to_string(WAVE_MIN_D) + ".." +
+              std::to_string(MAX_PROGRAM_D);
         return 1;
     }
     if (!source) {
@@ -184,7 +256,7 @@ int32_t get_code(int d, const char* source, const char* options, std::shared_ptr
     std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-I" + inc};
     for (const char* const* s = k_layout_switches; *s; ++s) opts.push_back(*s);
     for (auto& o : split_options(options)) opts.push_back(o);
-    const std::string text = compose(d, source);
+    const std::string text = compose(d, source, unit);
     std::string key = text;
     for (const auto& o : opts) key += '\0' + o;
     {
@@ -193,7 +265,7 @@ int32_t get_code(int d, const char* source, const char* options, std::shared_ptr
         if (it != g_code_cache.end()) { out = it->second; return 0; }
     }
     auto code = std::make_shared<Code>();
-    if (!compile(text, opts, d, *code, err)) return 1;
+    if (!compile(text, opts, d, unit, *code, err)) return 1;
     std::lock_guard<std::mutex> lk(g_prog_mu);
     auto ins = g_code_cache.emplace(key, code);           // (another thread may have compiled the same program meanwhile)
     out = ins.first->second;
@@ -209,8 +281,14 @@ int32_t get_module(const std::shared_ptr<const Code>& code, int device, Module& 
     Module m;
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipModuleLoadData(&m.module, code->object.data());
-    if (e == hipSuccess) e = hipModuleGetFunction(&m.window_full, m.module, code->window_full.c_str());
-    if (e == hipSuccess) e = hipModuleGetFunction(&m.window_blocks, m.module, code->window_blocks.c_str());
+    if (code->unit == UNIT_WAVE) {
+        for (int live = 0; live < 2; ++live)
+            for (int temper = 0; temper < 2; ++temper)
+                if (e == hipSuccess) e = hipModuleGetFunction(&m.wave[live][temper], m.module, code->wave[live][temper].c_str());
+    } else {
+        if (e == hipSuccess) e = hipModuleGetFunction(&m.window_full, m.module, code->window_full.c_str());
+        if (e == hipSuccess) e = hipModuleGetFunction(&m.window_blocks, m.module, code->window_blocks.c_str());
+    }
     if (e == hipSuccess) e = hipModuleGetFunction(&m.logp, m.module, code->logp.c_str());
     if (e != hipSuccess) {
         if (m.module) (void)hipModuleUnload(m.module);

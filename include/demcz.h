@@ -98,12 +98,16 @@ typedef struct demcz_config {
                                      (smallest N; MvNormal at every d in 2..32, the isotropic quadratic
                                      at d in 6..32).  The regression target: d = 10 on the FP64 matrix
                                      instruction (split layouts), any other d in 2..28 on sixteen
-                                     lanes per chain with helper waves.  Results are bit-identical. */
+                                     lanes per chain with helper waves.  Results are bit-identical.
+                                     DEMCZ_LAYOUT_PROGRAM_WAVE: a program target on the wave-per-chain
+                                     layout (see "Program targets" below; only with
+                                     DEMCZ_TARGET_PROGRAM, which otherwise takes 0 or 1). */
     int32_t reserved0;
 } demcz_config;
 
 #define DEMCZ_LAYOUT_SPLIT 100
 #define DEMCZ_LAYOUT_SPLIT_WAVE 164
+#define DEMCZ_LAYOUT_PROGRAM_WAVE 264
 
 /* Program targets (DEMCZ_TARGET_PROGRAM): the closure of demcz.jl:189 as a small HIP C++ function the library compiles for
  * gfx950 at run time (hipRTC) together with its one-lane window kernel, so that it runs on the device like a built-in target
@@ -113,7 +117,7 @@ typedef struct demcz_config {
  * (device memory, read-only).  Compiled with --offload-arch=gfx950 -O3 -ffp-contract=off followed by `options` (space-separated,
  * e.g. "-DNOBS=1000"; may be NULL): with contraction off a fused multiply-add happens only where fma() is written, so what the
  * source says is what is computed, bit for bit.  Handles of a program target take lanes_per_chain 0 or 1 (both: one lane per
- * chain) and 1 <= d <= 32; the target fields of demcz_config are not read.
+ * chain) or DEMCZ_LAYOUT_PROGRAM_WAVE (below) and 1 <= d <= 32; the target fields of demcz_config are not read.
  *   demcz_program_check  compiles the program for dimension d and needs no device.  DEMCZ_OK, or DEMCZ_ERR_INVALID_ARGUMENT with
  *                        the compiler log (user's line numbers, file "program") in demcz_last_error(NULL).
  *   demcz_set_program    compiles the program (or takes it from the process-wide cache: a second handle with the same program and
@@ -123,6 +127,24 @@ typedef struct demcz_config {
  *                        error is DEMCZ_ERR_INVALID_ARGUMENT with the log in demcz_last_error(h); the handle stays usable for a
  *                        corrected demcz_set_program. */
 int32_t demcz_program_check(int32_t d, const char* source, const char* options);
+/* Program targets on the wave-per-chain layout (opt-in: lanes_per_chain = DEMCZ_LAYOUT_PROGRAM_WAVE at demcz_create).  The same
+ * source, contract and bits as above, compiled into the split layout's wave-per-chain consumer instead of the one-lane kernel: one
+ * wavefront per chain resolves up to five generations a pass, lane n of it evaluating demcz_logobj on candidate n of the 31 nodes
+ * of the pass's accept / reject tree; the draws come from the library's producer kernel, and on one GPU a launch runs through
+ * many K boundaries with the rows handed over inside it (one launch per K-window where N is more than such a launch holds).
+ * Measured at N = 1024 (where a launch of it holds every chain): 4.6 to 11.7 times less kernel time per K-window than the
+ * one-lane kernel, which stays the default and the only one for N > 2048.  Valid only with DEMCZ_TARGET_PROGRAM, one block 0..d-1 in order, 2 <= d <= 32, N <= 2048 and an archive
+ * reachable by 32-bit offsets (Mcap * 8 * (d rounded up to a multiple of 8) < 2^32); anything else is
+ * DEMCZ_ERR_INVALID_ARGUMENT at demcz_create with a message that names the condition.  demcz_comm_init and demcz_peer_group
+ * return DEMCZ_ERR_STATE on such a handle (host-driven sharding -- demcz_set_external_append, demcz_append_rows -- works).
+ * What the layout asks of demcz_logobj beyond the contract above: it is called for ALL 31 candidates of a pass, most of which the
+ * chain never takes (candidates several accepted steps away from the current state among them), so it must be a pure function of
+ * (x, data) -- no state kept between calls, no writes to data -- that terminates for every finite x.  A NaN result rejects, as
+ * on the one-lane layout.
+ *   demcz_program_check_layout  demcz_program_check for the unit a handle with this lanes_per_chain would compile (0, 1 or
+ *                        DEMCZ_LAYOUT_PROGRAM_WAVE; the latter needs 2 <= d <= 32): a compiler error of the wave unit -- registers,
+ *                        a construct that does not inline -- shows without a device.  Fills the same process-wide cache. */
+int32_t demcz_program_check_layout(int32_t d, const char* source, const char* options, int32_t lanes_per_chain);
 int32_t demcz_set_program(demcz_handle* h, const char* source, const char* options, const double* data, int64_t ndata);
 
 /* Version of this header's ABI; demcz_abi_version() must return the same number. */

@@ -58,6 +58,8 @@ end
 # lanes_per_chain beyond 0 (the library chooses) / 1 / 8 / 16: the producer-consumer split layouts (include/demcz.h)
 const LAYOUT_SPLIT = Int32(100)
 const LAYOUT_SPLIT_WAVE = Int32(164)
+# a ProgramTarget on the wave-per-chain layout (opt-in; the function is then called for all 31 candidates of a pass: include/demcz.h)
+const LAYOUT_PROGRAM_WAVE = Int32(264)
 
 struct DemczError <: Exception; code::Int32; msg::String; end
 lasterr(h) = unsafe_string(ccall((:demcz_last_error, libdemcz), Cstring, (Ptr{Cvoid},), h))
@@ -67,7 +69,7 @@ chk(rc, h=C_NULL) = rc == 0 ? nothing : throw(DemczError(rc, lasterr(h)))
 # (demcz.jl:189 calls it once per block-step per chain; such a closure runs on the host, see run_closure! below)
 const LogObj = Union{DeviceTarget,Function}
 
-function create(t::LogObj, N, d, K, Mcap, Gcap, blockindex, eps_scale, seed; device_id=0, chain_id0=0)
+function create(t::LogObj, N, d, K, Mcap, Gcap, blockindex, eps_scale, seed; device_id=0, chain_id0=0, lanes_per_chain=0)
     offs = Int32[0; cumsum(length.(blockindex))]
     idx = Int32[i - 1 for b in blockindex for i in b]                       # 1-based -> 0-based
     eps = Vector{Float64}(eps_scale)
@@ -80,7 +82,7 @@ function create(t::LogObj, N, d, K, Mcap, Gcap, blockindex, eps_scale, seed; dev
             t isa ProgramTarget ? (Int32(4), Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL), 0.0, Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL), 0) :
             (Int32(3), Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL), 0.0, Ptr{Float64}(C_NULL), Ptr{Float64}(C_NULL), 0)   # DEMCZ_TARGET_HOST_CALLBACK
         cfg = DemczConfig(N, chain_id0, d, K, Mcap, Gcap, length(blockindex), pointer(offs), pointer(idx), pointer(eps),
-                          UInt64(seed), device_id, kind, mu, W, c0, design, y, nobs, C_NULL, 0, 0)
+                          UInt64(seed), device_id, kind, mu, W, c0, design, y, nobs, C_NULL, Int32(lanes_per_chain), 0)
         chk(ccall((:demcz_create, libdemcz), Int32, (Ref{Ptr{Cvoid}}, Ref{DemczConfig}), h, cfg))   # config is copied
     end
     if t isa ProgramTarget         # compiled (or taken from the process-wide cache) and loaded before set_state
@@ -93,6 +95,10 @@ end
 # compile a program target without a device: throws DemczError with the compiler log
 check(t::ProgramTarget) = chk(ccall((:demcz_program_check, libdemcz), Int32, (Int32, Cstring, Cstring),
                                     Int32(t.d), t.source, join(t.options, " ")))
+# ... for the unit a handle with this lanes_per_chain compiles (0, 1 or LAYOUT_PROGRAM_WAVE)
+check(t::ProgramTarget, lanes_per_chain::Integer) =
+    chk(ccall((:demcz_program_check_layout, libdemcz), Int32, (Int32, Cstring, Cstring, Int32),
+              Int32(t.d), t.source, join(t.options, " "), Int32(lanes_per_chain)))
 destroy(h) = ccall((:demcz_destroy, libdemcz), Int32, (Ptr{Cvoid},), h)
 
 set_state(h, X::Matrix{Float64}, logp, Z::Matrix{Float64}) =

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Register / spill / LDS figures of every kernel in a build of the HIP library, from the code object's own metadata
-(no GPU needed):  python scripts/kernel_regs.py [lib.so] [name filter]
+(no GPU needed):  python scripts/kernel_regs.py [lib.so | object.co] [name filter]
+A `.co` argument is a plain gfx950 code object, e.g. a program target's as DEMCZ_PROGRAM_DUMP=<dir> writes it (demcz_program.hip).
 Columns: VGPRs, AGPRs, SGPRs, SGPR spills, VGPR spills, scratch bytes, static LDS bytes."""
 import re
 import subprocess
@@ -13,10 +14,15 @@ LLVM = Path("/opt/rocm/lib/llvm/bin")
 
 def kernel_table(lib):
     notes = ""
+    if str(lib).endswith(".co"):
+        notes = subprocess.run([str(LLVM / "llvm-readelf"), "--notes", str(lib)], check=True, capture_output=True, text=True).stdout
     with tempfile.TemporaryDirectory() as td:      # (one offload bundle per translation unit of the library: all of them)
         fat = Path(td) / "fat.bin"
-        subprocess.run([str(LLVM / "llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", str(lib), str(fat)], check=True)
-        blob = fat.read_bytes()
+        if str(lib).endswith(".co"):
+            blob = b""
+        else:
+            subprocess.run([str(LLVM / "llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", str(lib), str(fat)], check=True)
+            blob = fat.read_bytes()
         magic = b"__CLANG_OFFLOAD_BUNDLE__"
         starts = [i for i in range(len(blob)) if blob.startswith(magic, i)]
         for n, a in enumerate(starts):
@@ -24,7 +30,7 @@ def kernel_table(lib):
             part.write_bytes(blob[a:starts[n + 1] if n + 1 < len(starts) else len(blob)])
             r = subprocess.run([str(LLVM / "clang-offload-bundler"), "--type=o", "--unbundle", f"--input={part}", f"--output={co}",
                                 "--targets=hipv4-amdgcn-amd-amdhsa--gfx950"], stderr=subprocess.DEVNULL)
-            if r.returncode == 0 and co.exists() and co.stat().st_size > 0:
+            if not str(lib).endswith(".co") and r.returncode == 0 and co.exists() and co.stat().st_size > 0:
                 notes += subprocess.run([str(LLVM / "llvm-readelf"), "--notes", str(co)], check=True, capture_output=True, text=True).stdout
     rows = []
     for blk in re.split(r"\n\s*- \.agpr_count:", notes)[1:]:
@@ -43,8 +49,8 @@ def kernel_table(lib):
 
 
 if __name__ == "__main__":
-    lib = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1].endswith(".so") else str(Path(__file__).resolve().parent.parent / "demc.jl_amd" / "libdemcz_hip.so")
-    filt = sys.argv[-1] if len(sys.argv) > 1 and not sys.argv[-1].endswith(".so") else ""
+    lib = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1].endswith((".so", ".co")) else str(Path(__file__).resolve().parent.parent / "demc.jl_amd" / "libdemcz_hip.so")
+    filt = sys.argv[-1] if len(sys.argv) > 1 and not sys.argv[-1].endswith((".so", ".co")) else ""
     print(f"{'VGPR':>5} {'AGPR':>5} {'SGPR':>5} {'sspill':>6} {'vspill':>6} {'scratch':>7} {'LDS':>7}  kernel")
     for r in sorted(kernel_table(lib)):
         if filt in r[0]:
