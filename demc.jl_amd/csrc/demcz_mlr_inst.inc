@@ -1,5 +1,5 @@
 // demcz_mlr_inst.inc -- body of the translation units demcz_mlr_inst_<g>.hip (MLR_GROUP = g): window_kernel_ml<LINREG_SSE, d, 16> for
-// the dimensions d in 2..28 with d % 2 == g, with and without helper waves (COOP), behind mlr_launch_g<g> (demcz_mlr_dispatch.h).
+// the dimensions d in 2..28 with d % 2 == g, with and without helper waves (COOP), behind mlr_kernel_g<g> (demcz_mlr_dispatch.h).
 #define DEMCZ_NO_AUX_KERNELS 1
 #include "demcz_kernels_ml.h"
 #include "demcz_mlr_dispatch.h"
@@ -16,25 +16,23 @@
 
 namespace demcz {
 
-int32_t MLR_CAT(mlr_launch_g, MLR_GROUP)(int d, bool coop, unsigned blocks, int waves, hipStream_t s, const WindowParams& P)
+const void* MLR_CAT(mlr_kernel_g, MLR_GROUP)(int d, bool coop)
 {
     switch (d) {
 #if ML_LRDPP
 #define MLR_CASE(DD)                                                                                                                        \
     case DD:                                                                                                                                \
-        if (coop) hipLaunchKernelGGL((window_kernel_ml<TARGET_LINREG_SSE, DD, 16, false, false, true>), dim3(blocks), dim3(64 * ML_COOP_WAVES), 0, s, P); \
-        else hipLaunchKernelGGL((window_kernel_ml<TARGET_LINREG_SSE, DD, 16>), dim3(blocks), dim3(64 * (unsigned)waves), 0, s, P);           \
-        return 0;
-#else
+        return coop ? reinterpret_cast<const void*>(&window_kernel_ml<TARGET_LINREG_SSE, DD, 16, false, false, true>)                        \
+                    : reinterpret_cast<const void*>(&window_kernel_ml<TARGET_LINREG_SSE, DD, 16>);
+#else       // (no helper-wave instantiations: the caller never asks for them, ml_coop)
 #define MLR_CASE(DD)                                                                                                                        \
     case DD:                                                                                                                                \
-        hipLaunchKernelGGL((window_kernel_ml<TARGET_LINREG_SSE, DD, 16>), dim3(blocks), dim3(64 * (unsigned)waves), 0, s, P);                \
-        return 0;
+        return coop ? nullptr : reinterpret_cast<const void*>(&window_kernel_ml<TARGET_LINREG_SSE, DD, 16>);
 #endif
         MLR_DIMS(MLR_CASE)
 #undef MLR_CASE
     }
-    return 1;
+    return nullptr;
 }
 
 }  // namespace demcz

@@ -1,6 +1,6 @@
 // demcz_pw_inst.inc -- body of the translation units demcz_pw_inst_<g>.hip (PW_GROUP = g): window_kernel_pw for the dimensions
 // d in 6..32 with d % 8 == g, MvNormal and the isotropic quadratic, in its six forms (LIVE x tempered, general and regular
-// launches; d = 20, MvNormal: the matrix form too), behind pw_launch_g<g> / pw_query_g<g> (demcz_pw_dispatch.h).
+// launches; d = 20, MvNormal: the matrix form too), behind pw_kernel_g<g> (demcz_pw_dispatch.h).
 #define DEMCZ_NO_AUX_KERNELS 1
 #include "demcz_kernels_pw.h"
 #include "demcz_pw_dispatch.h"
@@ -30,88 +30,40 @@
 namespace demcz {
 namespace {
 
+// the kernel of (LIVE, tempered, form), nullptr where that form is not built: the matrix form exists at d = 20, MvNormal, and it and
+// the regular form only as LIVE kernels
 template <int TARGET, int D>
-int32_t launch_td(bool live, bool temper, int form, unsigned blocks, hipStream_t s, const WindowParams& P)
+const void* kernel_td(bool live, bool temper, int form)
 {
-    const dim3 grid(blocks), wg(64 * PS_CHAINS), wgl(64 * (PS_CHAINS + 1));
+#define PW_FN(...) reinterpret_cast<const void*>(&window_kernel_pw<TARGET, D, __VA_ARGS__>)
     if (form == PW_FORM_MATRIX) {
         if constexpr (D == 20 && TARGET == TARGET_MVNORMAL) {
-            if (!live) return 1;
-            if (temper) hipLaunchKernelGGL((window_kernel_pw<TARGET, D, true, true, true>), grid, wgl, 0, s, P);
-            else hipLaunchKernelGGL((window_kernel_pw<TARGET, D, true, false, true>), grid, wgl, 0, s, P);
-            return 0;
+            if (!live) return nullptr;
+            return temper ? PW_FN(true, true, true) : PW_FN(true, false, true);
         } else {
-            return 1;
+            return nullptr;
         }
     }
     if (form == PW_FORM_REGULAR) {
-        if (!live) return 1;
-        if (temper) hipLaunchKernelGGL((window_kernel_pw<TARGET, D, true, true, false, true>), grid, wgl, 0, s, P);
-        else hipLaunchKernelGGL((window_kernel_pw<TARGET, D, true, false, false, true>), grid, wgl, 0, s, P);
-        return 0;
+        if (!live) return nullptr;
+        return temper ? PW_FN(true, true, false, true) : PW_FN(true, false, false, true);
     }
-    if (temper) {
-        if (live) hipLaunchKernelGGL((window_kernel_pw<TARGET, D, true, true>), grid, wgl, 0, s, P);
-        else hipLaunchKernelGGL((window_kernel_pw<TARGET, D, false, true>), grid, wg, 0, s, P);
-    } else {
-        if (live) hipLaunchKernelGGL((window_kernel_pw<TARGET, D, true, false>), grid, wgl, 0, s, P);
-        else hipLaunchKernelGGL((window_kernel_pw<TARGET, D, false, false>), grid, wg, 0, s, P);
-    }
-    return 0;
-}
-
-// the consumer workgroups of a LIVE launch must all be resident: the fewest any LIVE form of this (target, d) fits on a CU
-template <int TARGET, int D>
-int query_td(int what)
-{
-    const void* fs[6] = {reinterpret_cast<const void*>(&window_kernel_pw<TARGET, D, true, false>),
-                         reinterpret_cast<const void*>(&window_kernel_pw<TARGET, D, true, true>),
-                         reinterpret_cast<const void*>(&window_kernel_pw<TARGET, D, true, false, false, true>),
-                         reinterpret_cast<const void*>(&window_kernel_pw<TARGET, D, true, true, false, true>), nullptr, nullptr};
-    int nf = 4;
-    if constexpr (D == 20 && TARGET == TARGET_MVNORMAL) {
-        fs[nf++] = reinterpret_cast<const void*>(&window_kernel_pw<TARGET, D, true, false, true>);
-        fs[nf++] = reinterpret_cast<const void*>(&window_kernel_pw<TARGET, D, true, true, true>);
-    }
-    if (what == PW_QUERY_BUILT) return 1;
-    int best = (what == PW_QUERY_LIVE_BLOCKS_PER_CU) ? 1 << 30 : 0;
-    for (int i = 0; i < nf; ++i) {
-        if (what == PW_QUERY_LIVE_BLOCKS_PER_CU) {
-            int n = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fs[i], 64 * (PS_CHAINS + 1), 0) != hipSuccess) n = 0;
-            best = (n < best) ? n : best;
-        } else {
-            hipFuncAttributes a{};
-            if (hipFuncGetAttributes(&a, fs[i]) == hipSuccess && (int)a.sharedSizeBytes > best) best = (int)a.sharedSizeBytes;
-        }
-    }
-    return best;
+    if (temper) return live ? PW_FN(true, true) : PW_FN(false, true);
+    return live ? PW_FN(true, false) : PW_FN(false, false);
+#undef PW_FN
 }
 
 }  // namespace
 
-int32_t PW_CAT(pw_launch_g, PW_GROUP)(int target, int d, bool live, bool temper, int form, unsigned blocks, hipStream_t s, const WindowParams& P)
+const void* PW_CAT(pw_kernel_g, PW_GROUP)(int target, int d, bool live, bool temper, int form)
 {
 #define PW_CASE(DD)                                                                                                     \
     case DD:                                                                                                            \
-        return (target == TARGET_MVNORMAL) ? launch_td<TARGET_MVNORMAL, DD>(live, temper, form, blocks, s, P)          \
-               : (target == TARGET_ISO_QUAD) ? launch_td<TARGET_ISO_QUAD, DD>(live, temper, form, blocks, s, P) : 1;
+        return (target == TARGET_MVNORMAL) ? kernel_td<TARGET_MVNORMAL, DD>(live, temper, form)                        \
+               : (target == TARGET_ISO_QUAD) ? kernel_td<TARGET_ISO_QUAD, DD>(live, temper, form) : nullptr;
     switch (d) {
         PW_DIMS(PW_CASE)
-    default: return 1;
-    }
-#undef PW_CASE
-}
-
-int PW_CAT(pw_query_g, PW_GROUP)(int target, int d, int what)
-{
-#define PW_CASE(DD)                                                                                                     \
-    case DD:                                                                                                            \
-        return (target == TARGET_MVNORMAL) ? query_td<TARGET_MVNORMAL, DD>(what)                                       \
-               : (target == TARGET_ISO_QUAD) ? query_td<TARGET_ISO_QUAD, DD>(what) : 0;
-    switch (d) {
-        PW_DIMS(PW_CASE)
-    default: return 0;
+    default: return nullptr;
     }
 #undef PW_CASE
 }
