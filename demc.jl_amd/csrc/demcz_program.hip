@@ -3,7 +3,7 @@
 // device.  Host code only: the kernels of a program live in its code object, not in this library.
 //
 // The composed translation unit (compose):
-//     #define DEMCZ_D <d> / DEMCZ_PROGRAM_TARGET / DEMCZ_NO_AUX_KERNELS
+//     #define DEMCZ_D <d> / DEMCZ_PROGRAM_TARGET / DEMCZ_NO_AUX_KERNELS, INFINITY and NAN as <math.h> has them
 //     the user's source                      (#line 1 "program": compiler messages carry the user's own line numbers)
 //     #include "demcz_kernels.h"             (its text and demcz_device.h's are embedded into this library at build time)
 //     explicit instantiations of window_kernel<TARGET_PROGRAM, DEMCZ_D, true / false> and logp_kernel<TARGET_PROGRAM>
@@ -83,13 +83,16 @@ std::mutex g_prog_mu;
 std::map<std::string, std::shared_ptr<const demcz_prog::Code>> g_code_cache;                        // composed text + options
 std::map<std::pair<const demcz_prog::Code*, int>, demcz_prog::Module> g_module_cache;               // (code object, device)
 
+// <math.h>'s INFINITY and NAN, which hipRTC's built-in headers leave undefined: a log-density with bounded support returns -INFINITY
+const char k_math_macros[] = "#ifndef INFINITY\n#define INFINITY (__builtin_inff())\n#endif\n#ifndef NAN\n#define NAN (__builtin_nanf(\"\"))\n#endif\n";
+
 std::string compose(int d, const std::string& source, int unit)
 {
     std::ostringstream s;
     if (unit == demcz_prog::UNIT_WAVE) {
         const char* kn = (d <= 5) ? "window_kernel_ps" : "window_kernel_pw";
         s << "#define DEMCZ_D " << d << "\n#define DEMCZ_PROGRAM_TARGET\n#define DEMCZ_NO_AUX_KERNELS\n#define ML_LRDPP 0\n#define PW_DDPP 0\n"
-          << "#include <hip/hip_runtime.h>\n#include <stdint.h>\n"
+          << "#include <hip/hip_runtime.h>\n#include <stdint.h>\n" << k_math_macros
           << "#line 1 \"program\"\n" << source << "\n"
           << "#line 1 \"demcz_program_wave_unit\"\n#include \"demcz_kernels_pw.h\"\n";
         for (int live = 0; live < 2; ++live)
@@ -101,7 +104,7 @@ std::string compose(int d, const std::string& source, int unit)
         return s.str();
     }
     s << "#define DEMCZ_D " << d << "\n#define DEMCZ_PROGRAM_TARGET\n#define DEMCZ_NO_AUX_KERNELS\n"
-      << "#include <hip/hip_runtime.h>\n#include <stdint.h>\n"
+      << "#include <hip/hip_runtime.h>\n#include <stdint.h>\n" << k_math_macros
       << "#line 1 \"program\"\n" << source << "\n"
       << "#line 1 \"demcz_program_unit\"\n#include \"demcz_kernels.h\"\n"
       << "template __global__ void demcz::window_kernel<demcz::TARGET_PROGRAM, DEMCZ_D, true>(const demcz::WindowParams);\n"

@@ -140,7 +140,8 @@ int32_t demcz_program_check(int32_t d, const char* source, const char* options);
  * What the layout asks of demcz_logobj beyond the contract above: it is called for ALL 31 candidates of a pass, most of which the
  * chain never takes (candidates several accepted steps away from the current state among them), so it must be a pure function of
  * (x, data) -- no state kept between calls, no writes to data -- that terminates for every finite x.  A NaN result rejects, as
- * on the one-lane layout.
+ * on the one-lane layout.  INFINITY and NAN are defined for the program as <math.h> defines them (return -INFINITY outside a
+ * bounded support).
  *   demcz_program_check_layout  demcz_program_check for the unit a handle with this lanes_per_chain would compile (0, 1 or
  *                        DEMCZ_LAYOUT_PROGRAM_WAVE; the latter needs 2 <= d <= 32): a compiler error of the wave unit -- registers,
  *                        a construct that does not inline -- shows without a device.  Fills the same process-wide cache. */
@@ -159,7 +160,12 @@ const char* demcz_last_error(const demcz_handle* h);   /* h may be NULL: last cr
 
 /* Upload the start state: demcz.jl:13-22.  X is N x d (ld N); logp is N values or NULL to have
  * the device evaluate the target at X (demcz.jl:17); Z is M0 x d with leading dimension ldZ;
- * 2 <= M0 <= Mcap (two distinct archive rows are needed, demcz.jl:176-179). */
+ * 2 <= M0 <= Mcap (two distinct archive rows are needed, demcz.jl:176-179).
+ * Non-finite values are accepted, in X, logp and Z alike (+-Inf, NaN, -0.0, subnormals), as the reference accepts them: +-Inf and
+ * NaN log-densities follow the accept rule (log u < lp' - lp, strict: a NaN difference rejects) and the changed rule
+ * ((lp_after - lp_before) != 0: a NaN difference counts) bit for bit in every layout; signs of zero and subnormals are kept; which
+ * NaN (sign, payload) comes out of an operation is unspecified.  One bit pattern is reserved and must not occur in X or Z:
+ * 0xFFF4DEADC0DE5EED, the sentinel the unwritten part of the archive holds. */
 int32_t demcz_set_state(demcz_handle* h, const double* X, const double* logp,
                         const double* Z, int64_t ldZ, int64_t M0);
 
