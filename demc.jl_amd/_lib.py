@@ -48,6 +48,7 @@ SYMBOLS = [
     "demcz_peer_detach", "demcz_get_peer_ping", "demcz_set_live_rearms", "demcz_get_live_rearms",
     "demcz_closure_buffers", "demcz_program_check", "demcz_set_program",
     "demcz_program_check_layout",
+    "demcz_autocov_sums", "demcz_autocov_sums_array", "demcz_ess_from_sums", "demcz_ess", "demcz_ess_array",
 ]
 
 
@@ -165,6 +166,11 @@ def load():
     L.demcz_set_rng_offset.argtypes = [C.c_void_p, C.c_int64]
     L.demcz_set_append_lag.argtypes = [C.c_void_p, C.c_int32]
     L.demcz_rhat_array.argtypes = [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int64, _dp]
+    L.demcz_autocov_sums.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _dp]
+    L.demcz_autocov_sums_array.argtypes = [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _dp]
+    L.demcz_ess_from_sums.argtypes = [C.c_int32, C.c_int64, C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, _dp, _lp, _ip]
+    L.demcz_ess.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, _dp, _dp, _dp, _lp, _ip]
+    L.demcz_ess_array.argtypes = [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int64, C.c_int64, _dp, _dp, _dp, _lp, _ip]
     L.demcz_accept_ratio_array.argtypes = [C.c_int32, _dp, C.c_int64, C.c_int64, _dp]
     L.demcz_mean_cov_array.argtypes = [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int64, _dp, _dp]
     L.demcz_set_external_append.argtypes = [C.c_void_p, C.c_int32]

@@ -4,6 +4,7 @@
 // DEMCZ_ERR_NO_DEVICE.
 #include "../../include/demcz.h"
 #include "demcz_kernels.h"
+#include "demcz_kernels_acf.h"
 #include "demcz_kernels_ml.h"
 #include "demcz_kernels_pc.h"
 #include "demcz_kernels_lr.h"
@@ -3065,26 +3066,34 @@ extern "C" int32_t demcz_get_changed_total(demcz_handle* h, int64_t g_from, int6
 }
 
 // ---- R-hat ---------------------------------------------------------------------------------------
-struct RhatPlan { int64_t N, w, s0, n, nd; int d, nchunk; double *S1, *S2, *mean_j, *s2_j, *sums; };
+struct RhatPlan { int64_t N, w, s0, n, nd, need; int d, nchunk; double *S1, *S2, *mean_j, *s2_j, *sums; };
 
-static int32_t rhat_prepare(demcz_handle* h, int64_t g_from, int64_t g_to, RhatPlan& r, bool compute, hipStream_t qs = nullptr)
+// The window's shape and what its plan needs of the scratch buffer (r.need doubles); allocates and launches nothing.
+static int32_t rhat_plan(demcz_handle* h, int64_t g_from, int64_t g_to, RhatPlan& r, const char* who = "demcz_rhat")
 {
-    int32_t rc = check_hist_range(h, g_from, g_to, "demcz_rhat");
+    int32_t rc = check_hist_range(h, g_from, g_to, who);
     if (rc) return rc;
     r.N = h->cfg.N; r.w = g_to - g_from + 1; r.s0 = g_from - h->g0 - 1; r.d = h->cfg.d;
     r.n = r.w / 2;                                            // utils.jl:4
-    if (r.n < 2) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_rhat: window needs at least 4 generations");
-    HIPCHK(h, hipSetDevice(h->cfg.device_id));
+    if (r.n < 2) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": window needs at least 4 generations");
     r.nchunk = (int)std::min<int64_t>(std::max<int64_t>(1, r.n / 32), 32);
     r.nd = r.N * r.d;
-    const int64_t need = 2 * (2 * r.nchunk * r.nd) + 2 * (2 * r.nd) + 4 * r.d;
-    rc = ensure_scratch(h, need);
+    r.need = 2 * (2 * r.nchunk * r.nd) + 2 * (2 * r.nd) + 4 * r.d;
+    return DEMCZ_OK;
+}
+
+// The scratch for a plan, with `extra` doubles behind it (at h->d_scratch + r.need) for a statistic that builds on the split
+// chains' means, and (compute) the moments and per-chain statistics.
+static int32_t rhat_scratch(demcz_handle* h, RhatPlan& r, int64_t extra, bool compute, hipStream_t qs = nullptr)
+{
+    HIPCHK(h, hipSetDevice(h->cfg.device_id));
+    int32_t rc = ensure_scratch(h, r.need + extra);
     if (rc) return rc;
     r.S1 = h->d_scratch;
     r.S2 = r.S1 + 2 * r.nchunk * r.nd;
     r.mean_j = r.S2 + 2 * r.nchunk * r.nd;
     r.s2_j = r.mean_j + 2 * r.nd;
-    r.sums = r.s2_j + 2 * r.nd;          // [0,d): stage 0 / grand mean; [d,3d): stage 1
+    r.sums = r.s2_j + 2 * r.nd;          // [0,d): stage 0 / grand mean; [d,3d): stage 1; [3d,4d): R-hat
     if (compute) {
         const int bs = 256;
         const unsigned gx = (unsigned)((r.nd + bs - 1) / bs);
@@ -3094,6 +3103,13 @@ static int32_t rhat_prepare(demcz_handle* h, int64_t g_from, int64_t g_to, RhatP
         HIPCHK(h, hipGetLastError());
     }
     return DEMCZ_OK;
+}
+
+static int32_t rhat_prepare(demcz_handle* h, int64_t g_from, int64_t g_to, RhatPlan& r, bool compute, hipStream_t qs = nullptr)
+{
+    int32_t rc = rhat_plan(h, g_from, g_to, r);
+    if (rc) return rc;
+    return rhat_scratch(h, r, 0, compute, qs);
 }
 
 extern "C" int32_t demcz_rhat_partial(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t stage, const double* grand, double* out)
@@ -3217,6 +3233,163 @@ extern "C" int32_t demcz_rhat(demcz_handle* h, int64_t g_from, int64_t g_to, dou
     rc = rhat_enqueue(h, g_from, g_to, rhat);
     if (rc) return rc;
     SYNCCHK(h, h->stream);
+    return DEMCZ_OK;
+}
+
+// ---- effective sample size (K8, demcz_kernels_acf.h) ------------------------------------------------
+// The split chains, their means and the between-chain sum are R-hat's (rhat_prepare, rhat_reduce_kernel); what is new is the
+// lagged self-product of every split chain, summed over the chains per (parameter, lag), and Geyer's initial monotone
+// sequence over those sums on the host (demcz_ess_from_sums).  Everything runs on the compute stream, on request only.
+struct AcfPlan { RhatPlan r; int nchunk, tiles; int64_t per; double *part, *out; };
+
+// Time chunks of one half and lag tiles per launch: a function of (N, d, n) alone, so that a lag's bits do not depend on the
+// batch that computes it.  Chunks are whole numbers of tiles long (a trip of the kernel's loop is ACF_TL left samples), at
+// least two, and only as many as it takes for 2 halves x 4 tiles x chunks x waves to give every SIMD a few waves.
+static void acf_chunks(int64_t N, int d, int64_t n, int& nchunk, int64_t& per)
+{
+    const int64_t waves = (N * d + ACF_BS - 1) / ACF_BS;
+    const int64_t want = (4096 + 8 * waves - 1) / (8 * waves);
+    const int64_t k = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n / (2 * ACF_TL), want), 64));
+    per = ((n + k - 1) / k + ACF_TL - 1) / ACF_TL * ACF_TL;
+    nchunk = (int)((n + per - 1) / per);
+}
+
+// live_verify, R-hat's plan for the window, the scratch for it with the chunk partials and one batch of sums behind it, the
+// wait for side-stream checks (they work in the same scratch, see rhat_enqueue); launches nothing.
+// A launch holds up to four lag tiles, fewer where four tiles of partials would pass 2^24 doubles (128 MB) -- but always one,
+// which at one chunk is 64 N d doubles: the size of 64 generations of the history itself.
+static int32_t acf_prepare(demcz_handle* h, int64_t g_from, int64_t g_to, AcfPlan& a, const char* who)
+{
+    int32_t rc = live_verify(h);
+    if (rc) return rc;
+    rc = rhat_plan(h, g_from, g_to, a.r, who);
+    if (rc) return rc;
+    RhatPlan& r = a.r;
+    acf_chunks(r.N, r.d, r.n, a.nchunk, a.per);
+    const int64_t tile = (int64_t)2 * a.nchunk * ACF_TL * r.nd;               // doubles of partials per lag tile
+    a.tiles = (int)std::max<int64_t>(1, std::min<int64_t>(4, ((int64_t)1 << 24) / tile));
+    rc = rhat_scratch(h, r, a.tiles * tile + (int64_t)a.tiles * ACF_TL * r.d, false);
+    if (rc) return rc;
+    if (h->rhat_side_pending) {
+        HIPCHK(h, hipStreamWaitEvent(h->stream, h->rhat_side_ev, 0));
+        h->rhat_side_pending = false;
+    }
+    a.part = h->d_scratch + r.need;
+    a.out = a.part + a.tiles * tile;
+    return DEMCZ_OK;
+}
+
+// Enqueues lags lag_from..lag_to (inside 0..n-1) in launches of a.tiles tiles and the copies of their sums to
+// sums[p + d (t - lag_from)]; does not wait.
+static int32_t acf_enqueue(demcz_handle* h, const AcfPlan& a, int64_t lag_from, int64_t lag_to, double* sums)
+{
+    const RhatPlan& r = a.r;
+    const unsigned gx = (unsigned)((r.nd + ACF_BS - 1) / ACF_BS);
+    for (int64_t t = lag_from; t <= lag_to; t += (int64_t)a.tiles * ACF_TL) {
+        const int64_t nl = std::min<int64_t>((int64_t)a.tiles * ACF_TL, lag_to - t + 1);
+        const unsigned nz = (unsigned)((nl + ACF_TL - 1) / ACF_TL);
+        hipLaunchKernelGGL(acf_products_kernel, dim3(gx, 2 * a.nchunk, nz), dim3(ACF_BS), 0, h->stream, (const double*)h->dchain,
+                           (const double*)r.mean_j, r.N, r.d, r.s0, r.n, a.nchunk, a.per, t, a.part);
+        hipLaunchKernelGGL(acf_reduce_kernel, dim3(r.d, (unsigned)nl), dim3(256), 0, h->stream, (const double*)a.part, r.N, r.d, a.nchunk,
+                           a.out, (int64_t)0);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(sums + (size_t)r.d * (t - lag_from), a.out, (size_t)r.d * nl * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    }
+    return DEMCZ_OK;
+}
+
+extern "C" int32_t demcz_autocov_sums(demcz_handle* h, int64_t g_from, int64_t g_to, int64_t lag_from, int64_t lag_to, double* sums)
+{
+    if (!h || !sums) return DEMCZ_ERR_INVALID_ARGUMENT;
+    AcfPlan a;
+    int32_t rc = acf_prepare(h, g_from, g_to, a, "demcz_autocov_sums");
+    if (rc) return rc;
+    if (lag_from < 0 || lag_to < lag_from || lag_to > a.r.n - 1)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_autocov_sums: 0 <= lag_from <= lag_to <= n - 1, n = half the window");
+    rc = rhat_scratch(h, a.r, 0, true);                      // (the scratch is there: this is the split chains' means)
+    if (rc) return rc;
+    rc = acf_enqueue(h, a, lag_from, lag_to, sums);
+    if (rc) return rc;
+    SYNCCHK(h, h->stream);
+    return DEMCZ_OK;
+}
+
+extern "C" int32_t demcz_ess_from_sums(int32_t d, int64_t m, int64_t n, int64_t nlags, const double* sums, const double* between,
+                                       double* ess, double* tau, double* varplus, int64_t* pairs, int32_t* converged)
+{
+    if (d <= 0 || m < 1 || n < 2 || nlags < 1 || !sums || !between || !ess) return DEMCZ_ERR_INVALID_ARGUMENT;
+    const double dn = (double)n, dm = (double)m, S = dm * dn;
+    const double cap = S * std::log10(S), floor_tau = 1.0 / std::log10(S);
+    const int64_t L = nlags - 1;
+    for (int p = 0; p < d; ++p) {
+        const double A0 = sums[p] / S;
+        const double W = A0 * dn / (dn - 1.0);
+        const double vp = A0 + between[p] / (dm - 1.0);
+        double sum = 0.0, prev = 0.0;
+        int64_t k = 0;
+        int32_t conv = 0;
+        for (; 2 * k + 1 <= L; ++k) {
+            const double r0 = k ? 1.0 - (W - sums[p + (size_t)d * (2 * k)] / S) / vp : 1.0;
+            const double r1 = 1.0 - (W - sums[p + (size_t)d * (2 * k + 1)] / S) / vp;
+            double P = r0 + r1;
+            if (!(P > 0.0)) {                       // the stopping pair is not summed; a NaN pair stops too, and shows in tau
+                conv = 1;
+                if (P != P) sum = P;
+                break;
+            }
+            if (k && prev < P) P = prev;            // initial monotone sequence
+            sum += P;
+            prev = P;
+        }
+        const double t = -1.0 + 2.0 * sum;
+        ess[p] = (t < floor_tau) ? cap : S / t;
+        if (tau) tau[p] = t;
+        if (varplus) varplus[p] = vp;
+        if (pairs) pairs[p] = k;
+        if (converged) converged[p] = conv;
+    }
+    return DEMCZ_OK;
+}
+
+extern "C" int32_t demcz_ess(demcz_handle* h, int64_t g_from, int64_t g_to, int64_t max_lag,
+                             double* ess, double* tau, double* varplus, int64_t* pairs, int32_t* converged)
+{
+    if (!h || !ess) return DEMCZ_ERR_INVALID_ARGUMENT;
+    if (h->comm && h->nranks > 1)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_ess: on a sharded handle add demcz_autocov_sums and demcz_rhat_partial over the ranks "
+                                                   "on the host and finish with demcz_ess_from_sums");
+    AcfPlan a;
+    int32_t rc = acf_prepare(h, g_from, g_to, a, "demcz_ess");
+    if (rc) return rc;
+    rc = rhat_scratch(h, a.r, 0, true);                      // (the scratch is there: this is the split chains' means)
+    if (rc) return rc;
+    const RhatPlan& r = a.r;
+    const int d = r.d;
+    const int64_t n = r.n, m = 2 * r.N;
+    const int64_t L = (max_lag <= 0) ? n - 1 : std::min<int64_t>(n - 1, max_lag);
+    // between[p] = sum_j (mean_j - grand)^2, the grand mean formed on the device as the sharded R-hat forms it
+    hipLaunchKernelGGL(rhat_reduce_kernel, dim3(d), dim3(256), 0, h->stream, r.mean_j, r.s2_j, r.N, d, 0, (const double*)nullptr, 1.0, r.sums);
+    hipLaunchKernelGGL(rhat_reduce_kernel, dim3(d), dim3(256), 0, h->stream, r.mean_j, r.s2_j, r.N, d, 1, (const double*)r.sums, (double)m, r.sums + d);
+    HIPCHK(h, hipGetLastError());
+    std::vector<double> between((size_t)d), sums;
+    std::vector<int32_t> conv((size_t)d);
+    HIPCHK(h, hipMemcpyAsync(between.data(), r.sums + d, (size_t)d * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    // lags in batches of one launch, the finisher after each: it never looks past its stopping pair, so the first batch after
+    // which every parameter has stopped gives what all L lags would
+    const int64_t batch = (int64_t)a.tiles * ACF_TL;
+    int64_t have = 0;
+    for (;;) {
+        const int64_t to = std::min<int64_t>(L, have + batch - 1);
+        sums.resize((size_t)d * (to + 1));
+        rc = acf_enqueue(h, a, have, to, sums.data() + (size_t)d * have);
+        if (rc) { (void)hipStreamSynchronize(h->stream); return rc; }       // (copies into this call's vectors may be under way)
+        SYNCCHK(h, h->stream);
+        have = to + 1;
+        rc = demcz_ess_from_sums(d, m, n, have, sums.data(), between.data(), ess, tau, varplus, pairs, conv.data());
+        if (rc) return fail(h, rc, "demcz_ess: finisher");
+        if (have > L || std::all_of(conv.begin(), conv.end(), [](int32_t c) { return c == 1; })) break;
+    }
+    if (converged) std::copy(conv.begin(), conv.end(), converged);
     return DEMCZ_OK;
 }
 
@@ -4018,6 +4191,26 @@ extern "C" int32_t demcz_rhat_array(int32_t device_id, const double* chain, int6
     int32_t rc = s.open(device_id, N, d, G, chain, nullptr);
     if (rc) return diag_fail(s, rc);
     return diag_fail(s, demcz_rhat(&s.h, 1, G, rhat));
+}
+
+extern "C" int32_t demcz_autocov_sums_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G,
+                                            int64_t lag_from, int64_t lag_to, double* sums)
+{
+    if (!chain || !sums) return DEMCZ_ERR_INVALID_ARGUMENT;
+    ScratchHandle s;
+    int32_t rc = s.open(device_id, N, d, G, chain, nullptr);
+    if (rc) return diag_fail(s, rc);
+    return diag_fail(s, demcz_autocov_sums(&s.h, 1, G, lag_from, lag_to, sums));
+}
+
+extern "C" int32_t demcz_ess_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, int64_t max_lag,
+                                   double* ess, double* tau, double* varplus, int64_t* pairs, int32_t* converged)
+{
+    if (!chain || !ess) return DEMCZ_ERR_INVALID_ARGUMENT;
+    ScratchHandle s;
+    int32_t rc = s.open(device_id, N, d, G, chain, nullptr);
+    if (rc) return diag_fail(s, rc);
+    return diag_fail(s, demcz_ess(&s.h, 1, G, max_lag, ess, tau, varplus, pairs, converged));
 }
 
 extern "C" int32_t demcz_accept_ratio_array(int32_t device_id, const double* log_obj, int64_t N, int64_t G, double* ratio)

@@ -8,12 +8,33 @@ without a GPU.)
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 
 from . import _lib
 from ._lib import DemczError
 from .targets import is_device_target
+
+# per parameter: effective sample size, autocorrelation time (uncapped), var+ (R-hat's varhat), pairs summed by Geyer's
+# initial monotone sequence, and whether a non-positive pair ended it (0: the lags ran out, ess is an upper bound)
+ESS = namedtuple("ESS", "ess tau varplus pairs converged")
+
+
+def ess_from_sums(m, n, sums, between):
+    """demcz_ess_from_sums (host code, no device): `sums` is d x nlags from lag 0, sum over all m split chains of n c_j(t);
+    `between` is sum_j (mean_j - grand)^2 per parameter."""
+    sums = _lib.f64(sums, "F")
+    d, nlags = sums.shape
+    between = _lib.f64(between)
+    if between.shape != (d,):
+        raise ValueError("between must have d entries")
+    out = ESS(np.empty(d), np.empty(d), np.empty(d), np.zeros(d, dtype=np.int64), np.zeros(d, dtype=np.int32))
+    rc = _lib.load().demcz_ess_from_sums(d, int(m), int(n), nlags, _lib.ptr(sums), _lib.ptr(between), _lib.ptr(out.ess), _lib.ptr(out.tau),
+                                         _lib.ptr(out.varplus), _lib.ptr(out.pairs, _lib._lp), _lib.ptr(out.converged, _lib._ip))
+    if rc != 0:
+        raise DemczError(rc, "demcz_ess_from_sums: d >= 1, n >= 2, nlags >= 1")
+    return out
 
 
 def blocks_to_csr(blockindex, d):
@@ -296,6 +317,20 @@ class HipEngine:
         out = np.empty(self.d if stage == 0 else 2 * self.d)
         g = _lib.f64(grand) if grand is not None else None
         self._chk(self._L.demcz_rhat_partial(self._h, int(g_from), int(g_to), int(stage), _lib.ptr(g), _lib.ptr(out)))
+        return out
+
+    def autocov_sums(self, g_from, g_to, lag_from, lag_to):
+        """d x (lag_to - lag_from + 1): the sum over this engine's 2N split chains of n c_j(t) (demcz_autocov_sums)."""
+        out = np.empty((self.d, max(0, int(lag_to) - int(lag_from) + 1)), order="F")
+        self._chk(self._L.demcz_autocov_sums(self._h, int(g_from), int(g_to), int(lag_from), int(lag_to), _lib.ptr(out)))
+        return out
+
+    def ess(self, g_from, g_to, max_lag=0):
+        """Effective sample size per parameter over generations g_from..g_to (demcz_ess): an ESS tuple."""
+        d = self.d
+        out = ESS(np.empty(d), np.empty(d), np.empty(d), np.zeros(d, dtype=np.int64), np.zeros(d, dtype=np.int32))
+        self._chk(self._L.demcz_ess(self._h, int(g_from), int(g_to), int(max_lag), _lib.ptr(out.ess), _lib.ptr(out.tau),
+                                    _lib.ptr(out.varplus), _lib.ptr(out.pairs, _lib._lp), _lib.ptr(out.converged, _lib._ip)))
         return out
 
     def accept_ratio(self, g_from, g_to):

@@ -252,6 +252,30 @@ class _Runner:
         varhat = (n - 1) / n * W + B / n
         return np.sqrt(varhat / W)
 
+    def ess(self, g_from, g_to, max_lag=0):
+        """Effective sample size per parameter over all N_total chains (an engine.ESS tuple).  One engine: demcz_ess.  Several
+        shards: their lag sums and R-hat partials are additive; the host adds them and finishes with demcz_ess_from_sums."""
+        if self.lib_exchange:
+            raise NotImplementedError("ess over a communicator of several ranks: add autocov_sums and rhat_partial over the ranks "
+                                      "on the host and finish with engine.ess_from_sums")
+        if not self.host_exchange and len(self.engines) == 1:
+            return self.engines[0].ess(g_from, g_to, max_lag)
+        from .engine import ess_from_sums
+        n = (g_to - g_from + 1) // 2
+        m = 2 * self.N_total
+        L = n - 1 if max_lag <= 0 else min(n - 1, int(max_lag))
+        s0 = self._allsum(sum(e.rhat_partial(g_from, g_to, 0, None) for e in self.engines))
+        s1 = self._allsum(sum(e.rhat_partial(g_from, g_to, 1, s0 / m) for e in self.engines))
+        # lags in batches, the finisher after each, as demcz_ess does: it never looks past its stopping pair
+        sums, have = np.empty((self.d, 0), order="F"), 0
+        while True:
+            to = min(L, have + 127)
+            part = self._allsum(sum(e.autocov_sums(g_from, g_to, have, to) for e in self.engines))
+            sums, have = np.asfortranarray(np.concatenate([sums, part], axis=1)), to + 1
+            out = ess_from_sums(m, n, sums, s1[:self.d])
+            if have > L or out.converged.all():
+                return out
+
     def changed(self, g_from, g_to):
         c = sum(e.get_changed(g_from, g_to) for e in self.engines)
         if self.sh is not None and self.sh.world_size > 1:

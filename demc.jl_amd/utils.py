@@ -4,6 +4,7 @@
 examples pass them (test/example_normpdf.jl:35-47); the arrays are uploaded and reduced by the same
 kernels the autostop uses.  ``flatten_chain`` is a pure re-indexing (utils.jl:22-32).  Plotting,
 ``save_res`` and ``extract_best`` are not reproduced (dead code in Julia >= 1.0).
+Beyond the reference: ``ess_chain``, ``autocov_chain`` and ``posterior_summary`` (effective sample size).
 Checkpoints: the reference only resumes in memory (``prevrun=``); ``save_checkpoint`` /
 ``load_checkpoint`` put the same information in one ``.npz`` file.
 """
@@ -60,6 +61,46 @@ def mean_cov_chain(chain, Npop=None, Ngeneration=None, Npar=None, device_id=0):
     cov = np.empty((d, d), order="F")
     _chk(_lib.load().demcz_mean_cov_array(device_id, _lib.ptr(chain), N, d, G, _lib.ptr(mean), _lib.ptr(cov)))
     return mean, cov
+
+
+def ess_chain(chain, max_lag=0, device_id=0):
+    """Effective sample size per parameter of an Npop x Npar x Ngeneration history (BDA3 section 11.5 / Stan, on the split chains
+    of Rhat_gelman, without rank normalisation): an ESS tuple (ess, tau, varplus, pairs, converged).  Not in the reference."""
+    from .engine import ESS
+    chain = _lib.f64(chain, "F")
+    N, d, G = chain.shape
+    out = ESS(np.empty(d), np.empty(d), np.empty(d), np.zeros(d, dtype=np.int64), np.zeros(d, dtype=np.int32))
+    _chk(_lib.load().demcz_ess_array(device_id, _lib.ptr(chain), N, d, G, int(max_lag), _lib.ptr(out.ess), _lib.ptr(out.tau),
+                                     _lib.ptr(out.varplus), _lib.ptr(out.pairs, _lib._lp), _lib.ptr(out.converged, _lib._ip)))
+    return out
+
+
+def autocov_sums_chain(chain, lag_from, lag_to, device_id=0):
+    """d x (lag_to - lag_from + 1): sum over the 2 Npop split chains of n c_j(t) (demcz_autocov_sums_array)."""
+    chain = _lib.f64(chain, "F")
+    N, d, G = chain.shape
+    out = np.empty((d, max(0, int(lag_to) - int(lag_from) + 1)), order="F")
+    _chk(_lib.load().demcz_autocov_sums_array(device_id, _lib.ptr(chain), N, d, G, int(lag_from), int(lag_to), _lib.ptr(out)))
+    return out
+
+
+def autocov_chain(chain, max_lag, device_id=0):
+    """A(t) = mean over the split chains of their biased autocovariance c_j(t), t = 0 .. L: Npar x (L + 1), with L = n - 1 for
+    max_lag <= 0 and min(n - 1, max_lag) otherwise, n = Ngeneration // 2."""
+    N, _, G = np.shape(chain)
+    n = G // 2
+    L = n - 1 if max_lag <= 0 else min(n - 1, int(max_lag))
+    return autocov_sums_chain(chain, 0, L, device_id) / (2.0 * N * n)
+
+
+def posterior_summary(chain, device_id=0):
+    """Per parameter: mean, sd = sqrt(var+), mcse = sqrt(var+ / ess), ess, rhat, converged (of the ESS: 0 where the lags ran out
+    and ess is an upper bound) -- mean_cov_chain, Rhat_gelman and ess_chain, all reduced on the device."""
+    mean, _ = mean_cov_chain(chain, device_id=device_id)
+    e = ess_chain(chain, device_id=device_id)
+    with np.errstate(all="ignore"):
+        return dict(mean=mean, sd=np.sqrt(e.varplus), mcse=np.sqrt(e.varplus / e.ess), ess=e.ess,
+                    rhat=Rhat_gelman(chain, device_id=device_id), converged=e.converged)
 
 
 def convergence_check(chain, log_obj, figure_path=None, verbose=True, parnames=None, device_id=0):

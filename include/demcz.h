@@ -245,6 +245,31 @@ int32_t demcz_rhat(demcz_handle* h, int64_t g_from, int64_t g_to, double* rhat);
 int32_t demcz_rhat_partial(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t stage,
                            const double* grand, double* out);
 
+/* Effective sample size per parameter over generations g_from..g_to of the on-device history (BDA3 section 11.5 / the Stan
+ * reference manual, without rank normalisation).  The split chains are demcz_rhat's: n = (g_to-g_from+1)/2
+ * samples each, m = 2 N of them; the window needs at least 4 generations.  With c_j(t) = 1/n sum_i (x_i - mean_j)(x_{i+t} - mean_j)
+ * and A(t) = 1/m sum_j c_j(t): W = A(0) n/(n-1), var+ = A(0) + sum_j (mean_j - grand)^2 / (m-1), rho_t = 1 - (W - A(t))/var+
+ * (rho_0 = 1), Geyer's initial monotone sequence over the pairs P_k = rho_2k + rho_2k+1 up to lag L (n-1, or min(n-1, max_lag)
+ * when max_lag > 0), tau = -1 + 2 sum P_k, ESS = m n / tau, and m n log10(m n) where tau < 1 / log10(m n).
+ *
+ * demcz_autocov_sums   sums[p + d*(t - lag_from)] = sum over the LOCAL 2N split chains of n*c_j(t), t = lag_from..lag_to
+ *                      (0 <= lag_from <= lag_to <= n-1).  A lag's value does not depend on the other lags of the call.
+ * demcz_ess_from_sums  pure host code, no device: the finisher.  sums: d x nlags from lag 0 (an unpaired last lag is ignored);
+ *                      between[p] = sum_j (mean_j - grand)^2 over all m split chains (demcz_rhat_partial stage 1, out[0..d)).
+ *                      pairs[p] = pairs summed; converged[p] = 1 when a pair with !(P_k > 0) ended the sequence (that pair is not
+ *                      summed; a NaN pair ends it too and makes tau and ess NaN), 0 when the lags ran out: ess is then an upper
+ *                      bound.  tau is returned uncapped.  Any output pointer but ess may be NULL.
+ * demcz_ess            the whole statistic.  Lags are computed in batches and the finisher runs after each, until every
+ *                      parameter has converged or L is reached: the cost follows the autocorrelation time, and the result is, bit
+ *                      for bit, what all L lags give.  Any output pointer but ess may be NULL.  On a handle whose communicator
+ *                      has more than one rank: DEMCZ_ERR_INVALID_ARGUMENT -- the sums are additive over shards; add
+ *                      demcz_autocov_sums and demcz_rhat_partial over the ranks on the host and call demcz_ess_from_sums. */
+int32_t demcz_autocov_sums(demcz_handle* h, int64_t g_from, int64_t g_to, int64_t lag_from, int64_t lag_to, double* sums);
+int32_t demcz_ess_from_sums(int32_t d, int64_t m, int64_t n, int64_t nlags, const double* sums, const double* between,
+                            double* ess, double* tau, double* varplus, int64_t* pairs, int32_t* converged);
+int32_t demcz_ess(demcz_handle* h, int64_t g_from, int64_t g_to, int64_t max_lag,
+                  double* ess, double* tau, double* varplus, int64_t* pairs, int32_t* converged);
+
 /* Per-chain acceptance ratio over generations g_from..g_to:
  * sum(diff(log_obj, dims=2) .!= 0, dims=2) ./ (G-1), src/utils.jl:61.  ratio: N values. */
 int32_t demcz_accept_ratio(demcz_handle* h, int64_t g_from, int64_t g_to, double* ratio);
@@ -354,10 +379,15 @@ int32_t demcz_set_rng_offset(demcz_handle* h, int64_t generations);
  * on the device, and nothing is kept.
  *   demcz_rhat_array          Rhat_gelman(chain, N, G, d)              src/utils.jl:2-20
  *   demcz_accept_ratio_array  sum(diff(log_obj,dims=2).!=0,dims=2)./(G-1)   src/utils.jl:61
- *   demcz_mean_cov_array      mean_cov_chain(chain, N, G, d)           src/utils.jl:96-111 */
+ *   demcz_mean_cov_array      mean_cov_chain(chain, N, G, d)           src/utils.jl:96-111
+ *   demcz_autocov_sums_array / demcz_ess_array   the two calls above over the whole array (not in the reference) */
 int32_t demcz_rhat_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, double* rhat);
 int32_t demcz_accept_ratio_array(int32_t device_id, const double* log_obj, int64_t N, int64_t G, double* ratio);
 int32_t demcz_mean_cov_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, double* mean, double* cov);
+int32_t demcz_autocov_sums_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G,
+                                 int64_t lag_from, int64_t lag_to, double* sums);
+int32_t demcz_ess_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, int64_t max_lag,
+                        double* ess, double* tau, double* varplus, int64_t* pairs, int32_t* converged);
 
 /* Introspection for benchmarks and tests. */
 int32_t demcz_get_info(const demcz_handle* h, int64_t* M, int64_t* launches_window, int32_t* lanes_per_chain);

@@ -361,6 +361,21 @@ function mean_cov(h, g_from, g_to, d)
     b = zeros(d); cov = zeros(d, d)
     chk(ccall((:demcz_mean_cov, libdemcz), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Ptr{Float64}), h, g_from, g_to, b, cov), h); b, cov
 end
+# effective sample size per parameter (BDA3 11.5 / Stan, on Rhat_gelman's split chains, no rank normalisation; not in the reference):
+# (ess, tau, varplus, pairs, converged) -- converged[p] == 0: the lags ran out before a non-positive pair, ess[p] is an upper bound
+function ess(h, g_from, g_to, d; max_lag=0)
+    e = zeros(d); tau = zeros(d); vp = zeros(d); pairs = zeros(Int64, d); conv = zeros(Int32, d)
+    chk(ccall((:demcz_ess, libdemcz), Int32, (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int32}),
+              h, g_from, g_to, max_lag, e, tau, vp, pairs, conv), h)
+    (ess=e, tau=tau, varplus=vp, pairs=pairs, converged=conv)
+end
+function ess_chain(chain::Array{Float64,3}; max_lag=0, device_id=0)
+    Npop, Npar, Ngeneration = size(chain)
+    e = zeros(Npar); tau = zeros(Npar); vp = zeros(Npar); pairs = zeros(Int64, Npar); conv = zeros(Int32, Npar)
+    chk(ccall((:demcz_ess_array, libdemcz), Int32, (Int32, Ptr{Float64}, Int64, Int32, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int32}),
+              device_id, chain, Npop, Npar, Ngeneration, max_lag, e, tau, vp, pairs, conv))
+    (ess=e, tau=tau, varplus=vp, pairs=pairs, converged=conv)
+end
 
 # ---- checkpoint: what a resumed run needs (the reference resumes in memory only, demcz.jl:18-22) ----------------------------
 struct Checkpoint
