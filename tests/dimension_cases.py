@@ -101,17 +101,20 @@ def passes_of(g_from, g_to, k=K):
     return out
 
 
-def pass_outcomes(pieces, log_obj, lp0, k=K):
-    """{form: counts[32]} over the full five-generation passes of every form's pieces.  A pass's outcome: the five bits
-    log_obj[g] != log_obj[g - 1], the first generation's the highest (generation 0 is the starting log-density lp0)."""
+def pass_outcomes(pieces, log_obj, lp0, k=K, forms=FORMS, length=PASS, chains=None):
+    """{form: counts[2 ** length]} over the passes of `length` generations (the full ones: five) of every form's pieces, of all
+    chains or of the subset `chains`.  A pass's outcome: the bits log_obj[g] != log_obj[g - 1], the first generation's the highest
+    (generation 0 is the starting log-density lp0)."""
     lo = np.concatenate([np.asarray(lp0, dtype=np.float64)[:, None], np.asarray(log_obj)], axis=1)      # column g = generation g
+    if chains is not None:
+        lo = lo[chains]
     moved = lo[:, 1:] != lo[:, :-1]                                                                     # column g - 1 = generation g
-    counts = {f: np.zeros(32, dtype=np.int64) for f in FORMS}
+    counts = {f: np.zeros(1 << length, dtype=np.int64) for f in forms}
     for g_from, g_to, _, form in pieces:
         for a, b in passes_of(g_from, g_to, k):
-            if b - a + 1 == PASS:
-                code = (moved[:, a - 1:b] * (1 << np.arange(PASS - 1, -1, -1))).sum(axis=1)
-                counts[form] += np.bincount(code, minlength=32)
+            if b - a + 1 == length:
+                code = (moved[:, a - 1:b] * (1 << np.arange(length - 1, -1, -1))).sum(axis=1)
+                counts[form] += np.bincount(code, minlength=1 << length)
     return counts
 
 

@@ -19,12 +19,13 @@ from helpers import SPLIT_WAVE
 pytestmark = pytest.mark.gpu
 
 
-def engine_run(demc, case, lanes):
+def engine_run(demc, case, lanes, history=True):
     """The library over the case's pieces on one handle.  dimension_cases.oracle_run's dict (changed: the total), `names`: the
-    kernel's name and the count of window launches after every piece, `layout` and `live_status`."""
+    kernel's name and the count of window launches after every piece, `layout` and `live_status`.  history = False: a handle that
+    keeps none (Gcap = 0), chain and log_obj are None."""
     w, N, d, G = case["problem"], case["N"], case["d"], case["G"]
     M0 = w["Zinit"].shape[0]
-    e = demc.HipEngine(N=N, d=d, K=case["K"], Mcap=M0 + N * (G // case["K"] + 1), Gcap=G, blockindex=[range(d)],
+    e = demc.HipEngine(N=N, d=d, K=case["K"], Mcap=M0 + N * (G // case["K"] + 1), Gcap=G if history else 0, blockindex=[range(d)],
                        eps_scale=w["eps_scale"], seed=case["seed"], target=w["target"], lanes_per_chain=lanes)
     try:
         layout = e.info()["lanes_per_chain"]
@@ -35,7 +36,7 @@ def engine_run(demc, case, lanes):
             e.run(a, b, case["gamma"], case["temperature"][a - 1:b] if tempered else None)
             names.append(e.kernel_name())
             launches.append(e.info()["window_launches"])
-        chain, lobj = e.get_history(1, G)
+        chain, lobj = e.get_history(1, G) if history else (None, None)
         X, lp, Z, M = e.get_state()
         return dict(chain=chain, log_obj=lobj, X=X, logp=lp, Z=np.array(Z[:M]), M=M, changed=e.changed_total(1, G), names=names,
                     launches=launches, layout=layout, live_status=tuple(e.live_status()))
@@ -43,8 +44,8 @@ def engine_run(demc, case, lanes):
         e.close()
 
 
-def _same_as_oracle(got, ref, what):
-    for k in ("chain", "log_obj", "X", "logp", "Z"):
+def _same_as_oracle(got, ref, what, keys=("chain", "log_obj", "X", "logp", "Z")):
+    for k in keys:
         assert got[k].shape == ref[k].shape, f"{what}: {k}: shapes {got[k].shape}, oracle {ref[k].shape}"
         ne = got[k] != ref[k]
         assert np.array_equal(got[k], ref[k]), (f"{what}: {k} differs from the oracle in {int(ne.sum())} places, first at "
