@@ -29,6 +29,7 @@ OK, ERR_INVALID_ARGUMENT, ERR_HIP, ERR_CAPACITY, ERR_STATE, ERR_NO_DEVICE, ERR_C
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
 _lp = C.POINTER(C.c_int64)
+_up = C.POINTER(C.c_uint64)
 
 # every symbol include/demcz.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -49,6 +50,8 @@ SYMBOLS = [
     "demcz_closure_buffers", "demcz_program_check", "demcz_set_program",
     "demcz_program_check_layout",
     "demcz_autocov_sums", "demcz_autocov_sums_array", "demcz_ess_from_sums", "demcz_ess", "demcz_ess_array",
+    "demcz_quantile_plan", "demcz_select_counts", "demcz_select_step", "demcz_quantile_finish", "demcz_quantiles",
+    "demcz_quantiles_array", "demcz_best", "demcz_best_array",
 ]
 
 
@@ -171,6 +174,14 @@ def load():
     L.demcz_ess_from_sums.argtypes = [C.c_int32, C.c_int64, C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, _dp, _lp, _ip]
     L.demcz_ess.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, _dp, _dp, _dp, _lp, _ip]
     L.demcz_ess_array.argtypes = [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int64, C.c_int64, _dp, _dp, _dp, _lp, _ip]
+    L.demcz_quantile_plan.argtypes = [C.c_int64, C.c_int32, _dp, _lp, _lp, _dp]
+    L.demcz_select_counts.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _up, _lp, _lp]
+    L.demcz_select_step.argtypes = [C.c_int32, C.c_int32, _lp, _up, _lp]
+    L.demcz_quantile_finish.argtypes = [C.c_int32, C.c_int32, _up, _up, _dp, _lp, _dp, _dp, _dp]
+    L.demcz_quantiles.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp, _dp]
+    L.demcz_quantiles_array.argtypes = [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int64, C.c_int32, _dp, _dp, _dp, _dp]
+    L.demcz_best.argtypes = [C.c_void_p, C.c_int64, C.c_int64, _dp, _lp, _lp, _dp]
+    L.demcz_best_array.argtypes = [C.c_int32, _dp, C.c_int64, C.c_int64, _dp, _lp, _lp]
     L.demcz_accept_ratio_array.argtypes = [C.c_int32, _dp, C.c_int64, C.c_int64, _dp]
     L.demcz_mean_cov_array.argtypes = [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int64, _dp, _dp]
     L.demcz_set_external_append.argtypes = [C.c_void_p, C.c_int32]

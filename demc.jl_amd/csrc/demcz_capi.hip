@@ -5,6 +5,8 @@
 #include "../../include/demcz.h"
 #include "demcz_kernels.h"
 #include "demcz_kernels_acf.h"
+#include "demcz_kernels_sel.h"
+#include "demcz_select_host.h"
 #include "demcz_kernels_ml.h"
 #include "demcz_kernels_pc.h"
 #include "demcz_kernels_lr.h"
@@ -3069,6 +3071,9 @@ extern "C" int32_t demcz_get_changed_total(demcz_handle* h, int64_t g_from, int6
 struct RhatPlan { int64_t N, w, s0, n, nd, need; int d, nchunk; double *S1, *S2, *mean_j, *s2_j, *sums; };
 
 // The window's shape and what its plan needs of the scratch buffer (r.need doubles); allocates and launches nothing.
+static int rhat_chunks(int64_t n) { return (int)std::min<int64_t>(std::max<int64_t>(1, n / 32), 32); }
+static int64_t rhat_need(int64_t nd, int d, int nchunk) { return 2 * (2 * nchunk * nd) + 2 * (2 * nd) + 4 * d; }
+
 static int32_t rhat_plan(demcz_handle* h, int64_t g_from, int64_t g_to, RhatPlan& r, const char* who = "demcz_rhat")
 {
     int32_t rc = check_hist_range(h, g_from, g_to, who);
@@ -3076,9 +3081,9 @@ static int32_t rhat_plan(demcz_handle* h, int64_t g_from, int64_t g_to, RhatPlan
     r.N = h->cfg.N; r.w = g_to - g_from + 1; r.s0 = g_from - h->g0 - 1; r.d = h->cfg.d;
     r.n = r.w / 2;                                            // utils.jl:4
     if (r.n < 2) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": window needs at least 4 generations");
-    r.nchunk = (int)std::min<int64_t>(std::max<int64_t>(1, r.n / 32), 32);
+    r.nchunk = rhat_chunks(r.n);
     r.nd = r.N * r.d;
-    r.need = 2 * (2 * r.nchunk * r.nd) + 2 * (2 * r.nd) + 4 * r.d;
+    r.need = rhat_need(r.nd, r.d, r.nchunk);
     return DEMCZ_OK;
 }
 
@@ -3390,6 +3395,201 @@ extern "C" int32_t demcz_ess(demcz_handle* h, int64_t g_from, int64_t g_to, int6
         if (have > L || std::all_of(conv.begin(), conv.end(), [](int32_t c) { return c == 1; })) break;
     }
     if (converged) std::copy(conv.begin(), conv.end(), converged);
+    return DEMCZ_OK;
+}
+
+// ---- selection (K9, demcz_kernels_sel.h): quantiles by radix select, the best draw ----------------------------------------------
+// A counting pass reads the window once and returns integer histograms of one key byte; the host walks the ranks one byte down
+// (demcz_select_host.h) and asks for the next byte.  Everything runs on the compute stream, on request only, in scratch that lies
+// behind R-hat's plan for the same window, as the autocovariance partials do.
+struct SelPlan { int64_t N, w, s0, nd, off, cb, per; int d, nchunk; };
+
+// live_verify, the window, the chunk plan and `extra` doubles of scratch at h->d_scratch + s.off; the wait for side-stream checks.
+// Chunks: enough workgroups to fill the chip whatever the shape of the window (as demcz_accept_ratio), at least 16 generations
+// each, and never so long that a workgroup's 32-bit bins could wrap (64 chains x 2^20 generations).
+static int32_t sel_prepare(demcz_handle* h, int64_t g_from, int64_t g_to, SelPlan& s, int64_t extra, const char* who)
+{
+    DEADCHK(h);
+    int32_t rc = live_verify(h);
+    if (rc) return rc;
+    rc = check_hist_range(h, g_from, g_to, who);
+    if (rc) return rc;
+    s.N = h->cfg.N; s.d = h->cfg.d; s.w = g_to - g_from + 1; s.s0 = g_from - h->g0 - 1; s.nd = s.N * s.d;
+    s.off = rhat_need(s.nd, s.d, rhat_chunks(s.w / 2));
+    s.cb = (s.N + 63) / 64;
+    if (s.cb * s.d > 0x7fffffffll) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": N d too large for one launch");
+    const int64_t fill = (4096 + s.cb * s.d - 1) / (s.cb * s.d);
+    int64_t nchunk = std::max<int64_t>(1, std::min<int64_t>((s.w + 15) / 16, fill));
+    nchunk = std::max<int64_t>(nchunk, (s.w + ((int64_t)1 << 20) - 1) >> 20);
+    s.per = (s.w + nchunk - 1) / nchunk;
+    s.nchunk = (int)((s.w + s.per - 1) / s.per);
+    HIPCHK(h, hipSetDevice(h->cfg.device_id));
+    rc = ensure_scratch(h, s.off + extra);
+    if (rc) return rc;
+    if (h->rhat_side_pending) {
+        HIPCHK(h, hipStreamWaitEvent(h->stream, h->rhat_side_ev, 0));
+        h->rhat_side_pending = false;
+    }
+    return DEMCZ_OK;
+}
+
+static int sel_width(int nprefix) { int np = 1; while (np < nprefix) np *= 2; return np; }
+// doubles of scratch one pass needs: the padded prefixes, the counts and the NaN counts (all 8-byte words)
+static int64_t sel_words(int d, int np) { return (int64_t)d * np + (int64_t)d * np * 256 + d; }
+
+template <int NP>
+static void sel_launch(demcz_handle* h, const SelPlan& s, int shift, const uint64_t* dpre, unsigned long long* dcnt, unsigned long long* dnan)
+{
+    hipLaunchKernelGGL(select_counts_kernel<NP>, dim3((unsigned)(s.cb * s.d), (unsigned)s.nchunk), dim3(SEL_BS), 0, h->stream,
+                       (const double*)h->dchain, s.N, s.d, s.s0, s.w, s.cb, s.per, shift, dpre, dcnt, dnan);
+}
+
+// One pass: uploads the prefixes (hpre: [d][np], padded with ~0; it must live until the stream is synchronised), counts, and
+// copies [d][np][256] counts and d NaN counts to hcnt / hnan.  Does not wait.
+static int32_t sel_enqueue(demcz_handle* h, const SelPlan& s, int shift, int np, const uint64_t* hpre, uint64_t* hcnt, uint64_t* hnan)
+{
+    static_assert(sizeof(unsigned long long) == sizeof(double) && sizeof(uint64_t) == sizeof(double), "scratch reuse");
+    uint64_t* dpre = reinterpret_cast<uint64_t*>(h->d_scratch + s.off);
+    unsigned long long* dcnt = reinterpret_cast<unsigned long long*>(dpre + (size_t)s.d * np);
+    unsigned long long* dnan = dcnt + (size_t)s.d * np * 256;
+    HIPCHK(h, hipMemcpyAsync(dpre, hpre, (size_t)s.d * np * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(dcnt, 0, ((size_t)s.d * np * 256 + s.d) * sizeof(unsigned long long), h->stream));
+    switch (np) {
+    case 1: sel_launch<1>(h, s, shift, dpre, dcnt, dnan); break;
+    case 2: sel_launch<2>(h, s, shift, dpre, dcnt, dnan); break;
+    case 4: sel_launch<4>(h, s, shift, dpre, dcnt, dnan); break;
+    case 8: sel_launch<8>(h, s, shift, dpre, dcnt, dnan); break;
+    case 16: sel_launch<16>(h, s, shift, dpre, dcnt, dnan); break;
+    case 32: sel_launch<32>(h, s, shift, dpre, dcnt, dnan); break;
+    default: return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "select_counts: prefix count");
+    }
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(hcnt, dcnt, (size_t)s.d * np * 256 * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(hnan, dnan, (size_t)s.d * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    return DEMCZ_OK;
+}
+
+extern "C" int32_t demcz_select_counts(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t shift, int32_t nprefix,
+                                       const uint64_t* prefix, int64_t* counts, int64_t* nan_count)
+{
+    if (!h || !prefix || !counts) return DEMCZ_ERR_INVALID_ARGUMENT;
+    if (nprefix < 1 || nprefix > SEL_MAX_PREFIX || shift < 0 || shift > 56 || shift % 8 != 0)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_select_counts: 1 <= nprefix <= 32, shift a multiple of 8 in 0..56");
+    const int np = (shift == 56) ? 1 : sel_width(nprefix);       // at shift 56 every draw matches every prefix: counted once
+    SelPlan s;
+    int32_t rc = sel_prepare(h, g_from, g_to, s, sel_words(h->cfg.d, np), "demcz_select_counts");
+    if (rc) return rc;
+    const int d = s.d;
+    std::vector<uint64_t> hpre((size_t)d * np, ~(uint64_t)0), hcnt((size_t)d * np * 256), hnan((size_t)d);
+    for (int p = 0; p < d; ++p)
+        for (int u = 0; u < (shift == 56 ? 1 : nprefix); ++u) hpre[(size_t)p * np + u] = (shift == 56) ? 0 : prefix[p + (size_t)d * u];
+    rc = sel_enqueue(h, s, shift, np, hpre.data(), hcnt.data(), hnan.data());
+    if (rc) { (void)hipStreamSynchronize(h->stream); return rc; }          // (copies into this call's vectors may be under way)
+    SYNCCHK(h, h->stream);
+    for (int p = 0; p < d; ++p)
+        for (int u = 0; u < nprefix; ++u)
+            for (int b = 0; b < 256; ++b)
+                counts[b + 256 * ((size_t)u + (size_t)nprefix * p)] = (int64_t)hcnt[b + 256 * ((size_t)(shift == 56 ? 0 : u) + (size_t)np * p)];
+    if (nan_count) for (int p = 0; p < d; ++p) nan_count[p] = (int64_t)hnan[p];
+    return DEMCZ_OK;
+}
+
+extern "C" int32_t demcz_quantiles(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t nq, const double* probs,
+                                   double* q, double* lower, double* upper)
+{
+    if (!h || !probs || !q) return DEMCZ_ERR_INVALID_ARGUMENT;
+    if (h->comm && h->nranks > 1)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_quantiles: on a sharded handle add demcz_select_counts over the ranks on the host "
+                                                   "and step with demcz_select_step");
+    if (nq < 1 || nq > SEL_MAX_PROBS) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_quantiles: 1 <= nq <= 16");
+    const int nr = 2 * nq;
+    SelPlan s;
+    int32_t rc = sel_prepare(h, g_from, g_to, s, sel_words(h->cfg.d, sel_width(nr)), "demcz_quantiles");
+    if (rc) return rc;
+    const int d = s.d;
+    std::vector<int64_t> rlo((size_t)nq), rhi((size_t)nq);
+    std::vector<double> frac((size_t)nq);
+    rc = demcz_quantile_plan(s.N * s.w, nq, probs, rlo.data(), rhi.data(), frac.data());
+    if (rc) return fail(h, rc, "demcz_quantiles: every probability must lie in [0, 1]");
+    // rank r = 2 j (lower) and 2 j + 1 (upper) of probability j; prefix / rank: [p + d r]
+    std::vector<uint64_t> prefix((size_t)d * nr, 0), hpre, hcnt, hnan((size_t)d);
+    std::vector<int64_t> rank((size_t)d * nr), cnt((size_t)256 * nr * d), nan((size_t)d);
+    std::vector<int> slot((size_t)d * nr);
+    for (int p = 0; p < d; ++p)
+        for (int j = 0; j < nq; ++j) { rank[p + (size_t)d * (2 * j)] = rlo[j]; rank[p + (size_t)d * (2 * j + 1)] = rhi[j]; }
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        // the distinct prefixes of each parameter, in order of first appearance; slot[p + d r] = where rank r's prefix went
+        int most = 1;
+        for (int p = 0; p < d; ++p) {
+            int n = 0;
+            for (int r = 0; r < nr; ++r) {
+                int u = 0;
+                while (u < r && prefix[p + (size_t)d * u] != prefix[p + (size_t)d * r]) ++u;
+                slot[p + (size_t)d * r] = (u < r) ? slot[p + (size_t)d * u] : n++;
+            }
+            most = std::max(most, n);
+        }
+        const int np = (shift == 56) ? 1 : sel_width(most);
+        hpre.assign((size_t)d * np, ~(uint64_t)0);
+        for (int p = 0; p < d; ++p)
+            for (int r = 0; r < nr; ++r) hpre[(size_t)p * np + slot[p + (size_t)d * r]] = prefix[p + (size_t)d * r];
+        hcnt.resize((size_t)d * np * 256);
+        rc = sel_enqueue(h, s, shift, np, hpre.data(), hcnt.data(), hnan.data());
+        if (rc) { (void)hipStreamSynchronize(h->stream); return rc; }
+        SYNCCHK(h, h->stream);
+        for (int p = 0; p < d; ++p)
+            for (int r = 0; r < nr; ++r)
+                for (int b = 0; b < 256; ++b)
+                    cnt[b + 256 * ((size_t)r + (size_t)nr * p)] = (int64_t)hcnt[b + 256 * ((size_t)slot[p + (size_t)d * r] + (size_t)np * p)];
+        rc = demcz_select_step(d, nr, cnt.data(), prefix.data(), rank.data());
+        if (rc) return fail(h, rc, "demcz_quantiles: a rank fell outside the counts");
+    }
+    for (int p = 0; p < d; ++p) nan[p] = (int64_t)hnan[p];
+    std::vector<uint64_t> klo((size_t)d * nq), khi((size_t)d * nq);
+    for (int p = 0; p < d; ++p)
+        for (int j = 0; j < nq; ++j) { klo[p + (size_t)d * j] = prefix[p + (size_t)d * (2 * j)]; khi[p + (size_t)d * j] = prefix[p + (size_t)d * (2 * j + 1)]; }
+    return demcz_quantile_finish(d, nq, klo.data(), khi.data(), frac.data(), nan.data(), q, lower, upper);
+}
+
+// ---- the best draw: arg-max of log_obj over the window -----------------------------------------------------------------------
+extern "C" int32_t demcz_best(demcz_handle* h, int64_t g_from, int64_t g_to, double* bestval, int64_t* chain, int64_t* generation,
+                              double* bestpar)
+{
+    if (!h || !bestval || !chain || !generation) return DEMCZ_ERR_INVALID_ARGUMENT;
+    int32_t rc = check_hist_range(h, g_from, g_to, "demcz_best");
+    if (rc) return rc;
+    const int64_t total = h->cfg.N * (g_to - g_from + 1);
+    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((total + 2047) / 2048, 1024));
+    SelPlan s;                       // (of the plan only the window and the scratch offset are used here)
+    rc = sel_prepare(h, g_from, g_to, s, 2 * (int64_t)nb + 2, "demcz_best");
+    if (rc) return rc;
+    if (bestpar && !h->dchain) return fail(h, DEMCZ_ERR_STATE, "demcz_best: no chain history to take bestpar from");
+    static_assert(sizeof(long long) == sizeof(double), "scratch reuse");
+    double* pv = h->d_scratch + s.off;
+    long long* pi = reinterpret_cast<long long*>(pv + nb);
+    double* ov = pv + 2 * (size_t)nb;
+    long long* oi = reinterpret_cast<long long*>(ov + 1);
+    hipLaunchKernelGGL(best_partial_kernel, dim3((unsigned)nb), dim3(256), 0, h->stream, (const double*)(h->dlogobj + (size_t)s.N * s.s0), total, pv, pi);
+    hipLaunchKernelGGL(best_final_kernel, dim3(1), dim3(256), 0, h->stream, (const double*)pv, (const long long*)pi, nb, ov, oi);
+    HIPCHK(h, hipGetLastError());
+    double v = 0.0;
+    long long i = -1;
+    HIPCHK(h, hipMemcpyAsync(&v, ov, sizeof v, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&i, oi, sizeof i, hipMemcpyDeviceToHost, h->stream));
+    SYNCCHK(h, h->stream);
+    *bestval = v;
+    if (i < 0) {
+        *chain = -1; *generation = -1;
+        if (bestpar) for (int p = 0; p < s.d; ++p) bestpar[p] = std::nan("");
+        return DEMCZ_OK;
+    }
+    *chain = i % s.N;
+    *generation = g_from + i / s.N;
+    if (bestpar) {
+        HIPCHK(h, hipMemcpy2DAsync(bestpar, sizeof(double), h->dchain + (size_t)(i % s.N) + (size_t)s.nd * (s.s0 + i / s.N),
+                                   (size_t)s.N * sizeof(double), sizeof(double), (size_t)s.d, hipMemcpyDeviceToHost, h->stream));
+        SYNCCHK(h, h->stream);
+    }
     return DEMCZ_OK;
 }
 
@@ -4211,6 +4411,29 @@ extern "C" int32_t demcz_ess_array(int32_t device_id, const double* chain, int64
     int32_t rc = s.open(device_id, N, d, G, chain, nullptr);
     if (rc) return diag_fail(s, rc);
     return diag_fail(s, demcz_ess(&s.h, 1, G, max_lag, ess, tau, varplus, pairs, converged));
+}
+
+extern "C" int32_t demcz_quantiles_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, int32_t nq,
+                                         const double* probs, double* q, double* lower, double* upper)
+{
+    if (!chain || !probs || !q) return DEMCZ_ERR_INVALID_ARGUMENT;
+    ScratchHandle s;
+    int32_t rc = s.open(device_id, N, d, G, chain, nullptr);
+    if (rc) return diag_fail(s, rc);
+    return diag_fail(s, demcz_quantiles(&s.h, 1, G, nq, probs, q, lower, upper));
+}
+
+extern "C" int32_t demcz_best_array(int32_t device_id, const double* log_obj, int64_t N, int64_t G, double* bestval, int64_t* chain,
+                                    int64_t* column)
+{
+    if (!log_obj || !bestval || !chain || !column) return DEMCZ_ERR_INVALID_ARGUMENT;
+    ScratchHandle s;
+    int32_t rc = s.open(device_id, N, 1, G, nullptr, log_obj);
+    if (rc) return diag_fail(s, rc);
+    int64_t g = -1;
+    rc = demcz_best(&s.h, 1, G, bestval, chain, &g, nullptr);
+    if (!rc) *column = (g < 0) ? -1 : g - 1;
+    return diag_fail(s, rc);
 }
 
 extern "C" int32_t demcz_accept_ratio_array(int32_t device_id, const double* log_obj, int64_t N, int64_t G, double* ratio)

@@ -37,6 +37,76 @@ def ess_from_sums(m, n, sums, between):
     return out
 
 
+# quantiles per parameter (d x nq) and, on request, the two order statistics they were formed from (lower = x_(lo), upper = x_(hi))
+Quantiles = namedtuple("Quantiles", "q lower upper")
+# the best draw of a window: max of log_obj, 0-based chain, generation, chain[chain, :, generation]
+Best = namedtuple("Best", "bestval chain generation bestpar")
+
+
+def quantile_plan(S, probs):
+    """demcz_quantile_plan (host code, no device): (rank_lo, rank_hi, frac) of Hyndman-Fan type 7 for S draws."""
+    probs = np.ascontiguousarray(np.atleast_1d(probs), dtype=np.float64)
+    nq = probs.size
+    lo, hi, frac = np.zeros(nq, dtype=np.int64), np.zeros(nq, dtype=np.int64), np.zeros(nq)
+    rc = _lib.load().demcz_quantile_plan(int(S), nq, _lib.ptr(probs), _lib.ptr(lo, _lib._lp), _lib.ptr(hi, _lib._lp), _lib.ptr(frac))
+    if rc != 0:
+        raise DemczError(rc, "demcz_quantile_plan: S >= 1, 1 to 16 probabilities, each in [0, 1]")
+    return lo, hi, frac
+
+
+def select_step(counts, prefix, rank):
+    """demcz_select_step (host code, no device): counts (d, nr, 256) int64 already added over shards, prefix (d, nr) uint64 and
+    rank (d, nr) int64; returns the new (prefix, rank)."""
+    prefix = np.array(prefix, dtype=np.uint64, order="F", ndmin=2)
+    rank = np.array(rank, dtype=np.int64, order="F", ndmin=2)
+    d, nr = prefix.shape
+    counts = np.ascontiguousarray(counts, dtype=np.int64)
+    if counts.shape != (d, nr, 256) or rank.shape != (d, nr):
+        raise ValueError("counts must be (d, nr, 256), prefix and rank (d, nr)")
+    rc = _lib.load().demcz_select_step(d, nr, _lib.ptr(counts, _lib._lp), _lib.ptr(prefix, _lib._up), _lib.ptr(rank, _lib._lp))
+    if rc != 0:
+        raise DemczError(rc, "demcz_select_step: a rank is not below the total of its counts")
+    return prefix, rank
+
+
+def quantile_finish(key_lo, key_hi, frac, nan_count=None):
+    """demcz_quantile_finish (host code, no device): keys (d, nq) uint64 -> Quantiles."""
+    key_lo = np.array(key_lo, dtype=np.uint64, order="F", ndmin=2)
+    key_hi = np.array(key_hi, dtype=np.uint64, order="F", ndmin=2)
+    d, nq = key_lo.shape
+    frac = np.ascontiguousarray(frac, dtype=np.float64)
+    nan_count = None if nan_count is None else np.ascontiguousarray(nan_count, dtype=np.int64)
+    if key_hi.shape != (d, nq) or frac.shape != (nq,) or (nan_count is not None and nan_count.shape != (d,)):
+        raise ValueError("key_lo and key_hi must be (d, nq), frac (nq,), nan_count (d,)")
+    out = Quantiles(np.empty((d, nq), order="F"), np.empty((d, nq), order="F"), np.empty((d, nq), order="F"))
+    rc = _lib.load().demcz_quantile_finish(d, nq, _lib.ptr(key_lo, _lib._up), _lib.ptr(key_hi, _lib._up), _lib.ptr(frac),
+                                           _lib.ptr(nan_count, _lib._lp), _lib.ptr(out.q), _lib.ptr(out.lower), _lib.ptr(out.upper))
+    if rc != 0:
+        raise DemczError(rc, "demcz_quantile_finish: 1 to 16 probabilities")
+    return out
+
+
+def select_quantiles(count_pass, S, d, probs):
+    """The radix select driven from the host, for counts that have to be added over shards first: `count_pass(shift, prefix)`
+    returns ((d, nprefix, 256) int64 counts, (d,) NaN counts) over ALL shards for a (d, nprefix) uint64 prefix array.  Eight
+    passes; the ranks of one parameter that share a prefix share one column of the pass (demcz_quantiles does the same)."""
+    lo, hi, frac = quantile_plan(S, probs)
+    nq = lo.size
+    rank = np.asfortranarray(np.broadcast_to(np.stack([lo, hi], axis=1).reshape(1, 2 * nq), (d, 2 * nq)))
+    prefix = np.zeros((d, 2 * nq), dtype=np.uint64, order="F")
+    nan = np.zeros(d, dtype=np.int64)
+    for shift in range(56, -8, -8):
+        uniq = [list(dict.fromkeys(prefix[p].tolist())) for p in range(d)]
+        npre = max(len(u) for u in uniq)
+        pre = np.full((d, npre), ~np.uint64(0), dtype=np.uint64, order="F")
+        for p, u in enumerate(uniq):
+            pre[p, :len(u)] = u
+        counts, nan = count_pass(shift, pre)
+        slot = np.array([[uniq[p].index(v) for v in prefix[p].tolist()] for p in range(d)])
+        prefix, rank = select_step(np.take_along_axis(counts, slot[:, :, None], axis=1), prefix, rank)
+    return quantile_finish(prefix[:, 0::2], prefix[:, 1::2], frac, nan)
+
+
 def blocks_to_csr(blockindex, d):
     """DEMCopt.blockindex (1-based ranges / index vectors, DEMC.jl:29) is given here as a list
     of 0-based index sequences; returns CSR (offsets, indices) as int32 arrays."""
@@ -332,6 +402,36 @@ class HipEngine:
         self._chk(self._L.demcz_ess(self._h, int(g_from), int(g_to), int(max_lag), _lib.ptr(out.ess), _lib.ptr(out.tau),
                                     _lib.ptr(out.varplus), _lib.ptr(out.pairs, _lib._lp), _lib.ptr(out.converged, _lib._ip)))
         return out
+
+    def select_counts(self, g_from, g_to, shift, prefix):
+        """One counting pass of the quantiles' radix select over this engine's chains (demcz_select_counts): prefix is (d, nprefix)
+        uint64; returns (counts (d, nprefix, 256) int64, nan_count (d,) int64)."""
+        prefix = np.array(prefix, dtype=np.uint64, order="F", ndmin=2)
+        if prefix.shape[0] != self.d:
+            raise ValueError("prefix must be (d, nprefix)")
+        nprefix = prefix.shape[1]
+        counts = np.zeros((self.d, nprefix, 256), dtype=np.int64)
+        nan = np.zeros(self.d, dtype=np.int64)
+        self._chk(self._L.demcz_select_counts(self._h, int(g_from), int(g_to), int(shift), nprefix, _lib.ptr(prefix, _lib._up),
+                                              _lib.ptr(counts, _lib._lp), _lib.ptr(nan, _lib._lp)))
+        return counts, nan
+
+    def quantiles(self, g_from, g_to, probs, with_order_stats=False):
+        """Quantiles per parameter over generations g_from..g_to (demcz_quantiles, Hyndman-Fan type 7, exact selection): d x nq,
+        or a Quantiles tuple (q, lower, upper) with the two order statistics behind every entry."""
+        probs = np.ascontiguousarray(np.atleast_1d(probs), dtype=np.float64)
+        nq, d = probs.size, self.d
+        out = Quantiles(np.empty((d, nq), order="F"), np.empty((d, nq), order="F"), np.empty((d, nq), order="F"))
+        self._chk(self._L.demcz_quantiles(self._h, int(g_from), int(g_to), nq, _lib.ptr(probs), _lib.ptr(out.q),
+                                          _lib.ptr(out.lower), _lib.ptr(out.upper)))
+        return out if with_order_stats else out.q
+
+    def best(self, g_from, g_to):
+        """The best draw of generations g_from..g_to (demcz_best): a Best tuple; chain is 0-based and local to this engine."""
+        v, c, g = C.c_double(), C.c_int64(), C.c_int64()
+        par = np.empty(self.d)
+        self._chk(self._L.demcz_best(self._h, int(g_from), int(g_to), C.byref(v), C.byref(c), C.byref(g), _lib.ptr(par)))
+        return Best(v.value, c.value, g.value, par)
 
     def accept_ratio(self, g_from, g_to):
         out = np.empty(self.N)

@@ -276,6 +276,45 @@ class _Runner:
             if have > L or out.converged.all():
                 return out
 
+    def quantiles(self, g_from, g_to, probs, with_order_stats=False):
+        """Quantiles per parameter over all N_total chains (d x nq, or an engine.Quantiles tuple).  One engine: demcz_quantiles.
+        Several shards: the counts of every pass are integers and additive; the host adds them and steps with demcz_select_step."""
+        if self.lib_exchange:
+            raise NotImplementedError("quantiles over a communicator of several ranks: add select_counts over the ranks on the host "
+                                      "and step with engine.select_step")
+        if not self.host_exchange and len(self.engines) == 1:
+            return self.engines[0].quantiles(g_from, g_to, probs, with_order_stats)
+        from .engine import select_quantiles
+
+        def count_pass(shift, prefix):
+            parts = [e.select_counts(g_from, g_to, shift, prefix) for e in self.engines]
+            both = np.concatenate([sum(c for c, _ in parts).ravel(), sum(n for _, n in parts)])
+            if self.sh is not None and self.sh.world_size > 1:        # (counts stay below 2^53: exact as doubles)
+                both = self.sh.all_reduce_sum(np.ascontiguousarray(both.astype(np.float64))).astype(np.int64)
+            return both[:-self.d].reshape(self.d, -1, 256), both[-self.d:]
+
+        out = select_quantiles(count_pass, self.N_total * (g_to - g_from + 1), self.d, probs)
+        return out if with_order_stats else out.q
+
+    def best(self, g_from, g_to):
+        """The best draw over all N_total chains (an engine.Best tuple with the GLOBAL 0-based chain): the maximum over the engines,
+        ties to the earliest generation, then to the lowest chain."""
+        if self.lib_exchange:
+            raise NotImplementedError("best over a communicator of several ranks: compare engine.best of the ranks on the host")
+        from .engine import Best
+        cands = [Best(b.bestval, b.chain + e.chain_id0 if b.chain >= 0 else -1, b.generation, b.bestpar)
+                 for e, b in ((e, e.best(g_from, g_to)) for e in self.engines)]
+        if self.sh is not None and self.sh.world_size > 1:
+            rows = np.array([[b.bestval, b.chain, b.generation] + list(b.bestpar) for b in cands])
+            rows = np.concatenate(self.sh.all_gather(np.ascontiguousarray(rows)), axis=0)
+            cands = [Best(float(r[0]), int(r[1]), int(r[2]), np.array(r[3:])) for r in rows]
+        best = cands[0]
+        for b in cands[1:]:
+            if b.chain >= 0 and (best.chain < 0 or b.bestval > best.bestval
+                                 or (b.bestval == best.bestval and (b.generation, b.chain) < (best.generation, best.chain))):
+                best = b
+        return best
+
     def changed(self, g_from, g_to):
         c = sum(e.get_changed(g_from, g_to) for e in self.engines)
         if self.sh is not None and self.sh.world_size > 1:

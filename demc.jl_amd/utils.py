@@ -2,9 +2,11 @@
 
 ``Rhat_gelman``, ``mean_cov_chain`` and ``convergence_check`` take the host arrays the reference's
 examples pass them (test/example_normpdf.jl:35-47); the arrays are uploaded and reduced by the same
-kernels the autostop uses.  ``flatten_chain`` is a pure re-indexing (utils.jl:22-32).  Plotting,
-``save_res`` and ``extract_best`` are not reproduced (dead code in Julia >= 1.0).
-Beyond the reference: ``ess_chain``, ``autocov_chain`` and ``posterior_summary`` (effective sample size).
+kernels the autostop uses.  ``flatten_chain`` is a pure re-indexing (utils.jl:22-32).  ``extract_best``
+(utils.jl:120-125) finds the best draw on the device.  Plotting and ``save_res`` are not reproduced (dead code in Julia >= 1.0,
+SURVEY.md Q16).
+Beyond the reference: ``ess_chain``, ``autocov_chain``, ``quantile_chain`` and ``posterior_summary`` (effective sample size and
+quantiles by exact selection).
 Checkpoints: the reference only resumes in memory (``prevrun=``); ``save_checkpoint`` /
 ``load_checkpoint`` put the same information in one ``.npz`` file.
 """
@@ -93,14 +95,51 @@ def autocov_chain(chain, max_lag, device_id=0):
     return autocov_sums_chain(chain, 0, L, device_id) / (2.0 * N * n)
 
 
-def posterior_summary(chain, device_id=0):
+def quantile_chain(chain, probs, device_id=0, with_order_stats=False):
+    """Quantiles per parameter of an Npop x Npar x Ngeneration history over all its draws: Npar x len(probs), Hyndman-Fan type 7
+    (np.quantile's default) between two order statistics found exactly by a radix select on the device (demcz_quantiles_array).
+    `with_order_stats`: a Quantiles tuple (q, lower, upper).  A parameter that holds a NaN is NaN.  Not in the reference."""
+    from .engine import Quantiles
+    chain = _lib.f64(chain, "F")
+    N, d, G = chain.shape
+    probs = np.ascontiguousarray(np.atleast_1d(probs), dtype=np.float64)
+    nq = probs.size
+    out = Quantiles(np.empty((d, nq), order="F"), np.empty((d, nq), order="F"), np.empty((d, nq), order="F"))
+    _chk(_lib.load().demcz_quantiles_array(device_id, _lib.ptr(chain), N, d, G, nq, _lib.ptr(probs), _lib.ptr(out.q),
+                                           _lib.ptr(out.lower), _lib.ptr(out.upper)))
+    return out if with_order_stats else out.q
+
+
+def best_logobj(log_obj, device_id=0):
+    """(bestval, chain, column), 0-based: the maximum of an Npop x Ngeneration log_obj ignoring NaN, ties (by ==) to the earliest
+    generation and then to the lowest chain, as findn(bestval .== log_obj) lists them (demcz_best_array).  All NaN: (nan, -1, -1)."""
+    log_obj = _lib.f64(log_obj, "F")
+    N, G = log_obj.shape
+    v, c, g = C.c_double(), C.c_int64(), C.c_int64()
+    _chk(_lib.load().demcz_best_array(device_id, _lib.ptr(log_obj), N, G, C.byref(v), C.byref(c), C.byref(g)))
+    return v.value, c.value, g.value
+
+
+def extract_best(mc, device_id=0):
+    """(bestval, bestpar) of a run, src/utils.jl:120-125: the largest log_obj and the parameters that gave it."""
+    bestval, c, g = best_logobj(mc.log_obj, device_id)
+    if c < 0:
+        return bestval, np.full(np.shape(mc.chain)[1], np.nan)
+    return bestval, np.array(mc.chain[c, :, g])
+
+
+def posterior_summary(chain, device_id=0, probs=None):
     """Per parameter: mean, sd = sqrt(var+), mcse = sqrt(var+ / ess), ess, rhat, converged (of the ESS: 0 where the lags ran out
-    and ess is an upper bound) -- mean_cov_chain, Rhat_gelman and ess_chain, all reduced on the device."""
+    and ess is an upper bound) -- mean_cov_chain, Rhat_gelman and ess_chain, all reduced on the device.  With `probs`, also
+    quantiles = quantile_chain(chain, probs): Npar x len(probs)."""
     mean, _ = mean_cov_chain(chain, device_id=device_id)
     e = ess_chain(chain, device_id=device_id)
     with np.errstate(all="ignore"):
-        return dict(mean=mean, sd=np.sqrt(e.varplus), mcse=np.sqrt(e.varplus / e.ess), ess=e.ess,
-                    rhat=Rhat_gelman(chain, device_id=device_id), converged=e.converged)
+        out = dict(mean=mean, sd=np.sqrt(e.varplus), mcse=np.sqrt(e.varplus / e.ess), ess=e.ess,
+                   rhat=Rhat_gelman(chain, device_id=device_id), converged=e.converged)
+    if probs is not None:
+        out["quantiles"] = quantile_chain(chain, probs, device_id=device_id)
+    return out
 
 
 def convergence_check(chain, log_obj, figure_path=None, verbose=True, parnames=None, device_id=0):

@@ -270,6 +270,52 @@ int32_t demcz_ess_from_sums(int32_t d, int64_t m, int64_t n, int64_t nlags, cons
 int32_t demcz_ess(demcz_handle* h, int64_t g_from, int64_t g_to, int64_t max_lag,
                   double* ess, double* tau, double* varplus, int64_t* pairs, int32_t* converged);
 
+/* Quantiles per parameter over generations g_from..g_to of the on-device history, by exact selection (not
+ * in the reference).  All N chains and all w = g_to-g_from+1 generations are used, S = N w draws per parameter; any w >= 1.
+ * Draws are ordered by the key of their bit pattern, key = bits ^ 0xFFFFFFFFFFFFFFFF when the sign bit is set and
+ * bits | 1 << 63 otherwise:  -NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN.  The quantile of probability q in [0, 1] is
+ * Hyndman-Fan type 7 (np.quantile's and Julia's default): h = (double)(S-1) q, lo = floor(h) clipped to [0, S-1],
+ * hi = min(lo+1, S-1), frac = h - lo, a = x_(lo), b = x_(hi) (0-based order statistics); the result is a when frac == 0 or
+ * a == b and a + frac (b - a) otherwise, each operation rounded.  A parameter whose window holds a NaN is NaN in q, a and b.
+ * The order statistics are found by a radix select over the key, one byte per pass from the top: eight passes, each reading
+ * the window once however many probabilities were asked for.  Range and state errors are demcz_rhat's.
+ *
+ * demcz_quantile_plan    host code, no device: rank_lo, rank_hi, frac (nq values each) for S draws.  INVALID_ARGUMENT for nq < 1,
+ *                        nq > 16, S < 1, or a probability that is NaN or outside [0, 1]; unsorted and repeated ones are fine.
+ * demcz_select_counts    one counting pass over the LOCAL chains, for hosts that add over shards: for parameter p and prefix u,
+ *                        counts[b + 256 (u + nprefix p)] = draws with (key >> (shift+8)) == prefix[p + d u] and
+ *                        ((key >> shift) & 255) == b.  shift: a multiple of 8 in 0..56; at 56 every draw matches every prefix.
+ *                        nprefix: 1..32; the prefixes of one parameter should be distinct (a draw counts towards the first it
+ *                        matches).  nan_count[p] = draws with x != x (may be NULL).  The counts are integers: exact, and
+ *                        additive over shards in any order.
+ * demcz_select_step      host code, no device: one byte of the walk.  counts: 256 x nr x d as above with one column per rank
+ *                        (already added over shards; ranks that share a prefix share its counts); for every (p, r) the first
+ *                        byte whose cumulative count exceeds rank[p + d r] is appended to prefix[p + d r] (prefix << 8 | byte)
+ *                        and the count below it is subtracted from the rank.  A rank not below the total of its counts:
+ *                        INVALID_ARGUMENT, and nothing is written.  Start from prefix = 0, rank = the rank among all S draws;
+ *                        after the pass at shift 0 the prefix is the key of the order statistic.
+ * demcz_quantile_finish  host code, no device: keys back to doubles, the formula, the NaN rule.  key_lo, key_hi, q, lower, upper:
+ *                        d x nq column-major; frac: nq; nan_count (d), lower and upper may be NULL.
+ * demcz_quantiles        the whole statistic; q (and lower = a, upper = b unless NULL): d x nq column-major.  On a handle whose
+ *                        communicator has more than one rank: DEMCZ_ERR_INVALID_ARGUMENT -- add demcz_select_counts over the
+ *                        ranks on the host and step with demcz_select_step. */
+int32_t demcz_quantile_plan(int64_t S, int32_t nq, const double* probs, int64_t* rank_lo, int64_t* rank_hi, double* frac);
+int32_t demcz_select_counts(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t shift, int32_t nprefix,
+                            const uint64_t* prefix, int64_t* counts, int64_t* nan_count);
+int32_t demcz_select_step(int32_t d, int32_t nr, const int64_t* counts, uint64_t* prefix, int64_t* rank);
+int32_t demcz_quantile_finish(int32_t d, int32_t nq, const uint64_t* key_lo, const uint64_t* key_hi, const double* frac,
+                              const int64_t* nan_count, double* q, double* lower, double* upper);
+int32_t demcz_quantiles(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t nq, const double* probs,
+                        double* q, double* lower, double* upper);
+
+/* The best draw of the window (extract_best, src/utils.jl:120-125): bestval = the maximum of log_obj over generations
+ * g_from..g_to, ignoring NaN (+inf can win).  Ties by == (0.0 and -0.0 tie) go to the earliest generation, then to the lowest
+ * chain: the reference's column-major findn(...)[1].  chain: 0-based local chain; generation: numbered as g_from..g_to;
+ * bestpar (d values, may be NULL) = chain[chain, :, generation] of the history.  When every entry is NaN, bestval is NaN, both
+ * indices are -1 and bestpar is NaN.  Range and state errors are demcz_rhat's. */
+int32_t demcz_best(demcz_handle* h, int64_t g_from, int64_t g_to, double* bestval, int64_t* chain, int64_t* generation,
+                   double* bestpar);
+
 /* Per-chain acceptance ratio over generations g_from..g_to:
  * sum(diff(log_obj, dims=2) .!= 0, dims=2) ./ (G-1), src/utils.jl:61.  ratio: N values. */
 int32_t demcz_accept_ratio(demcz_handle* h, int64_t g_from, int64_t g_to, double* ratio);
@@ -380,7 +426,9 @@ int32_t demcz_set_rng_offset(demcz_handle* h, int64_t generations);
  *   demcz_rhat_array          Rhat_gelman(chain, N, G, d)              src/utils.jl:2-20
  *   demcz_accept_ratio_array  sum(diff(log_obj,dims=2).!=0,dims=2)./(G-1)   src/utils.jl:61
  *   demcz_mean_cov_array      mean_cov_chain(chain, N, G, d)           src/utils.jl:96-111
- *   demcz_autocov_sums_array / demcz_ess_array   the two calls above over the whole array (not in the reference) */
+ *   demcz_autocov_sums_array / demcz_ess_array   the two calls above over the whole array (not in the reference)
+ *   demcz_quantiles_array     demcz_quantiles over the whole array (not in the reference)
+ *   demcz_best_array          demcz_best over an N x G log_obj; column: 0-based              src/utils.jl:120-125 */
 int32_t demcz_rhat_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, double* rhat);
 int32_t demcz_accept_ratio_array(int32_t device_id, const double* log_obj, int64_t N, int64_t G, double* ratio);
 int32_t demcz_mean_cov_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, double* mean, double* cov);
@@ -388,6 +436,10 @@ int32_t demcz_autocov_sums_array(int32_t device_id, const double* chain, int64_t
                                  int64_t lag_from, int64_t lag_to, double* sums);
 int32_t demcz_ess_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, int64_t max_lag,
                         double* ess, double* tau, double* varplus, int64_t* pairs, int32_t* converged);
+int32_t demcz_quantiles_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, int32_t nq,
+                              const double* probs, double* q, double* lower, double* upper);
+int32_t demcz_best_array(int32_t device_id, const double* log_obj, int64_t N, int64_t G, double* bestval, int64_t* chain,
+                         int64_t* column);
 
 /* Introspection for benchmarks and tests. */
 int32_t demcz_get_info(const demcz_handle* h, int64_t* M, int64_t* launches_window, int32_t* lanes_per_chain);

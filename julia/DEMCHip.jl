@@ -376,6 +376,36 @@ function ess_chain(chain::Array{Float64,3}; max_lag=0, device_id=0)
               device_id, chain, Npop, Npar, Ngeneration, max_lag, e, tau, vp, pairs, conv))
     (ess=e, tau=tau, varplus=vp, pairs=pairs, converged=conv)
 end
+# quantiles per parameter by exact selection on the device (Hyndman-Fan type 7, Julia's `quantile` default; not in the reference):
+# (q, lower, upper), each d x length(probs) -- lower / upper are the two order statistics behind every entry
+function quantiles(h, g_from, g_to, d, probs::Vector{Float64})
+    nq = length(probs); q = zeros(d, nq); lo = zeros(d, nq); hi = zeros(d, nq)
+    chk(ccall((:demcz_quantiles, libdemcz), Int32, (Ptr{Cvoid}, Int64, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+              h, g_from, g_to, nq, probs, q, lo, hi), h)
+    (q=q, lower=lo, upper=hi)
+end
+function quantile_chain(chain::Array{Float64,3}, probs::Vector{Float64}; device_id=0)
+    Npop, Npar, Ngeneration = size(chain)
+    nq = length(probs); q = zeros(Npar, nq); lo = zeros(Npar, nq); hi = zeros(Npar, nq)
+    chk(ccall((:demcz_quantiles_array, libdemcz), Int32, (Int32, Ptr{Float64}, Int64, Int32, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+              device_id, chain, Npop, Npar, Ngeneration, nq, probs, q, lo, hi))
+    q
+end
+# the best draw (utils.jl:120-125): ties go to the earliest generation, then to the lowest chain, as findn lists them.
+# best(h, ...) -> (bestval, chain, generation, bestpar) with a 1-based chain (0 when every entry is NaN)
+function best(h, g_from, g_to, d)
+    v = Ref{Float64}(NaN); c = Ref{Int64}(-1); g = Ref{Int64}(-1); par = zeros(d)
+    chk(ccall((:demcz_best, libdemcz), Int32, (Ptr{Cvoid}, Int64, Int64, Ref{Float64}, Ref{Int64}, Ref{Int64}, Ptr{Float64}),
+              h, g_from, g_to, v, c, g, par), h)
+    (bestval=v[], chain=c[] + 1, generation=g[], bestpar=par)
+end
+function extract_best(mc)                                                                                    # utils.jl:120-125
+    v = Ref{Float64}(NaN); c = Ref{Int64}(-1); g = Ref{Int64}(-1)
+    chk(ccall((:demcz_best_array, libdemcz), Int32, (Int32, Ptr{Float64}, Int64, Int64, Ref{Float64}, Ref{Int64}, Ref{Int64}),
+              0, mc.log_obj, size(mc.log_obj, 1), size(mc.log_obj, 2), v, c, g))
+    c[] < 0 && return v[], fill(NaN, size(mc.chain, 2))
+    v[], mc.chain[c[] + 1, :, g[] + 1]
+end
 
 # ---- checkpoint: what a resumed run needs (the reference resumes in memory only, demcz.jl:18-22) ----------------------------
 struct Checkpoint
