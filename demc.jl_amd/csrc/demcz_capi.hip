@@ -7,6 +7,7 @@
 #include "demcz_kernels_acf.h"
 #include "demcz_kernels_sel.h"
 #include "demcz_select_host.h"
+#include "demcz_slab_plan.h"
 #include "demcz_kernels_ml.h"
 #include "demcz_kernels_pc.h"
 #include "demcz_kernels_lr.h"
@@ -275,6 +276,9 @@ struct demcz_handle {
     int64_t pinned_cap = 0;
     bool timing = false;              // demcz_set_kernel_timing: events around every window-kernel launch
     std::vector<std::pair<hipEvent_t, hipEvent_t>> timed;
+    std::vector<int32_t> timed_slabs;    // autostop slabs each bracket covers (demcz_run_checked groups them; 1 otherwise)
+    int32_t bracket_slabs = 1;        // demcz_run_checked -> demcz_run: slabs of the call being made ...
+    int64_t plan_next = 0;            // ... and the generations of the launch that follows it (0: not known)
     std::vector<double> series_start_ms, series_dur_ms;     // of the brackets the last demcz_get_kernel_time summed up
     int64_t timed_launches = 0;
     int64_t live_wg_cap = -1;         // consumer workgroups a LIVE launch may have (all must be resident at once); -1: not asked yet
@@ -291,6 +295,7 @@ struct demcz_handle {
     // and log_obj histories in one too -- what window_kernel_ps2 needs to address everything with 32-bit offsets
     bool arena = false, rec_in_arena = false, hist_joint = false;
     int64_t arena_gens = 0;           // generations each record buffer of the arena holds
+    int64_t arena_span = 0;           // generations a LIVE launch of the arena may cover (demcz_slab_plan.h: arena_span)
     double* arena_rec[2] = {nullptr, nullptr};
     double* arena_temp = nullptr;
     int64_t rec_cap = 0;              // generations each buffer holds
@@ -660,6 +665,7 @@ static int32_t group_verify(demcz_handle* h);
 static int32_t live_failed(demcz_handle* h, bool& failed);
 static void live_release(demcz_handle* h);
 static int64_t live_span(demcz_handle* h);
+static int64_t rec_target_bytes(bool dual);
 static int32_t rec_reserve(demcz_handle* h, int64_t gens);
 static int32_t check_hist_range(demcz_handle* h, int64_t g_from, int64_t g_to, const char* who);
 static bool ps2_applicable(const demcz_handle* h, const WindowParams& P);
@@ -1004,18 +1010,15 @@ extern "C" int32_t demcz_create(demcz_handle** out, const demcz_config* cfg)
         if (h->lanes == DEMCZ_LAYOUT_SPLIT && h->split_kind == SPLIT_WAVE && d <= 5 && !h->prog_wave && !getenv("DEMCZ_NO_PS2")) {
             // (record buffers as demcz_run would size them: a LIVE launch's span, bounded by the history window; a caller that
             //  outruns the arena gets separate buffers and the general kernel)
-            const int64_t per_gen = (int64_t)(d + 2) * N_for_arena * (int64_t)sizeof(double);
-            // (64 MiB of records per buffer: 1170 generations at C2; a two-chain handle has up to twice the chains: 128 MiB, so that
-            //  an autostop slab of 1000 generations is still ONE launch at 2048 chains)
-            int64_t ag = std::max<int64_t>(cfg->K, std::min<int64_t>((int64_t)((h->ps_dual ? 128ll : 64ll) << 20) / per_gen, 1 << 20));
-            if (cfg->Gcap > 0) ag = std::min<int64_t>(ag, std::max<int64_t>(cfg->Gcap, 1024));      // (no history kept: launches are as long as a call)
-            ag = std::max<int64_t>(ag, (int64_t)cfg->K * 4);
-            const size_t zb = (zbytes + 255) & ~(size_t)255;
-            const size_t rb = (((size_t)ag * (size_t)(d + 2) * (size_t)N_for_arena + REC_PAD) * sizeof(double) + 255) & ~(size_t)255;
-            const size_t tb = (((size_t)ag + 64) * sizeof(double) + 255) & ~(size_t)255;
-            if (zb + 2 * rb + tb < 0xF0000000ull) {
+            // (demcz_slab_plan.h: 64 MiB of records per buffer -- 1170 generations at C2 --, twice the bytes for a two-chain handle,
+            //  which has up to twice the chains; shorter buffers beside an archive that leaves less room below the 32-bit reach)
+            const ArenaSpan as = arena_span(zbytes, N_for_arena, d, cfg->K, cfg->Gcap, rec_target_bytes(h->ps_dual), (int64_t)REC_PAD);
+            const int64_t ag = as.gens;
+            const size_t zb = as.zb, rb = as.rb, tb = as.tb;
+            if (ag > 0 && zb + 2 * rb + tb < ARENA_LIMIT) {
                 h->arena = true;
                 h->arena_gens = ag;
+                h->arena_span = as.span;
                 CRCHK(g_dev_pool.acquire((void**)&h->dZ, zb + 2 * rb + tb, cfg->device_id));
                 h->dZ_bytes = zb + 2 * rb + tb;
                 unsigned char* base = reinterpret_cast<unsigned char*>(h->dZ);
@@ -2511,6 +2514,19 @@ static bool peer_capable(const demcz_handle* h)
     return h->lanes == DEMCZ_LAYOUT_SPLIT && h->split_kind != SPLIT_PC8 && h->split_kind != SPLIT_NONE;
 }
 
+// DEMCZ_REC_MIB: MiB of draw records per buffer instead of the built-in choice (measurements)
+static int64_t rec_env_mib()
+{
+    static const int64_t env_mib = getenv("DEMCZ_REC_MIB") ? atol(getenv("DEMCZ_REC_MIB")) : 0;
+    return env_mib;
+}
+
+static int64_t rec_target_bytes(bool dual)
+{
+    const int64_t mib = rec_env_mib() > 0 ? rec_env_mib() : (dual ? 2 * ARENA_REC_MIB : ARENA_REC_MIB);
+    return mib << 20;
+}
+
 static int64_t live_span(demcz_handle* h)
 {
     // (sharded: only with the rows handed over inside the launches -- peer_mode 2; otherwise a launch ends at the exchange)
@@ -2523,13 +2539,15 @@ static int64_t live_span(demcz_handle* h)
     if ((h->cfg.N + per_wg - 1) / per_wg > live_wg_capacity(h)) return 0;
     if (!live_claim(h)) return 0;
     const int64_t per_gen = rec_fields(h) * h->cfg.N * (int64_t)sizeof(double);
-    // 64 MiB of records per buffer inside the arena (C2: 1170 generations, more than an autostop slab), 1 GiB outside it (C4's
+    // Inside the arena: what demcz_create sized its buffers for (arena_span, demcz_slab_plan.h: 64 MiB per buffer, C2 1170
+    // generations -- longer launches are not faster there, profiles/r10_launch_span.txt).  Outside it 1 GiB of records per buffer (C4's
     // shard 5960 generations instead of 372, C5 5450 instead of 340, C3 820 instead of 51; allocated as launches need it): every
     // launch boundary costs 15-25 us of gap, first-pass latency and tail imbalance -- C4's shard 7.4 -> 6.1 us per K-window,
     // C5 22.3 -> 21.5 (profiles/r03f_launch_span.txt)
-    static const int64_t env_mib = getenv("DEMCZ_REC_MIB") ? atol(getenv("DEMCZ_REC_MIB")) : 0;
+    if (h->arena) return std::max<int64_t>(h->cfg.K, std::min<int64_t>(h->arena_span, SPAN_GENS_MAX));
+    const int64_t env_mib = rec_env_mib();
     // (block updates, SPLIT_MLB: flat between 64 and 256 MiB, 4 % slower at 1 GiB -- 128)
-    const int64_t mib = env_mib > 0 ? env_mib : (h->arena ? (h->ps_dual ? 128 : 64) : (h->split_kind == SPLIT_MLB) ? 128 : 1024);
+    const int64_t mib = env_mib > 0 ? env_mib : (h->split_kind == SPLIT_MLB) ? 128 : 1024;
     const int64_t span = (int64_t)(mib << 20) / per_gen;
     return std::max<int64_t>(h->cfg.K, std::min<int64_t>(span, 1 << 20));
 }
@@ -2823,7 +2841,7 @@ extern "C" int32_t demcz_run(demcz_handle* h, int64_t g_from, int64_t g_to, doub
                 if (dc.ngen < n) n = std::max<int64_t>((dc.ngen / K) * K, K);
             } else {
                 const int64_t per_gen = rec_fields(h) * h->cfg.N * (int64_t)sizeof(double);
-                const int64_t cold = std::max<int64_t>(K, ((int64_t)((h->ps_dual ? 128ll : 64ll) << 20) / per_gen / K) * K);
+                const int64_t cold = std::max<int64_t>(K, ((int64_t)((h->ps_dual ? 2 * COLD_REC_MIB : COLD_REC_MIB) << 20) / per_gen / K) * K);
                 n = std::min(n, cold);
             }
             if (h->dual_now) n = std::max<int64_t>((n / PS2_R) * PS2_R, PS2_R);
@@ -2859,7 +2877,8 @@ extern "C" int32_t demcz_run(demcz_handle* h, int64_t g_from, int64_t g_to, doub
             if (E > 0 && !h->external_append) nend = ((nend / K + E - 1) / E) * E * (int64_t)K;
             int64_t nM = h->M, nn = nend - ng + 1;
             const int64_t rows_n = h->cfg.N * shards;
-            if (live_max > 0) nn = std::min(live_max, (w_end < g_to) ? g_to - w_end : G);   // a next call is taken to be as long as this one
+            // a next call is taken to be as long as this one -- unless demcz_run_checked knows what follows
+            if (live_max > 0) nn = std::min(live_max, (w_end < g_to) ? g_to - w_end : (h->plan_next > 0 ? h->plan_next : G));
             if (h->external_append) nn = 0;                      // the caller appends: M is not ours to predict
             else if (E == 0) nM = h->M_app + nbound * rows_n;                    // ... the rows appended now
             else for (const auto& pe : h->pending) if (pe.visible_from <= ng) nM = pe.M_after;   // ... or admitted by then
@@ -2925,6 +2944,7 @@ extern "C" int32_t demcz_run(demcz_handle* h, int64_t g_from, int64_t g_to, doub
         HIPCHK(h, hipEventRecord(tev.b, h->stream));
         h->after_launch_ev = tev.b;
         h->timed.emplace_back(tev.a, tev.b);
+        h->timed_slabs.push_back(std::max(h->bracket_slabs, 1));
         tev.a = tev.b = nullptr;
         h->timed_launches += timed_launches;
     }
@@ -3068,7 +3088,9 @@ extern "C" int32_t demcz_get_changed_total(demcz_handle* h, int64_t g_from, int6
 }
 
 // ---- R-hat ---------------------------------------------------------------------------------------
-struct RhatPlan { int64_t N, w, s0, n, nd, need; int d, nchunk; double *S1, *S2, *mean_j, *s2_j, *sums; };
+// (slabs > 1: a batch of checks over consecutive windows of w generations, slab z in its own slice of `need` doubles at
+//  h->d_scratch + z need; their statistics side by side in `out`, slabs x d doubles behind the last slice)
+struct RhatPlan { int64_t N, w, s0, n, nd, need; int d, nchunk; double *S1, *S2, *mean_j, *s2_j, *sums; int slabs = 1; double* out = nullptr; };
 
 // The window's shape and what its plan needs of the scratch buffer (r.need doubles); allocates and launches nothing.
 static int rhat_chunks(int64_t n) { return (int)std::min<int64_t>(std::max<int64_t>(1, n / 32), 32); }
@@ -3092,28 +3114,36 @@ static int32_t rhat_plan(demcz_handle* h, int64_t g_from, int64_t g_to, RhatPlan
 static int32_t rhat_scratch(demcz_handle* h, RhatPlan& r, int64_t extra, bool compute, hipStream_t qs = nullptr)
 {
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
-    int32_t rc = ensure_scratch(h, r.need + extra);
+    int32_t rc = ensure_scratch(h, r.need * r.slabs + (r.slabs > 1 ? (int64_t)r.slabs * r.d : 0) + extra);
     if (rc) return rc;
     r.S1 = h->d_scratch;
     r.S2 = r.S1 + 2 * r.nchunk * r.nd;
     r.mean_j = r.S2 + 2 * r.nchunk * r.nd;
     r.s2_j = r.mean_j + 2 * r.nd;
     r.sums = r.s2_j + 2 * r.nd;          // [0,d): stage 0 / grand mean; [d,3d): stage 1; [3d,4d): R-hat
+    r.out = r.slabs > 1 ? h->d_scratch + r.need * r.slabs : r.sums + 3 * r.d;
     if (compute) {
         const int bs = 256;
         const unsigned gx = (unsigned)((r.nd + bs - 1) / bs);
         if (!qs) qs = h->stream;
-        hipLaunchKernelGGL(rhat_moments_kernel, dim3(gx, 2 * r.nchunk), dim3(bs), 0, qs, h->dchain, r.N, r.d, r.s0, r.n, r.nchunk, r.S1, r.S2);
-        hipLaunchKernelGGL(rhat_chainstats_kernel, dim3(gx, 2), dim3(bs), 0, qs, h->dchain, r.N, r.d, r.s0, r.n, r.nchunk, r.S1, r.S2, r.mean_j, r.s2_j);
+        hipLaunchKernelGGL(rhat_moments_kernel, dim3(gx, 2 * r.nchunk, r.slabs), dim3(bs), 0, qs, h->dchain, r.N, r.d, r.s0, r.n, r.nchunk, r.S1, r.S2,
+                           r.w, r.need);
+        hipLaunchKernelGGL(rhat_chainstats_kernel, dim3(gx, 2, r.slabs), dim3(bs), 0, qs, h->dchain, r.N, r.d, r.s0, r.n, r.nchunk, r.S1, r.S2, r.mean_j,
+                           r.s2_j, r.w, r.need);
         HIPCHK(h, hipGetLastError());
     }
     return DEMCZ_OK;
 }
 
-static int32_t rhat_prepare(demcz_handle* h, int64_t g_from, int64_t g_to, RhatPlan& r, bool compute, hipStream_t qs = nullptr)
+static int32_t rhat_prepare(demcz_handle* h, int64_t g_from, int64_t g_to, RhatPlan& r, bool compute, hipStream_t qs = nullptr, int slabs = 1)
 {
     int32_t rc = rhat_plan(h, g_from, g_to, r);
     if (rc) return rc;
+    if (slabs > 1) {
+        rc = check_hist_range(h, g_from, g_from + r.w * slabs - 1, "demcz_run_checked");
+        if (rc) return rc;
+        r.slabs = slabs;
+    }
     return rhat_scratch(h, r, 0, compute, qs);
 }
 
@@ -3144,7 +3174,9 @@ extern "C" int32_t demcz_rhat_partial(demcz_handle* h, int64_t g_from, int64_t g
 // if the caller wants the copy to be asynchronous); does not wait.
 // `side`: unsharded runs only -- the statistic of a finished slab is computed on a second stream, behind an event,
 // beside the next slab's window kernel (which leaves most of the chip idle at small N).
-static int32_t rhat_enqueue(demcz_handle* h, int64_t g_from, int64_t g_to, double* out, bool side = false)
+// `slabs` > 1 (unsharded only): the checks of that many consecutive windows, g_from..g_to the first, as one batch -- three
+// launches and one copy of slabs x d doubles to `out`.
+static int32_t rhat_enqueue(demcz_handle* h, int64_t g_from, int64_t g_to, double* out, bool side = false, int slabs = 1)
 {
     RhatPlan r;
     hipStream_t qs = h->stream;
@@ -3202,7 +3234,8 @@ static int32_t rhat_enqueue(demcz_handle* h, int64_t g_from, int64_t g_to, doubl
             if (hipEventRecord(h->rhat_side_ev, qs) == hipSuccess) h->rhat_side_pending = true;
         }
     } side_mark{h, qs};
-    int32_t rc = rhat_prepare(h, g_from, g_to, r, true, qs);
+    if (slabs > 1 && h->comm) return fail(h, DEMCZ_ERR_STATE, "demcz_run_checked: batched checks are for unsharded runs");
+    int32_t rc = rhat_prepare(h, g_from, g_to, r, true, qs, slabs);
     if (rc) return rc;
     const int d = r.d;
     const int64_t n = r.n;
@@ -3210,9 +3243,9 @@ static int32_t rhat_enqueue(demcz_handle* h, int64_t g_from, int64_t g_to, doubl
     const bool sharded = (h->comm != nullptr);
     double* sums = r.sums;               // [0,d): sum_j mean_j; [d,3d): stage-1 sums; [3d,4d): R-hat
     if (!sharded) {
-        hipLaunchKernelGGL(rhat_tail_kernel, dim3(d), dim3(256), 0, qs, r.mean_j, r.s2_j, r.N, d, (double)n, (double)m, sums + 3 * d);
+        hipLaunchKernelGGL(rhat_tail_kernel, dim3(d, r.slabs), dim3(256), 0, qs, r.mean_j, r.s2_j, r.N, d, (double)n, (double)m, r.out, r.need);
         HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(out, sums + 3 * d, (size_t)d * sizeof(double), hipMemcpyDeviceToHost, qs));
+        HIPCHK(h, hipMemcpyAsync(out, r.out, (size_t)r.slabs * d * sizeof(double), hipMemcpyDeviceToHost, qs));
         return DEMCZ_OK;
     }
     // stage 0 -> all-reduce -> stage 1 with the grand mean formed on the device -> all-reduce ->
@@ -4541,18 +4574,53 @@ static int32_t run_checked_body(demcz_handle* h, int64_t g_from, int64_t g_to, d
         if (!h->spec_ev) HIPCHK(h, hipEventCreateWithFlags(&h->spec_ev, hipEventDisableTiming));
     }
     bool ahead = false;                 // the slab starting at g has already been enqueued
+    // Nothing decided per slab, one GPU, immediate visibility, appends owned by the library: consecutive slabs are ONE demcz_run
+    // call -- as few window launches as the record span allows, no launch boundary, event bracket or stream hop per slab -- and
+    // their checks one batch on the side stream, gated on the call's last launch, beside the next group (slab_group_end,
+    // demcz_slab_plan.h; the call's last slab stays a launch of its own, so that one slab's check trails the call as before).
+    const bool grouped = monitor && !h->comm && h->lag == 0 && !h->external_append;
+    int64_t max_slabs = 1;
+    if (grouped && h->cfg.Gcap > 0) {
+        // the largest batch's scratch, before anything is enqueued (growing it synchronises): at most 256 MiB of slices, and
+        // what the span allows whatever the length of THIS call -- a longer call later finds it there
+        const int64_t need1 = rhat_need(N * d, d, rhat_chunks(every / 2));
+        const int64_t ls0 = live_span(h);
+        max_slabs = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(SLAB_GROUP_MAX, ((int64_t)1 << 25) / need1), (ls0 > 0 ? ls0 : h->cfg.Gcap) / every + 1));
+        rc = ensure_scratch(h, max_slabs * (need1 + d));
+    }
+    // where a launch has to start: at the debug hook's generation; where a redo goes LIVE again (demcz_run re-arms at its entry)
+    auto cut_now = [h]() {
+        int64_t cut = 0;
+        if (h->live_fault_polls != 0) cut = h->live_fault_g;
+        if (h->no_live && h->rearm_from >= 0 && (cut == 0 || h->rearm_from + 1 < cut)) cut = h->rearm_from + 1;
+        return cut;
+    };
     while (g <= g_to && rc == DEMCZ_OK) {
-        const int64_t nxt = std::min(g_to, ((g - 1) / every + 1) * every);
+        int64_t nxt = std::min(g_to, ((g - 1) / every + 1) * every);
+        if (grouped) {
+            const int64_t ls = live_span(h);
+            const int64_t span = ls > 0 ? ls : INT64_MAX;
+            nxt = slab_group_end(g, g_to, every, span, cut_now(), max_slabs);
+            h->bracket_slabs = (int32_t)(slab_ends_in(g, nxt, every) + (nxt % every != 0 ? 1 : 0));
+            // (what the call's last launch prepares draws for: the first launch of the next group)
+            h->plan_next = nxt < g_to ? std::min<int64_t>(span, slab_group_end(nxt + 1, g_to, every, span, cut_now(), max_slabs) - nxt) : 0;
+        }
         if (!ahead) rc = demcz_run(h, g, nxt, gamma, temperature ? temperature + (g - g_from) : nullptr);
+        h->bracket_slabs = 1;
+        h->plan_next = 0;
         ahead = false;
         if (rc) break;
-        if (nxt % every == 0 && nxt - every >= h->g0) {          // demcz.jl:39-41
+        // the checks of the slab ends inside g..nxt (demcz.jl:39-41): windows c0 - every + 1 .. c0, c0 + 1 .. c0 + every, ...
+        int64_t c0 = slab_end_at_or_after(g, every);
+        while (c0 <= nxt && c0 - every < h->g0) c0 += every;
+        const int64_t nck = c0 <= nxt ? (nxt - c0) / every + 1 : 0;
+        if (nck > 0) {
             double* slot = pinned + (size_t)checks * d;
             // (the call's last slab: nothing follows it on the compute stream, so its check goes there -- no hop to the side
             //  stream, ~10 us of event latency, at the end of every call)
-            rc = rhat_enqueue(h, nxt - every + 1, nxt, slot, /*side=*/monitor && nxt < g_to);
+            rc = rhat_enqueue(h, c0 - every + 1, c0, slot, /*side=*/monitor && nxt < g_to, (int)nck);
             if (rc) break;
-            ++checks;
+            checks += (int32_t)nck;
             if (!monitor) {
                 int64_t M_before = 0;
                 if (speculate && nxt < g_to) {
@@ -4822,7 +4890,9 @@ extern "C" int32_t demcz_get_kernel_time(demcz_handle* h, int64_t* launches, dou
         float ms = 0.0f, st = 0.0f;
         HIPCHK(h, hipEventElapsedTime(&ms, pr.first, pr.second));
         if (&pr != &h->timed.front()) HIPCHK(h, hipEventElapsedTime(&st, h->timed.front().first, pr.first));   // (an event against itself faults in the runtime)
-        h->series_start_ms.push_back(st); h->series_dur_ms.push_back(ms);
+        // a bracket over k autostop slabs (demcz_run_checked): k entries of equal share -- means, not events
+        const int32_t k = h->timed_slabs[(size_t)(&pr - &h->timed.front())];
+        for (int32_t i = 0; i < k; ++i) { h->series_start_ms.push_back((double)st + i * ((double)ms / k)); h->series_dur_ms.push_back((double)ms / k); }
         total += ms;
     }
     for (auto& pr : h->timed) {
@@ -4832,6 +4902,7 @@ extern "C" int32_t demcz_get_kernel_time(demcz_handle* h, int64_t* launches, dou
     if (launches) *launches = h->timed_launches;
     if (milliseconds) *milliseconds = total;
     h->timed.clear();
+    h->timed_slabs.clear();
     h->timed_launches = 0;
     return DEMCZ_OK;
 }

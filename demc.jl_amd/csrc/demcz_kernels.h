@@ -654,13 +654,19 @@ __global__ void append_batch_kernel(double* Z, int64_t ZS, int64_t base, const d
 //   rhat_chainstats_kernel: mean_j = x0 + S1/n, s_j^2 = (S2 - S1^2/n)/(n-1) per split-chain.
 //   rhat_reduce_kernel stage 0: sum_j mean_j per parameter; stage 1 (given the grand mean):
 //       sum_j (mean_j - grand)^2 and sum_j s_j^2.  Fixed-order tree reductions: deterministic.
+//   A batch of checks (demcz_run_checked, several slabs per launch): blockIdx.z of the moments and chain-statistics kernels,
+//   blockIdx.y of the tail kernel, is the slab; slab z reads the window s0 + z w and works in its own slice of the scratch,
+//   `slice` doubles behind the slab before it.  Every thread adds the same values in the same order as with one slab.
 // ------------------------------------------------------------------------------------------------
 __global__ void rhat_moments_kernel(const double* chain, int64_t N, int d, int64_t s0, int64_t n, int nchunk,
-                                    double* S1, double* S2)
+                                    double* S1, double* S2, int64_t w, int64_t slice)
 {
-    // grid: x over N*d (chain fastest), y = h * nchunk + chunk
+    // grid: x over N*d (chain fastest), y = h * nchunk + chunk, z = slab
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N * d) return;
+    s0 += (int64_t)blockIdx.z * w;
+    S1 += (int64_t)blockIdx.z * slice;
+    S2 += (int64_t)blockIdx.z * slice;
     const int h = blockIdx.y / nchunk, ck = blockIdx.y % nchunk;
     const int64_t per = (n + nchunk - 1) / nchunk;
     const int64_t t0 = ck * per, t1 = (t0 + per < n) ? t0 + per : n;
@@ -693,10 +699,15 @@ __global__ void rhat_moments_kernel(const double* chain, int64_t N, int d, int64
 }
 
 __global__ void rhat_chainstats_kernel(const double* chain, int64_t N, int d, int64_t s0, int64_t n, int nchunk,
-                                       const double* S1, const double* S2, double* mean_j, double* s2_j)
+                                       const double* S1, const double* S2, double* mean_j, double* s2_j, int64_t w, int64_t slice)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N * d) return;
+    s0 += (int64_t)blockIdx.z * w;
+    S1 += (int64_t)blockIdx.z * slice;
+    S2 += (int64_t)blockIdx.z * slice;
+    mean_j += (int64_t)blockIdx.z * slice;
+    s2_j += (int64_t)blockIdx.z * slice;
     const int h = blockIdx.y;
     const int64_t stride = N * d;
     const double x0 = chain[i + stride * (s0 + h * n)];
@@ -756,10 +767,13 @@ __global__ void __launch_bounds__(256) rhat_reduce_kernel(const double* mean_j, 
 // Unsharded runs: both reduce stages and utils.jl:13-18 for one parameter in one workgroup -- the same
 // per-thread accumulation and tree order as rhat_reduce_kernel (bit-identical), two launches fewer per check.
 __global__ void __launch_bounds__(256) rhat_tail_kernel(const double* mean_j, const double* s2_j, int64_t N, int d,
-                                                        double n, double m, double* rhat)
+                                                        double n, double m, double* rhat, int64_t slice)
 {
     __shared__ double ra[256], rb[256];
     const int p = blockIdx.x;
+    mean_j += (int64_t)blockIdx.y * slice;       // grid (d, slabs): slab y writes rhat[y d + p]
+    s2_j += (int64_t)blockIdx.y * slice;
+    rhat += (int64_t)blockIdx.y * d;
     const int64_t stride = N * d;
     double a = 0.0, b = 0.0;
     int64_t h0 = 0, c0 = threadIdx.x;              // (h, c) = (k / N, k % N) of the thread's first element

@@ -276,7 +276,8 @@ class HipEngine:
         return int(n.value), float(ms.value)
 
     def get_kernel_time_series(self):
-        """(start_ms, duration_ms) arrays of the brackets the last get_kernel_time() summed up: one per demcz_run call."""
+        """(start_ms, duration_ms) arrays of the brackets the last get_kernel_time() summed up, one entry per autostop slab: a
+        bracket over k slabs that run_checked made one demcz_run call of comes back as k equal shares (means, not events)."""
         n = C.c_int32(0)
         self._chk(self._L.demcz_get_kernel_time_series(self._h, 0, None, None, C.byref(n)))
         st, du = np.zeros(n.value), np.zeros(n.value)

@@ -473,7 +473,10 @@ int32_t demcz_get_kernel_time(demcz_handle* h, int64_t* launches, double* millis
 /* The brackets the last demcz_get_kernel_time call summed up, one per demcz_run call (inside demcz_run_checked: one per slab):
  * start_ms[i] = start of bracket i on the device clock, relative to the first bracket's start; duration_ms[i] = its length.
  * start_ms[i+1] - start_ms[i] is therefore the wall time of step i as the GPU saw it, gaps between launches included -- what
- * bench.py takes its median step time from.  At most `cap` entries are written; *n = entries available. */
+ * bench.py takes its median step time from.  At most `cap` entries are written; *n = entries available.
+ * demcz_run_checked with threshold <= 0 may run k consecutive slabs as one demcz_run call with one bracket: that bracket is
+ * returned as k entries, start + i * duration / k and duration / k -- means over the launch, not events.  demcz_get_kernel_time
+ * keeps returning the true launch count and the summed bracket time. */
 int32_t demcz_get_kernel_time_series(demcz_handle* h, int32_t cap, double* start_ms, double* duration_ms, int32_t* n);
 
 /* Device self-test of the draw pipeline: for Philox block blk0+i of the
