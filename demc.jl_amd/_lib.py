@@ -52,6 +52,7 @@ SYMBOLS = [
     "demcz_autocov_sums", "demcz_autocov_sums_array", "demcz_ess_from_sums", "demcz_ess", "demcz_ess_array",
     "demcz_quantile_plan", "demcz_select_counts", "demcz_select_step", "demcz_quantile_finish", "demcz_quantiles",
     "demcz_quantiles_array", "demcz_best", "demcz_best_array",
+    "demcz_derive_check", "demcz_derive", "demcz_derive_array",
 ]
 
 
@@ -208,7 +209,11 @@ def load():
     L.demcz_program_check.argtypes = [C.c_int32, C.c_char_p, C.c_char_p]
     L.demcz_program_check_layout.argtypes = [C.c_int32, C.c_char_p, C.c_char_p, C.c_int32]
     L.demcz_set_program.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, _dp, C.c_int64]
-    L.demcz_get_archive_pinned.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), _lp]
+    L.demcz_derive_check.argtypes = [C.c_int32, C.c_int32, C.c_char_p, C.c_char_p]
+    L.demcz_derive.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_char_p, C.c_char_p, _dp, C.c_int64, C.POINTER(C.c_void_p)]
+    L.demcz_derive_array.argtypes = [C.c_int32, _dp, _dp, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_char_p, C.c_char_p, _dp,
+                                     C.c_int64, C.POINTER(C.c_void_p)]
+    L.demcz_get_archive_pinned.argtypes =[C.c_void_p, C.POINTER(C.c_void_p), _lp]
     L.demcz_get_kernel_time_series.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _ip]
     L.demcz_set_comm_timeout.argtypes = [C.c_void_p, C.c_int64]
     L.demcz_debug_stall_exchange.argtypes = [C.c_void_p, C.c_int32]
@@ -220,6 +225,15 @@ def load():
             fn.restype = C.c_int32
     _LIB = L
     return L
+
+
+def derive_launch_constants() -> tuple:
+    """(threads per workgroup, workgroups at the most) of a derive_kernel launch, read from the kernel's own header
+    (csrc/demcz_kernels_derive.h: the constants the library is built with).  A window of more draws than their product is strided
+    over by the same launch."""
+    import re
+    text = (PKG_DIR / "csrc" / "demcz_kernels_derive.h").read_text()
+    return tuple(int(re.search(rf"constexpr int {name} = (\d+);", text).group(1)) for name in ("DERIVE_THREADS", "DERIVE_MAX_WG"))
 
 
 def f64(a, order="C"):

@@ -416,6 +416,10 @@ struct demcz_handle {
     // created with DEMCZ_LAYOUT_PROGRAM_WAVE: lanes == DEMCZ_LAYOUT_SPLIT, split_kind == SPLIT_WAVE, and the consumer is the program's own
     // window_kernel_ps / _pw<TARGET_PROGRAM, d, LIVE, TEMPER> (prog.wave); records, producer, LIVE machinery: the library's
     bool prog_wave = false;
+    // a derived history (demcz_derive): N x cfg.d x cfg.Gcap values in dchain, the program's data in d_design, a stream, the
+    // staging buffer and nothing else -- no state, no archive, no log_obj.  The statistics over dchain and demcz_derive itself
+    // take it; every other entry point refuses it (NOT_DERIVED) before it looks at a buffer that is not there.
+    bool derived = false;
 };
 
 #define HIPCHK(h, expr)                                                                          \
@@ -447,6 +451,20 @@ static int32_t fail(demcz_handle* h, int32_t code, const std::string& msg)
     if (h) h->err = msg; else g_create_error = msg;
     return code;
 }
+
+static int32_t refuse_derived(const demcz_handle* h, const char* who)
+{
+    if (!h || !h->derived) return DEMCZ_OK;
+    return fail(const_cast<demcz_handle*>(h), DEMCZ_ERR_STATE,
+                std::string(who) + ": the handle is a derived history (demcz_derive): it takes the statistics over its values, demcz_get_history "
+                                   "without log_obj, demcz_derive, demcz_synchronize and demcz_destroy, and nothing else");
+}
+// first statement of every entry point a derived history does not take (a NULL handle is left to the function's own check)
+#define NOT_DERIVED(h)                                                                           \
+    do {                                                                                         \
+        int32_t rd_ = refuse_derived((h), __func__);                                             \
+        if (rd_) return rd_;                                                                     \
+    } while (0)
 
 // ---- comm failure path ---------------------------------------------------------------------------------------------
 // A sharded handle's streams carry RCCL kernels that wait for PEERS: a dead or wedged peer would make every blocking
@@ -1225,6 +1243,7 @@ static int32_t launch_logp(demcz_handle* h, const double* X, int64_t ldX, int64_
 extern "C" int32_t demcz_set_state(demcz_handle* h, const double* X, const double* logp, const double* Z,
                                    int64_t ldZ, int64_t M0)
 {
+    NOT_DERIVED(h);
     if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
     DEADCHK(h);
     if (!X || !Z) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_state: X and Z are required");
@@ -1284,6 +1303,7 @@ extern "C" int32_t demcz_set_state(demcz_handle* h, const double* X, const doubl
 
 extern "C" int32_t demcz_get_state(demcz_handle* h, double* X, double* logp, double* Z, int64_t ldZ, int64_t* M)
 {
+    NOT_DERIVED(h);
     if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
     DEADCHK(h);
     if (!h->has_state) return fail(h, DEMCZ_ERR_STATE, "demcz_get_state: no state set");
@@ -1317,6 +1337,7 @@ extern "C" int32_t demcz_get_state(demcz_handle* h, double* X, double* logp, dou
 
 extern "C" int32_t demcz_get_archive_pinned(demcz_handle* h, double** Z, int64_t* M)
 {
+    NOT_DERIVED(h);
     if (!h || !Z || !M) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (!h->has_state) return fail(h, DEMCZ_ERR_STATE, "demcz_get_archive_pinned: no state set");
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
@@ -1346,6 +1367,7 @@ extern "C" int32_t demcz_get_archive_pinned(demcz_handle* h, double** Z, int64_t
 
 extern "C" int32_t demcz_set_history_origin(demcz_handle* h, int64_t g0)
 {
+    NOT_DERIVED(h);
     if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (g0 < 0) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_history_origin: g0 >= 0");
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
@@ -1385,6 +1407,7 @@ extern "C" int32_t demcz_program_check_layout(int32_t d, const char* source, con
 
 extern "C" int32_t demcz_set_program(demcz_handle* h, const char* source, const char* options, const double* data, int64_t ndata)
 {
+    NOT_DERIVED(h);
     if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
     DEADCHK(h);
     if (h->cfg.target_kind != DEMCZ_TARGET_PROGRAM)
@@ -2574,6 +2597,7 @@ static int32_t stream_history(demcz_handle* h, int64_t g_from, int64_t g_to)
 
 extern "C" int32_t demcz_history_stream(demcz_handle* h, int32_t enabled)
 {
+    NOT_DERIVED(h);
     if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
     DEADCHK(h);
     if (h->cfg.Gcap <= 0) return fail(h, DEMCZ_ERR_STATE, "demcz_history_stream: handle keeps no history (Gcap = 0)");
@@ -2590,6 +2614,7 @@ extern "C" int32_t demcz_history_stream(demcz_handle* h, int32_t enabled)
 
 extern "C" int32_t demcz_get_history_view(demcz_handle* h, int64_t g_from, int64_t g_to, double** chain, double** log_obj)
 {
+    NOT_DERIVED(h);
     if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
     int32_t rc = check_hist_range(h, g_from, g_to, "demcz_get_history_view");
     if (rc) return rc;
@@ -2607,6 +2632,7 @@ extern "C" int32_t demcz_get_history_view(demcz_handle* h, int64_t g_from, int64
 
 extern "C" int32_t demcz_detach_history(demcz_handle* h, void** chain_base, void** logobj_base)
 {
+    NOT_DERIVED(h);
     if (!h || !chain_base || !logobj_base) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (!h->hs_chain) return fail(h, DEMCZ_ERR_STATE, "demcz_detach_history: no streamed history on this handle");
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
@@ -2633,6 +2659,7 @@ extern "C" int32_t demcz_pool_trim(int64_t* device_bytes, int64_t* pinned_bytes)
 
 extern "C" int32_t demcz_run(demcz_handle* h, int64_t g_from, int64_t g_to, double gamma, const double* temperature)
 {
+    NOT_DERIVED(h);
     if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
     DEADCHK(h);
     if (!h->has_state) return fail(h, DEMCZ_ERR_STATE, "demcz_run: call demcz_set_state first");
@@ -2979,6 +3006,7 @@ extern "C" int32_t demcz_get_history(demcz_handle* h, int64_t g_from, int64_t g_
 {
     if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
     DEADCHK(h);
+    if (log_obj) NOT_DERIVED(h);               // (a derived history has values only)
     int32_t rc = check_hist_range(h, g_from, g_to, "demcz_get_history");
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
@@ -2998,6 +3026,7 @@ extern "C" int32_t demcz_get_history(demcz_handle* h, int64_t g_from, int64_t g_
 
 extern "C" int32_t demcz_get_changed(demcz_handle* h, int64_t g_from, int64_t g_to, int64_t* changed)
 {
+    NOT_DERIVED(h);
     if (!h || !changed) return DEMCZ_ERR_INVALID_ARGUMENT;
     int32_t rc = check_hist_range(h, g_from, g_to, "demcz_get_changed");
     if (rc) return rc;
@@ -3047,6 +3076,7 @@ __global__ void __launch_bounds__(256) sum_counts_kernel(const unsigned int* acc
 
 extern "C" int32_t demcz_get_changed_total(demcz_handle* h, int64_t g_from, int64_t g_to, int64_t* total, int32_t* from_ballots)
 {
+    NOT_DERIVED(h);
     if (!h || !total || g_from < 1 || g_to < g_from) return DEMCZ_ERR_INVALID_ARGUMENT;
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
     int32_t rc = live_verify(h);
@@ -3588,6 +3618,7 @@ extern "C" int32_t demcz_quantiles(demcz_handle* h, int64_t g_from, int64_t g_to
 extern "C" int32_t demcz_best(demcz_handle* h, int64_t g_from, int64_t g_to, double* bestval, int64_t* chain, int64_t* generation,
                               double* bestpar)
 {
+    NOT_DERIVED(h);
     if (!h || !bestval || !chain || !generation) return DEMCZ_ERR_INVALID_ARGUMENT;
     int32_t rc = check_hist_range(h, g_from, g_to, "demcz_best");
     if (rc) return rc;
@@ -3628,6 +3659,7 @@ extern "C" int32_t demcz_best(demcz_handle* h, int64_t g_from, int64_t g_to, dou
 
 extern "C" int32_t demcz_accept_ratio(demcz_handle* h, int64_t g_from, int64_t g_to, double* ratio)
 {
+    NOT_DERIVED(h);
     if (!h || !ratio) return DEMCZ_ERR_INVALID_ARGUMENT;
     int32_t rc = check_hist_range(h, g_from, g_to, "demcz_accept_ratio");
     if (rc) return rc;
@@ -3782,6 +3814,7 @@ __global__ void end_generation_kernel(int64_t N, int d, const double* Xcur, cons
 
 extern "C" int32_t demcz_propose(demcz_handle* h, int64_t g, int32_t ib, double gamma, double* Xprop)
 {
+    NOT_DERIVED(h);
     if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (h->cfg.target_kind != DEMCZ_TARGET_HOST_CALLBACK) return fail(h, DEMCZ_ERR_STATE, "demcz_propose: handle was not created with DEMCZ_TARGET_HOST_CALLBACK");
     if (!h->has_state) return fail(h, DEMCZ_ERR_STATE, "demcz_propose: call demcz_set_state first");
@@ -3835,6 +3868,7 @@ extern "C" int32_t demcz_propose(demcz_handle* h, int64_t g, int32_t ib, double 
 // demcz_handle::hc_X).  The buffers belong to the handle and live as long as it does.
 extern "C" int32_t demcz_closure_buffers(demcz_handle* h, double** Xprop, double** logp)
 {
+    NOT_DERIVED(h);
     if (!h || !Xprop || !logp) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (h->cfg.target_kind != DEMCZ_TARGET_HOST_CALLBACK) return fail(h, DEMCZ_ERR_STATE, "demcz_closure_buffers: handle was not created with DEMCZ_TARGET_HOST_CALLBACK");
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
@@ -3862,6 +3896,7 @@ extern "C" int32_t demcz_closure_buffers(demcz_handle* h, double** Xprop, double
 
 extern "C" int32_t demcz_accept_commit(demcz_handle* h, const double* logp_prop, const double* temperature)
 {
+    NOT_DERIVED(h);
     if (!h || (!logp_prop && !h->hc_lp)) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (!h->proposal_pending) return fail(h, DEMCZ_ERR_STATE, "demcz_accept_commit: no pending proposal");
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
@@ -3891,6 +3926,7 @@ extern "C" int32_t demcz_accept_commit(demcz_handle* h, const double* logp_prop,
 
 extern "C" int32_t demcz_end_generation(demcz_handle* h, int64_t g)
 {
+    NOT_DERIVED(h);
     if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (h->cfg.target_kind != DEMCZ_TARGET_HOST_CALLBACK) return fail(h, DEMCZ_ERR_STATE, "demcz_end_generation: host-callback handles only");
     if (h->proposal_pending || !h->gen_open) return fail(h, DEMCZ_ERR_STATE, "demcz_end_generation: no open generation or uncommitted proposal");
@@ -3927,6 +3963,7 @@ extern "C" int32_t demcz_comm_unique_id(void* unique_id_128B)
 
 extern "C" int32_t demcz_comm_init(demcz_handle* h, const void* unique_id_128B, int32_t nranks, int32_t rank)
 {
+    NOT_DERIVED(h);
     if (!h || !unique_id_128B || nranks < 1 || rank < 0 || rank >= nranks) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (h->comm) return fail(h, DEMCZ_ERR_STATE, "demcz_comm_init: communicator already initialised");
     if (h->prog_wave)
@@ -3956,6 +3993,7 @@ extern "C" int32_t demcz_peer_group(demcz_handle** handles, int32_t R)
     for (int r = 0; r < R; ++r) {
         demcz_handle* m = handles[r];
         if (!m) return DEMCZ_ERR_INVALID_ARGUMENT;
+        NOT_DERIVED(m);
         for (int q = 0; q < r; ++q) if (handles[q] == m) return fail(m, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_peer_group: a handle appears twice");
         if (m->comm || m->peer_mode != 0) return fail(m, DEMCZ_ERR_STATE, "demcz_peer_group: handle is already sharded");
         if (m->prog_wave)
@@ -4034,6 +4072,7 @@ extern "C" int32_t demcz_peer_group(demcz_handle** handles, int32_t R)
 
 extern "C" int32_t demcz_get_peer_status(const demcz_handle* h, int32_t* mode, int32_t* peers)
 {
+    NOT_DERIVED(h);
     if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (mode) *mode = h->peer_mode;
     if (peers) *peers = h->n_peers;
@@ -4209,6 +4248,7 @@ static int32_t peer_setup_ipc(demcz_handle* h)
 // that saw it (DEMCZ_ERR_STATE), not an automatic redo -- the ranks have no way here to agree on one.
 extern "C" int32_t demcz_peer_export(demcz_handle* h, int32_t nranks, int32_t rank, void* handle_64B)
 {
+    NOT_DERIVED(h);
     static_assert(sizeof(hipIpcMemHandle_t) == 64, "IPC handle size");
     if (!h || !handle_64B || nranks < 2 || nranks > DEMCZ_MAX_PEERS + 1 || rank < 0 || rank >= nranks) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (h->comm || h->peer_mode != 0) return fail(h, DEMCZ_ERR_STATE, "demcz_peer_export: handle is already sharded");
@@ -4229,6 +4269,7 @@ extern "C" int32_t demcz_peer_export(demcz_handle* h, int32_t nranks, int32_t ra
 
 extern "C" int32_t demcz_peer_attach(demcz_handle* h, const void* handles_64B_each)
 {
+    NOT_DERIVED(h);
     if (!h || !handles_64B_each) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (!h->archive_fine || h->peer_mode != 0 || h->nranks < 2) return fail(h, DEMCZ_ERR_STATE, "demcz_peer_attach: call demcz_peer_export first");
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
@@ -4246,6 +4287,7 @@ extern "C" int32_t demcz_peer_attach(demcz_handle* h, const void* handles_64B_ea
 // further generations), the host makes them meet once more, and only then does any rank call demcz_destroy.
 extern "C" int32_t demcz_peer_detach(demcz_handle* h)
 {
+    NOT_DERIVED(h);
     if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (h->peer_mode != 3) return fail(h, DEMCZ_ERR_STATE, "demcz_peer_detach: host-mediated IPC peers only (demcz_peer_export / demcz_peer_attach)");
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
@@ -4261,6 +4303,7 @@ extern "C" int32_t demcz_peer_detach(demcz_handle* h)
 
 extern "C" int32_t demcz_get_peer_ping(const demcz_handle* h, int32_t* ok, double* wait_us)
 {
+    NOT_DERIVED(h);
     if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (ok) *ok = h->ping_ok;
     if (wait_us) *wait_us = h->ping_wait_us;
@@ -4269,6 +4312,7 @@ extern "C" int32_t demcz_get_peer_ping(const demcz_handle* h, int32_t* ok, doubl
 
 extern "C" int32_t demcz_set_comm_timeout(demcz_handle* h, int64_t milliseconds)
 {
+    NOT_DERIVED(h);
     if (!h || milliseconds < 0) return DEMCZ_ERR_INVALID_ARGUMENT;
     h->comm_timeout_ms = milliseconds;
     return DEMCZ_OK;
@@ -4276,6 +4320,7 @@ extern "C" int32_t demcz_set_comm_timeout(demcz_handle* h, int64_t milliseconds)
 
 extern "C" int32_t demcz_debug_stall_exchange(demcz_handle* h, int32_t milliseconds)
 {
+    NOT_DERIVED(h);
     if (!h || milliseconds < 0 || milliseconds > 10000) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (!h->comm) return fail(h, DEMCZ_ERR_STATE, "demcz_debug_stall_exchange: not a sharded handle (demcz_comm_init)");
     h->stall_next_ms = milliseconds;
@@ -4284,6 +4329,7 @@ extern "C" int32_t demcz_debug_stall_exchange(demcz_handle* h, int32_t milliseco
 
 extern "C" int32_t demcz_export_current_device(demcz_handle* h, double* X_device)
 {
+    NOT_DERIVED(h);
     if (!h || !X_device) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (!h->has_state) return fail(h, DEMCZ_ERR_STATE, "demcz_export_current_device: no state");
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
@@ -4293,6 +4339,7 @@ extern "C" int32_t demcz_export_current_device(demcz_handle* h, double* X_device
 
 extern "C" int32_t demcz_append_rows_device(demcz_handle* h, const double* rows_device, int64_t nrows, int64_t ldrows)
 {
+    NOT_DERIVED(h);
     if (!h || !rows_device || nrows < 1 || ldrows < nrows) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (!h->has_state) return fail(h, DEMCZ_ERR_STATE, "demcz_append_rows_device: no state");
     if (h->M_app + nrows > h->cfg.Mcap) return fail(h, DEMCZ_ERR_CAPACITY, "demcz_append_rows_device: Z capacity exceeded");
@@ -4309,6 +4356,7 @@ extern "C" int32_t demcz_append_rows_device(demcz_handle* h, const double* rows_
 
 extern "C" int32_t demcz_append_rows(demcz_handle* h, const double* rows, int64_t nrows, int64_t ldrows)
 {
+    NOT_DERIVED(h);
     if (!h || !rows || nrows < 1 || ldrows < nrows) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (!h->has_state) return fail(h, DEMCZ_ERR_STATE, "demcz_append_rows: no state");
     if (h->M_app + nrows > h->cfg.Mcap) return fail(h, DEMCZ_ERR_CAPACITY, "demcz_append_rows: Z capacity exceeded");
@@ -4330,6 +4378,7 @@ extern "C" int32_t demcz_append_rows(demcz_handle* h, const double* rows, int64_
 
 extern "C" int32_t demcz_set_external_append(demcz_handle* h, int32_t enabled)
 {
+    NOT_DERIVED(h);
     if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (!h->live_log.empty()) { int32_t rcv = live_verify(h); if (rcv) return rcv; }
     h->external_append = enabled != 0;
@@ -4338,6 +4387,7 @@ extern "C" int32_t demcz_set_external_append(demcz_handle* h, int32_t enabled)
 
 extern "C" int32_t demcz_set_append_lag(demcz_handle* h, int32_t batches)
 {
+    NOT_DERIVED(h);
     if (!h || batches < 0 || batches > 64) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (!h->live_log.empty()) { int32_t rcv = live_verify(h); if (rcv) return rcv; }
     if (h->M_app != h->M || !h->pending.empty()) return fail(h, DEMCZ_ERR_STATE, "demcz_set_append_lag: rows are still pending");
@@ -4372,6 +4422,7 @@ extern "C" int32_t demcz_set_append_lag(demcz_handle* h, int32_t batches)
 
 extern "C" int32_t demcz_set_rng_offset(demcz_handle* h, int64_t generations)
 {
+    NOT_DERIVED(h);
     if (!h || generations < 0) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (!h->live_log.empty()) { int32_t rcv = live_verify(h); if (rcv) return rcv; }
     h->rng_offset = generations;
@@ -4487,8 +4538,109 @@ extern "C" int32_t demcz_mean_cov_array(int32_t device_id, const double* chain, 
     return diag_fail(s, demcz_mean_cov(&s.h, 1, G, mean, cov));
 }
 
+// ---- derived quantities: user functions of the draws (demcz_kernels_derive.h) -----------------------------------------------
+extern "C" int32_t demcz_derive_check(int32_t d, int32_t m, const char* source, const char* options)
+{
+    std::shared_ptr<const demcz_prog::Code> code;
+    std::string err;
+    if (demcz_prog::get_code(d, source, options, demcz_prog::UNIT_DERIVE, code, err, m) != 0) return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, err);
+    return DEMCZ_OK;
+}
+
+namespace {
+// The derived history of N x m x w values on `device`, generations g0 + 1 .. g0 + w, with `data` copied into memory it owns:
+// the ScratchHandle shape on the heap.  On failure everything made so far is freed, nullptr is returned and `why` says what failed.
+demcz_handle* derived_create(int device, int64_t N, int m, int64_t w, int64_t g0, const double* data, int64_t ndata, std::string& why)
+{
+    demcz_handle* dh = new demcz_handle;
+    dh->cfg.N = N; dh->cfg.d = m; dh->cfg.Gcap = w; dh->cfg.device_id = device; dh->cfg.nobs = ndata;
+    dh->g0 = g0; dh->nranks = 1; dh->derived = true;
+    dh->stage_cap = 4096 + (int64_t)m * (m + 1);
+    const char* what = "hipSetDevice";
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) { what = "the derived history's stream"; e = stream_acquire(device, &dh->stream); dh->own_stream = e == hipSuccess; }
+    if (e == hipSuccess) { what = "the derived history (N x m x w doubles)"; e = dev_malloc(device, (void**)&dh->dchain, (size_t)N * m * w * sizeof(double)); }
+    if (e == hipSuccess) { what = "the program's data"; e = dev_alloc_copy(&dh->d_design, data, (size_t)ndata, dh->stream, device); }
+    if (e == hipSuccess) { what = "the staging buffer"; e = host_malloc((void**)&dh->d_stage, (size_t)dh->stage_cap * sizeof(double)); }
+    if (e == hipSuccess) { what = "the upload of the program's data"; e = hipStreamSynchronize(dh->stream); }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        why = std::string("demcz_derive: ") + what + ": " + hipGetErrorString(e);
+        free_all(dh);
+        delete dh;
+        return nullptr;
+    }
+    return dh;
+}
+
+// demcz_derive on a source that holds an N x d x Gcap history (a sampling handle, a derived history, a ScratchHandle)
+int32_t derive_from(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t m, const char* source, const char* options,
+                    const double* data, int64_t ndata, demcz_handle** derived)
+{
+    int32_t rc = check_hist_range(h, g_from, g_to, "demcz_derive");
+    if (rc) return rc;
+    if (ndata < 0 || (ndata > 0 && !data)) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_derive: need ndata >= 0 and data for ndata > 0");
+    HIPCHK(h, hipSetDevice(h->cfg.device_id));
+    rc = live_verify(h);
+    if (rc) return rc;
+    std::shared_ptr<const demcz_prog::Code> code;
+    std::string err;
+    if (demcz_prog::get_code(h->cfg.d, source, options, demcz_prog::UNIT_DERIVE, code, err, m) != 0) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, err);
+    demcz_prog::Module mod;
+    if (demcz_prog::get_module(code, h->cfg.device_id, mod, err) != 0) return fail(h, DEMCZ_ERR_HIP, err);
+    rc = quiesce_all(h);                        // (a sharded handle: the allocations below synchronise the device)
+    if (rc) return rc;
+    int64_t N = h->cfg.N, w = g_to - g_from + 1, s0 = g_from - h->g0 - 1, total = N * w;
+    demcz_handle* dh = derived_create(h->cfg.device_id, N, m, w, g_from - 1, data, ndata, err);
+    if (!dh) return fail(h, DEMCZ_ERR_HIP, err);
+    const double* chain = h->dchain;
+    const double* logobj = h->dlogobj;          // (nullptr on a derived history and on arrays given without log_obj: logp is NaN)
+    const double* ddata = ndata > 0 ? dh->d_design : nullptr;
+    double* out = dh->dchain;
+    void* args[] = {&chain, &logobj, &N, &s0, &total, &ddata, &ndata, &out};
+    const unsigned blocks = (unsigned)std::min<int64_t>((total + DERIVE_THREADS - 1) / DERIVE_THREADS, DERIVE_MAX_WG);
+    // on the source's stream: behind the window launches that write the history, and behind whatever else is queued there
+    hipError_t e = hipModuleLaunchKernel(mod.derive, blocks, 1, 1, DERIVE_THREADS, 1, 1, 0, h->stream, args, nullptr);
+    if (e != hipSuccess) h->err = std::string("demcz_derive: launching derive_kernel: ") + hipGetErrorString(e);
+    rc = (e != hipSuccess) ? DEMCZ_ERR_HIP : sync_stream(h, h->stream, "demcz_derive");
+    if (rc) {
+        if (rc == DEMCZ_ERR_HIP) (void)hipDeviceSynchronize();      // (the kernel may still be writing what is about to be freed)
+        free_all(dh);
+        delete dh;
+        return rc;
+    }
+    *derived = dh;
+    return DEMCZ_OK;
+}
+}  // namespace
+
+extern "C" int32_t demcz_derive(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t m, const char* source, const char* options,
+                                const double* data, int64_t ndata, demcz_handle** derived)
+{
+    if (!h || !derived) return DEMCZ_ERR_INVALID_ARGUMENT;
+    *derived = nullptr;
+    DEADCHK(h);
+    return derive_from(h, g_from, g_to, m, source, options, data, ndata, derived);
+}
+
+extern "C" int32_t demcz_derive_array(int32_t device_id, const double* chain, const double* log_obj, int64_t N, int32_t d, int64_t G,
+                                      int32_t m, const char* source, const char* options, const double* data, int64_t ndata,
+                                      demcz_handle** derived)
+{
+    if (!chain || !derived) return DEMCZ_ERR_INVALID_ARGUMENT;
+    *derived = nullptr;
+    // (compiled before anything is uploaded: a program that does not compile costs no copy)
+    int32_t rc = demcz_derive_check(d, m, source, options);
+    if (rc) return rc;
+    ScratchHandle s;                            // (the uploads: freed when this call returns, only the derived history stays)
+    rc = s.open(device_id, N, d, G, chain, log_obj);
+    if (rc) return diag_fail(s, rc);
+    return diag_fail(s, derive_from(&s.h, 1, G, m, source, options, data, ndata, derived));
+}
+
 extern "C" int32_t demcz_get_info(const demcz_handle* h, int64_t* M, int64_t* launches_window, int32_t* lanes_per_chain)
 {
+    NOT_DERIVED(h);
     if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (M) *M = h->M_app;
     if (launches_window) *launches_window = h->launches;
@@ -4526,6 +4678,7 @@ extern "C" int32_t demcz_selftest_draws(int32_t device_id, uint64_t seed, uint64
 // Diagnostic build only: the stamps of the last split-layout launch (16 per workgroup, first `n_wg` workgroups).
 extern "C" int32_t demcz_debug_read_stamps(demcz_handle* h, unsigned long long* out, int64_t n_wg)
 {
+    NOT_DERIVED(h);
     if (!h || !out || n_wg < 0 || n_wg > DEMCZ_STAMP_WGS || !h->d_stamps) return DEMCZ_ERR_INVALID_ARGUMENT;
     SYNCCHK(h, h->stream);
     HIPCHK(h, hipMemcpy(out, h->d_stamps, (size_t)n_wg * 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
@@ -4704,6 +4857,7 @@ extern "C" int32_t demcz_run_checked(demcz_handle* h, int64_t g_from, int64_t g_
                                      int64_t every, double threshold, int64_t* g_stop, int32_t* n_checks,
                                      double* rhat_max, int32_t n_max, double* rhat_last)
 {
+    NOT_DERIVED(h);
     if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
     DEADCHK(h);
     if (every < 4 || g_from < 1 || g_to < g_from) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_run_checked: need every >= 4 and 1 <= g_from <= g_to");
@@ -4746,6 +4900,7 @@ extern "C" int32_t demcz_run_checked(demcz_handle* h, int64_t g_from, int64_t g_
 // ---- diagnostic entry points (not part of the contract of SURVEY.md 8(b); benchmarks and tests only) ----------
 extern "C" int32_t demcz_set_live_spin_limit(demcz_handle* h, int32_t polls)
 {
+    NOT_DERIVED(h);
     if (!h || polls < 0) return DEMCZ_ERR_INVALID_ARGUMENT;
     h->live_spin_limit = (unsigned int)polls;
     return DEMCZ_OK;
@@ -4753,6 +4908,7 @@ extern "C" int32_t demcz_set_live_spin_limit(demcz_handle* h, int32_t polls)
 
 extern "C" int32_t demcz_set_live_rearms(demcz_handle* h, int32_t n)
 {
+    NOT_DERIVED(h);
     if (!h || n < 0) return DEMCZ_ERR_INVALID_ARGUMENT;
     h->live_rearms_left = n;
     if (h->peer_mode == 1 && h->group) {
@@ -4765,6 +4921,7 @@ extern "C" int32_t demcz_set_live_rearms(demcz_handle* h, int32_t n)
 
 extern "C" int32_t demcz_get_live_rearms(const demcz_handle* h, int32_t* rearms, int32_t* left)
 {
+    NOT_DERIVED(h);
     if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (rearms) *rearms = h->live_rearms;
     if (left) *left = h->live_rearms_left;
@@ -4773,6 +4930,7 @@ extern "C" int32_t demcz_get_live_rearms(const demcz_handle* h, int32_t* rearms,
 
 extern "C" int32_t demcz_debug_set_live_fault(demcz_handle* h, int32_t polls, int64_t g_from)
 {
+    NOT_DERIVED(h);
     if (!h || polls < -1 || g_from < 0) return DEMCZ_ERR_INVALID_ARGUMENT;
     h->live_fault_polls = polls;
     h->live_fault_g = g_from;
@@ -4781,6 +4939,7 @@ extern "C" int32_t demcz_debug_set_live_fault(demcz_handle* h, int32_t polls, in
 
 extern "C" int32_t demcz_debug_kernel_counts(const demcz_handle* h, int64_t* counts)
 {
+    NOT_DERIVED(h);
     if (!h || !counts) return DEMCZ_ERR_INVALID_ARGUMENT;
     const bool wave = h->lanes == DEMCZ_LAYOUT_SPLIT && h->split_kind == SPLIT_WAVE;
     counts[0] = h->kernel_counts[0];
@@ -4791,6 +4950,7 @@ extern "C" int32_t demcz_debug_kernel_counts(const demcz_handle* h, int64_t* cou
 
 extern "C" int32_t demcz_debug_kernel_name(const demcz_handle* h, char* buf, int32_t cap)
 {
+    NOT_DERIVED(h);
     if (!h || !buf || cap < 1) return DEMCZ_ERR_INVALID_ARGUMENT;
     const int d = h->cfg.d;
     const char* tg = h->cfg.target_kind == DEMCZ_TARGET_MVNORMAL ? "MVNORMAL" : h->cfg.target_kind == DEMCZ_TARGET_ISO_QUAD ? "ISO_QUAD"
@@ -4835,6 +4995,7 @@ extern "C" int32_t demcz_debug_kernel_name(const demcz_handle* h, char* buf, int
 
 extern "C" int32_t demcz_get_live_status(const demcz_handle* h, int32_t* live_enabled, int32_t* redos)
 {
+    NOT_DERIVED(h);
     if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (live_enabled) *live_enabled = (h->lanes == DEMCZ_LAYOUT_SPLIT && !h->no_live && h->live_claimed) ? 1 : 0;
     if (redos) *redos = h->live_redos;
@@ -4846,6 +5007,7 @@ extern "C" int32_t demcz_get_live_status(const demcz_handle* h, int32_t* live_en
 // [R][cnt][d][n_loc] with n_loc = this handle's N: lets a one-GPU box check the index arithmetic for R > 1.
 extern "C" int32_t demcz_debug_append_slab(demcz_handle* h, const double* slab, int32_t R, int32_t cnt, int32_t batched)
 {
+    NOT_DERIVED(h);
     if (!h || !slab || R < 1 || cnt < 1 || (!batched && cnt != 1)) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (!h->has_state) return fail(h, DEMCZ_ERR_STATE, "demcz_debug_append_slab: no state");
     if (h->lag != 0 || !h->pending.empty()) return fail(h, DEMCZ_ERR_STATE, "demcz_debug_append_slab: rows are pending");
@@ -4873,6 +5035,7 @@ extern "C" int32_t demcz_debug_append_slab(demcz_handle* h, const double* slab, 
 
 extern "C" int32_t demcz_set_kernel_timing(demcz_handle* h, int32_t enabled)
 {
+    NOT_DERIVED(h);
     if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
     h->timing = enabled != 0;
     return DEMCZ_OK;
@@ -4880,6 +5043,7 @@ extern "C" int32_t demcz_set_kernel_timing(demcz_handle* h, int32_t enabled)
 
 extern "C" int32_t demcz_get_kernel_time(demcz_handle* h, int64_t* launches, double* milliseconds)
 {
+    NOT_DERIVED(h);
     if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
     SYNCCHK(h, h->stream);
@@ -4909,6 +5073,7 @@ extern "C" int32_t demcz_get_kernel_time(demcz_handle* h, int64_t* launches, dou
 
 extern "C" int32_t demcz_get_kernel_time_series(demcz_handle* h, int32_t cap, double* start_ms, double* duration_ms, int32_t* n)
 {
+    NOT_DERIVED(h);
     if (!h || cap < 0 || !n) return DEMCZ_ERR_INVALID_ARGUMENT;
     const int32_t m = (int32_t)std::min<size_t>(h->series_start_ms.size(), (size_t)cap);
     for (int32_t i = 0; i < m; ++i) {

@@ -1,8 +1,11 @@
-// demcz_program.h -- host-side interface of demcz_program.hip (program targets, DEMCZ_TARGET_PROGRAM) for demcz_capi.hip.
+// demcz_program.h -- host-side interface of demcz_program.hip (program targets, DEMCZ_TARGET_PROGRAM, and derive programs,
+// demcz_derive) for demcz_capi.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "demcz_kernels_derive.h"      // (the launch constants; the kernel itself is compiled at run time only)
 
 #include <memory>
 #include <string>
@@ -11,10 +14,13 @@
 namespace demcz_prog {
 
 constexpr int MAX_PROGRAM_D = 32;
+constexpr int MAX_DERIVE_M = demcz::DERIVE_MAX_M;
 
 // The two units a program can be compiled into (demcz_program.hip, compose): the one-lane window kernel, or the wave-per-chain
 // consumers of the split layout (DEMCZ_LAYOUT_PROGRAM_WAVE: window_kernel_ps for d = 2..5, window_kernel_pw for d = 6..32).
-enum { UNIT_ONE_LANE = 0, UNIT_WAVE = 1 };
+// A derive program (demcz_derive, include/demcz.h) has a unit of its own: the user's demcz_derive and derive_kernel of
+// demcz_kernels_derive.h, nothing else.
+enum { UNIT_ONE_LANE = 0, UNIT_WAVE = 1, UNIT_DERIVE = 2 };
 constexpr int WAVE_MIN_D = 2;
 
 // One compiled program: the gfx950 code object and the mangled names of its kernels.
@@ -25,7 +31,9 @@ struct Code {
     std::string logp;             // logp_kernel<TARGET_PROGRAM>: the initial log_objcurrent (both units)
     std::string wave[2][2];       // UNIT_WAVE: window_kernel_ps / _pw<TARGET_PROGRAM, d, LIVE, TEMPER>, [LIVE][TEMPER] (the one-lane
                                   // kernels are not in that unit, and these not in the one-lane unit)
+    std::string derive;           // UNIT_DERIVE: derive_kernel, the only kernel of that unit
     int d = 0;
+    int m = 0;                    // UNIT_DERIVE: derived quantities per draw (DEMCZ_M)
     int unit = UNIT_ONE_LANE;
 };
 
@@ -34,13 +42,13 @@ struct Module {
     hipModule_t module = nullptr;
     hipFunction_t window_full = nullptr, window_blocks = nullptr, logp = nullptr;
     hipFunction_t wave[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+    hipFunction_t derive = nullptr;
     std::shared_ptr<const Code> code;
 };
 
 // Compile `source` for dimension d into `unit` (or take it from the process-wide cache, whose key includes the unit).  Needs no
-// device.  Returns 0, or 1 with the compiler log (or what else went wrong) in err.
-int32_t get_code(int d, const char* source, const char* options, int unit, std::shared_ptr<const Code>& out, std::string& err);
-// Load a code object on `device` (or take it from the cache).  Returns 0, or 2 (a HIP error) with the message in err.
+// device.  Returns 0, or 1 with the compiler log (or what else went wrong) in err.  m: UNIT_DERIVE only, 1..32 (part of the key).
+int32_t get_code(int d, const char* source, const char* options, int unit, std::shared_ptr<const Code>& out, std::string& err, int m = 0);// Load a code object on `device` (or take it from the cache).  Returns 0, or 2 (a HIP error) with the message in err.
 int32_t get_module(const std::shared_ptr<const Code>& code, int device, Module& out, std::string& err);
 
 }  // namespace demcz_prog

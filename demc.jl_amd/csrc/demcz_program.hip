@@ -16,9 +16,12 @@
 //     #include "demcz_kernels_pw.h"          (which brings _ps.h, _pc.h with the producer half, _ml.h, _rec.h, demcz_kernels.h)
 //     window_kernel_ps<TARGET_PROGRAM, DEMCZ_D, LIVE, TEMPER> (d <= 5) or window_kernel_pw<TARGET_PROGRAM, DEMCZ_D, LIVE, TEMPER>,
 //     LIVE and TEMPER both ways, and logp_kernel<TARGET_PROGRAM>
-// Compile options: --offload-arch=gfx950 -O3 -ffp-contract=off -I<rocm>/include, the library's own layout switches, then the
-// user's.  Code objects are cached per (composed text, options), loaded modules per (code object, device); both for the life of
-// the process.
+// The derive unit (UNIT_DERIVE, demcz_derive): #define DEMCZ_D <d> / DEMCZ_M <m> / DEMCZ_DERIVE_UNIT, INFINITY and NAN, the
+// user's source (#line 1 "program"), #include "demcz_kernels_derive.h" and nothing else of the library: derive_kernel is its
+// only kernel, and the unit compiles in a fraction of the time a program target takes.
+// Compile options: --offload-arch=gfx950 -O3 -ffp-contract=off -I<rocm>/include, the library's own layout switches (not for
+// the derive unit, which sees no struct of the library's), then the user's.  Code objects are cached per (composed text,
+// options), loaded modules per (code object, device); both for the life of the process.
 #include "demcz_program.h"
 
 #include <hip/hip_runtime.h>
@@ -68,6 +71,10 @@ const char k_ps_h[] = {
 const char k_pw_h[] = {
 #embed "demcz_kernels_pw.h"
     , 0};
+// the derive unit's only header
+const char k_derive_h[] = {
+#embed "demcz_kernels_derive.h"
+    , 0};
 #pragma clang diagnostic pop
 
 // -D switches of the library build that change the layout of WindowParams: the program's kernels must see the same struct
@@ -86,9 +93,16 @@ std::map<std::pair<const demcz_prog::Code*, int>, demcz_prog::Module> g_module_c
 // <math.h>'s INFINITY and NAN, which hipRTC's built-in headers leave undefined: a log-density with bounded support returns -INFINITY
 const char k_math_macros[] = "#ifndef INFINITY\n#define INFINITY (__builtin_inff())\n#endif\n#ifndef NAN\n#define NAN (__builtin_nanf(\"\"))\n#endif\n";
 
-std::string compose(int d, const std::string& source, int unit)
+std::string compose(int d, int m, const std::string& source, int unit)
 {
     std::ostringstream s;
+    if (unit == demcz_prog::UNIT_DERIVE) {
+        s << "#define DEMCZ_D " << d << "\n#define DEMCZ_M " << m << "\n#define DEMCZ_DERIVE_UNIT\n"
+          << "#include <hip/hip_runtime.h>\n#include <stdint.h>\n" << k_math_macros
+          << "#line 1 \"program\"\n" << source << "\n"
+          << "#line 1 \"demcz_unit_derive\"\n#include \"demcz_kernels_derive.h\"\n";
+        return s.str();
+    }
     if (unit == demcz_prog::UNIT_WAVE) {
         const char* kn = (d <= 5) ? "window_kernel_ps" : "window_kernel_pw";
         s << "#define DEMCZ_D " << d << "\n#define DEMCZ_PROGRAM_TARGET\n#define DEMCZ_NO_AUX_KERNELS\n#define ML_LRDPP 0\n#define PW_DDPP 0\n"
@@ -163,23 +177,32 @@ std::string trim_log(std::string log)
     do {                                                                                         \
         hiprtcResult r_ = (expr);                                                                \
         if (r_ != HIPRTC_SUCCESS) {                                                              \
-            err = std::string("program target: " #expr ": ") + hiprtcGetErrorString(r_);         \
+            err = who + #expr ": " + hiprtcGetErrorString(r_);                                   \
             return false;                                                                        \
         }                                                                                        \
     } while (0)
 
-bool compile(const std::string& text, const std::vector<std::string>& opts, int d, int unit, demcz_prog::Code& code, std::string& err)
+// what a failed call says first: which of the two kinds of program it was about
+const char* who_of(int unit) { return unit == demcz_prog::UNIT_DERIVE ? "derive program: " : "program target: "; }
+
+bool compile(const std::string& text, const std::vector<std::string>& opts, int d, int m, int unit, demcz_prog::Code& code, std::string& err)
 {
     hiprtcProgram prog = nullptr;
+    const std::string who = who_of(unit);
     const char* headers[] = {k_device_h, k_kernels_h, k_rec_h, k_ml_h, k_mlb_inc, k_pc_h, k_ps_h, k_pw_h};
     const char* names[] = {"demcz_device.h", "demcz_kernels.h", "demcz_kernels_rec.h", "demcz_kernels_ml.h", "demcz_mlb_dpp_20_5.inc",
                            "demcz_kernels_pc.h", "demcz_kernels_ps.h", "demcz_kernels_pw.h"};
-    const bool wave = unit == demcz_prog::UNIT_WAVE;
-    RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), wave ? "demcz_program_wave_unit.hip" : "demcz_program_unit.hip", wave ? 8 : 2, headers, names));
+    const bool wave = unit == demcz_prog::UNIT_WAVE, derive = unit == demcz_prog::UNIT_DERIVE;
+    const char* derive_headers[] = {k_derive_h};
+    const char* derive_names[] = {"demcz_kernels_derive.h"};
+    if (derive) RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_unit_derive.hip", 1, derive_headers, derive_names));
+    else RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), wave ? "demcz_program_wave_unit.hip" : "demcz_program_unit.hip", wave ? 8 : 2, headers, names));
     struct Guard { hiprtcProgram& p; ~Guard() { if (p) (void)hiprtcDestroyProgram(&p); } } guard{prog};
     const std::string ds = std::to_string(d);
     std::vector<std::string> exprs;
-    if (wave) {
+    if (derive) {
+        exprs = {"&demcz::derive_kernel"};
+    } else if (wave) {
         const std::string kn = (d <= 5) ? "&demcz::window_kernel_ps<4, " : "&demcz::window_kernel_pw<4, ";
         for (int live = 0; live < 2; ++live)
             for (int temper = 0; temper < 2; ++temper)
@@ -187,7 +210,7 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
     } else {
         exprs = {"&demcz::window_kernel<4, " + ds + ", true>", "&demcz::window_kernel<4, " + ds + ", false>"};
     }
-    exprs.push_back("&demcz::logp_kernel<4>");
+    if (!derive) exprs.push_back("&demcz::logp_kernel<4>");
     for (const auto& e : exprs) RTCCHK(hiprtcAddNameExpression(prog, e.c_str()));
     std::vector<const char*> argv;
     for (const auto& o : opts) argv.push_back(o.c_str());
@@ -200,10 +223,13 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
             if (hiprtcGetProgramLog(prog, &log[0]) != HIPRTC_SUCCESS) log.clear();
             while (!log.empty() && log.back() == '\0') log.pop_back();
         }
-        err = "program target: compilation failed (" + std::string(hiprtcGetErrorString(rc)) + ")";
-        if (text.find("demcz_logobj") == std::string::npos)          // (the library's own call is in demcz_kernels.h, not in `text`)
+        err = who + "compilation failed (" + std::string(hiprtcGetErrorString(rc)) + ")";
+        if (!derive && text.find("demcz_logobj") == std::string::npos)   // (the library's own call is in demcz_kernels.h, not in `text`)
             err += "; the program does not define demcz_logobj -- it must define "
                    "__device__ double demcz_logobj(const double* x, const double* data, int64_t ndata)";
+        if (derive && text.find("demcz_derive") == std::string::npos)    // (... and derive_kernel's in demcz_kernels_derive.h)
+            err += "; the program does not define demcz_derive -- it must define "
+                   "__device__ void demcz_derive(const double* x, double logp, const double* data, int64_t ndata, double* out)";
         err += ":\n" + trim_log(log);
         return false;
     }
@@ -213,12 +239,13 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
     RTCCHK(hiprtcGetCode(prog, code.object.data()));
     if (const char* dump = getenv("DEMCZ_PROGRAM_DUMP"); dump && *dump) {
         // diagnosis (scripts/kernel_regs.py, llvm-objdump): the code object as a file in that directory
-        const std::string path = std::string(dump) + "/demcz_program_" + (wave ? "wave" : "lane") + "_d" + ds + "_" +
+        const std::string path = std::string(dump) + "/demcz_program_" + (derive ? "derive" : wave ? "wave" : "lane") + "_d" + ds + "_" +
                                  std::to_string(std::hash<std::string>{}(text) % 1000000007ull) + ".co";
         if (FILE* f = fopen(path.c_str(), "wb")) { (void)fwrite(code.object.data(), 1, code.object.size(), f); fclose(f); }
     }
     std::vector<std::string*> lowered;
-    if (wave) lowered = {&code.wave[0][0], &code.wave[0][1], &code.wave[1][0], &code.wave[1][1], &code.logp};
+    if (derive) lowered = {&code.derive};
+    else if (wave) lowered = {&code.wave[0][0], &code.wave[0][1], &code.wave[1][0], &code.wave[1][1], &code.logp};
     else lowered = {&code.window_full, &code.window_blocks, &code.logp};
     for (size_t i = 0; i < lowered.size(); ++i) {
         const char* nm = nullptr;
@@ -226,6 +253,7 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
         *lowered[i] = nm;
     }
     code.d = d;
+    code.m = m;
     code.unit = unit;
     return true;
 }
@@ -235,14 +263,19 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
 
 namespace demcz_prog {
 
-int32_t get_code(int d, const char* source, const char* options, int unit, std::shared_ptr<const Code>& out, std::string& err)
+int32_t get_code(int d, const char* source, const char* options, int unit, std::shared_ptr<const Code>& out, std::string& err, int m)
 {
-    if (unit != UNIT_ONE_LANE && unit != UNIT_WAVE) {
+    if (unit != UNIT_ONE_LANE && unit != UNIT_WAVE && unit != UNIT_DERIVE) {
         err = "program target: lanes_per_chain must be 0, 1 or DEMCZ_LAYOUT_PROGRAM_WAVE";
         return 1;
     }
+    const std::string who = who_of(unit);
     if (d < 1 || d > MAX_PROGRAM_D) {
-        err = "program target: d must be in 1.." + std::to_string(MAX_PROGRAM_D);
+        err = who + "d must be in 1.." + std::to_string(MAX_PROGRAM_D);
+        return 1;
+    }
+    if (unit == UNIT_DERIVE && (m < 1 || m > MAX_DERIVE_M)) {
+        err = who + "m must be in 1.." + std::to_string(MAX_DERIVE_M);
         return 1;
     }
     if (unit == UNIT_WAVE && d < WAVE_MIN_D) {
@@ -251,15 +284,17 @@ int32_t get_code(int d, const char* source, const char* options, int unit, std::
         return 1;
     }
     if (!source) {
-        err = "program target: source is NULL";
+        err = who + "source is NULL";
         return 1;
     }
     std::string inc;
     if (!rocm_include(inc, err)) return 1;
     std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-I" + inc};
-    for (const char* const* s = k_layout_switches; *s; ++s) opts.push_back(*s);
+    if (unit != UNIT_DERIVE)
+        for (const char* const* s = k_layout_switches; *s; ++s) opts.push_back(*s);
     for (auto& o : split_options(options)) opts.push_back(o);
-    const std::string text = compose(d, source, unit);
+    // (the text is the key: it names the unit's kernel header and, for a derive unit, DEMCZ_M)
+    const std::string text = compose(d, m, source, unit);
     std::string key = text;
     for (const auto& o : opts) key += '\0' + o;
     {
@@ -268,7 +303,7 @@ int32_t get_code(int d, const char* source, const char* options, int unit, std::
         if (it != g_code_cache.end()) { out = it->second; return 0; }
     }
     auto code = std::make_shared<Code>();
-    if (!compile(text, opts, d, unit, *code, err)) return 1;
+    if (!compile(text, opts, d, m, unit, *code, err)) return 1;
     std::lock_guard<std::mutex> lk(g_prog_mu);
     auto ins = g_code_cache.emplace(key, code);           // (another thread may have compiled the same program meanwhile)
     out = ins.first->second;
@@ -284,7 +319,9 @@ int32_t get_module(const std::shared_ptr<const Code>& code, int device, Module& 
     Module m;
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipModuleLoadData(&m.module, code->object.data());
-    if (code->unit == UNIT_WAVE) {
+    if (code->unit == UNIT_DERIVE) {
+        if (e == hipSuccess) e = hipModuleGetFunction(&m.derive, m.module, code->derive.c_str());
+    } else if (code->unit == UNIT_WAVE) {
         for (int live = 0; live < 2; ++live)
             for (int temper = 0; temper < 2; ++temper)
                 if (e == hipSuccess) e = hipModuleGetFunction(&m.wave[live][temper], m.module, code->wave[live][temper].c_str());
@@ -292,10 +329,10 @@ int32_t get_module(const std::shared_ptr<const Code>& code, int device, Module& 
         if (e == hipSuccess) e = hipModuleGetFunction(&m.window_full, m.module, code->window_full.c_str());
         if (e == hipSuccess) e = hipModuleGetFunction(&m.window_blocks, m.module, code->window_blocks.c_str());
     }
-    if (e == hipSuccess) e = hipModuleGetFunction(&m.logp, m.module, code->logp.c_str());
+    if (code->unit != UNIT_DERIVE && e == hipSuccess) e = hipModuleGetFunction(&m.logp, m.module, code->logp.c_str());
     if (e != hipSuccess) {
         if (m.module) (void)hipModuleUnload(m.module);
-        err = std::string("program target: loading the code object: ") + hipGetErrorString(e);
+        err = std::string(who_of(code->unit)) + "loading the code object: " + hipGetErrorString(e);
         return 2;
     }
     m.code = code;          // (the cache keeps the code object alive with the module)

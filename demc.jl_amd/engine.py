@@ -135,7 +135,135 @@ class _PinnedOwner:
         self._bases = []
 
 
-class HipEngine:
+class _HistoryStatistics:
+    """The statistics over an on-device history, shared by everything that holds a handle with one: ``HipEngine`` (the history of
+    a run) and ``DerivedHistory`` (functions of it).  Needs ``_L``, ``_h``, ``_chk``, ``N`` and ``d``."""
+
+    def rhat(self, g_from, g_to):
+        out = np.empty(self.d)
+        self._chk(self._L.demcz_rhat(self._h, int(g_from), int(g_to), _lib.ptr(out)))
+        return out
+
+    def rhat_partial(self, g_from, g_to, stage, grand):
+        out = np.empty(self.d if stage == 0 else 2 * self.d)
+        g = _lib.f64(grand) if grand is not None else None
+        self._chk(self._L.demcz_rhat_partial(self._h, int(g_from), int(g_to), int(stage), _lib.ptr(g), _lib.ptr(out)))
+        return out
+
+    def autocov_sums(self, g_from, g_to, lag_from, lag_to):
+        """d x (lag_to - lag_from + 1): the sum over this engine's 2N split chains of n c_j(t) (demcz_autocov_sums)."""
+        out = np.empty((self.d, max(0, int(lag_to) - int(lag_from) + 1)), order="F")
+        self._chk(self._L.demcz_autocov_sums(self._h, int(g_from), int(g_to), int(lag_from), int(lag_to), _lib.ptr(out)))
+        return out
+
+    def ess(self, g_from, g_to, max_lag=0):
+        """Effective sample size per parameter over generations g_from..g_to (demcz_ess): an ESS tuple."""
+        d = self.d
+        out = ESS(np.empty(d), np.empty(d), np.empty(d), np.zeros(d, dtype=np.int64), np.zeros(d, dtype=np.int32))
+        self._chk(self._L.demcz_ess(self._h, int(g_from), int(g_to), int(max_lag), _lib.ptr(out.ess), _lib.ptr(out.tau),
+                                    _lib.ptr(out.varplus), _lib.ptr(out.pairs, _lib._lp), _lib.ptr(out.converged, _lib._ip)))
+        return out
+
+    def select_counts(self, g_from, g_to, shift, prefix):
+        """One counting pass of the quantiles' radix select over this engine's chains (demcz_select_counts): prefix is (d, nprefix)
+        uint64; returns (counts (d, nprefix, 256) int64, nan_count (d,) int64)."""
+        prefix = np.array(prefix, dtype=np.uint64, order="F", ndmin=2)
+        if prefix.shape[0] != self.d:
+            raise ValueError("prefix must be (d, nprefix)")
+        nprefix = prefix.shape[1]
+        counts = np.zeros((self.d, nprefix, 256), dtype=np.int64)
+        nan = np.zeros(self.d, dtype=np.int64)
+        self._chk(self._L.demcz_select_counts(self._h, int(g_from), int(g_to), int(shift), nprefix, _lib.ptr(prefix, _lib._up),
+                                              _lib.ptr(counts, _lib._lp), _lib.ptr(nan, _lib._lp)))
+        return counts, nan
+
+    def quantiles(self, g_from, g_to, probs, with_order_stats=False):
+        """Quantiles per parameter over generations g_from..g_to (demcz_quantiles, Hyndman-Fan type 7, exact selection): d x nq,
+        or a Quantiles tuple (q, lower, upper) with the two order statistics behind every entry."""
+        probs = np.ascontiguousarray(np.atleast_1d(probs), dtype=np.float64)
+        nq, d = probs.size, self.d
+        out = Quantiles(np.empty((d, nq), order="F"), np.empty((d, nq), order="F"), np.empty((d, nq), order="F"))
+        self._chk(self._L.demcz_quantiles(self._h, int(g_from), int(g_to), nq, _lib.ptr(probs), _lib.ptr(out.q),
+                                          _lib.ptr(out.lower), _lib.ptr(out.upper)))
+        return out if with_order_stats else out.q
+
+    def mean_cov(self, g_from, g_to):
+        mean = np.empty(self.d)
+        cov = np.empty((self.d, self.d), order="F")
+        self._chk(self._L.demcz_mean_cov(self._h, int(g_from), int(g_to), _lib.ptr(mean), _lib.ptr(cov)))
+        return mean, cov
+
+    def derive(self, program, g_from, g_to):
+        """``program`` (a ``DerivedProgram``) evaluated on every draw of generations g_from..g_to, on the device (demcz_derive):
+        a ``DerivedHistory`` whose generations keep their numbers.  It owns its memory and outlives this object."""
+        if program.d != self.d:
+            raise ValueError("the program's d is not the history's")
+        src, opts, data, ndata = program._args()
+        out = C.c_void_p()
+        self._chk(self._L.demcz_derive(self._h, int(g_from), int(g_to), program.m, src, opts, data, ndata, C.byref(out)))
+        return DerivedHistory(self._L, out, self.N, program.m, int(g_from), int(g_to), program.names, getattr(self, "chain_id0", 0))
+
+
+class DerivedHistory(_HistoryStatistics):
+    """An N x m x w history of derived quantities on the device (``demcz_derive``): generations ``g_from..g_to``, numbered as in
+    the history it came from.  ``rhat``, ``rhat_partial``, ``autocov_sums``, ``ess``, ``select_counts``, ``quantiles``, ``mean_cov``
+    and ``derive`` are ``HipEngine``'s; nothing else of an engine applies (the library answers ERR_STATE)."""
+
+    def __init__(self, L, handle, N, m, g_from, g_to, names=None, chain_id0=0):
+        self._L, self._h = L, handle
+        self.N, self.d, self.m = int(N), int(m), int(m)
+        self.g_from, self.g_to = int(g_from), int(g_to)
+        self.names = list(names) if names is not None else None
+        self.chain_id0 = int(chain_id0)
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise DemczError(rc, (self._L.demcz_last_error(self._h) or b"").decode())
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._L.demcz_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def synchronize(self):
+        self._chk(self._L.demcz_synchronize(self._h))
+
+    def get(self, g_from=None, g_to=None):
+        """The values of generations g_from..g_to (default: all) as an N x m x w column-major array."""
+        g_from = self.g_from if g_from is None else int(g_from)
+        g_to = self.g_to if g_to is None else int(g_to)
+        out = np.empty((self.N, self.m, max(0, g_to - g_from + 1)), order="F")
+        self._chk(self._L.demcz_get_history(self._h, g_from, g_to, _lib.ptr(out), None))
+        return out
+
+    def summary(self, probs=None):
+        """What ``posterior_summary`` returns for a host array (mean, sd, mcse, ess, rhat, converged and, with ``probs``,
+        quantiles), computed from the handle with no download, plus ``names``."""
+        mean, _ = self.mean_cov(self.g_from, self.g_to)
+        e = self.ess(self.g_from, self.g_to)
+        with np.errstate(all="ignore"):
+            out = dict(mean=mean, sd=np.sqrt(e.varplus), mcse=np.sqrt(e.varplus / e.ess), ess=e.ess,
+                       rhat=self.rhat(self.g_from, self.g_to), converged=e.converged)
+        if probs is not None:
+            out["quantiles"] = self.quantiles(self.g_from, self.g_to, probs)
+        out["names"] = self.names
+        return out
+
+
+class HipEngine(_HistoryStatistics):
     """Device state of one shard: Z replica, current states, history, RNG position."""
 
     def __init__(self, *, N, d, K, Mcap, Gcap, blockindex, eps_scale, seed, target, chain_id0=0,
@@ -379,54 +507,6 @@ class HipEngine:
         self._chk(self._L.demcz_get_changed_total(self._h, int(g_from), int(g_to), C.byref(tot), C.byref(src)))
         return (int(tot.value), bool(src.value)) if with_source else int(tot.value)
 
-    def rhat(self, g_from, g_to):
-        out = np.empty(self.d)
-        self._chk(self._L.demcz_rhat(self._h, int(g_from), int(g_to), _lib.ptr(out)))
-        return out
-
-    def rhat_partial(self, g_from, g_to, stage, grand):
-        out = np.empty(self.d if stage == 0 else 2 * self.d)
-        g = _lib.f64(grand) if grand is not None else None
-        self._chk(self._L.demcz_rhat_partial(self._h, int(g_from), int(g_to), int(stage), _lib.ptr(g), _lib.ptr(out)))
-        return out
-
-    def autocov_sums(self, g_from, g_to, lag_from, lag_to):
-        """d x (lag_to - lag_from + 1): the sum over this engine's 2N split chains of n c_j(t) (demcz_autocov_sums)."""
-        out = np.empty((self.d, max(0, int(lag_to) - int(lag_from) + 1)), order="F")
-        self._chk(self._L.demcz_autocov_sums(self._h, int(g_from), int(g_to), int(lag_from), int(lag_to), _lib.ptr(out)))
-        return out
-
-    def ess(self, g_from, g_to, max_lag=0):
-        """Effective sample size per parameter over generations g_from..g_to (demcz_ess): an ESS tuple."""
-        d = self.d
-        out = ESS(np.empty(d), np.empty(d), np.empty(d), np.zeros(d, dtype=np.int64), np.zeros(d, dtype=np.int32))
-        self._chk(self._L.demcz_ess(self._h, int(g_from), int(g_to), int(max_lag), _lib.ptr(out.ess), _lib.ptr(out.tau),
-                                    _lib.ptr(out.varplus), _lib.ptr(out.pairs, _lib._lp), _lib.ptr(out.converged, _lib._ip)))
-        return out
-
-    def select_counts(self, g_from, g_to, shift, prefix):
-        """One counting pass of the quantiles' radix select over this engine's chains (demcz_select_counts): prefix is (d, nprefix)
-        uint64; returns (counts (d, nprefix, 256) int64, nan_count (d,) int64)."""
-        prefix = np.array(prefix, dtype=np.uint64, order="F", ndmin=2)
-        if prefix.shape[0] != self.d:
-            raise ValueError("prefix must be (d, nprefix)")
-        nprefix = prefix.shape[1]
-        counts = np.zeros((self.d, nprefix, 256), dtype=np.int64)
-        nan = np.zeros(self.d, dtype=np.int64)
-        self._chk(self._L.demcz_select_counts(self._h, int(g_from), int(g_to), int(shift), nprefix, _lib.ptr(prefix, _lib._up),
-                                              _lib.ptr(counts, _lib._lp), _lib.ptr(nan, _lib._lp)))
-        return counts, nan
-
-    def quantiles(self, g_from, g_to, probs, with_order_stats=False):
-        """Quantiles per parameter over generations g_from..g_to (demcz_quantiles, Hyndman-Fan type 7, exact selection): d x nq,
-        or a Quantiles tuple (q, lower, upper) with the two order statistics behind every entry."""
-        probs = np.ascontiguousarray(np.atleast_1d(probs), dtype=np.float64)
-        nq, d = probs.size, self.d
-        out = Quantiles(np.empty((d, nq), order="F"), np.empty((d, nq), order="F"), np.empty((d, nq), order="F"))
-        self._chk(self._L.demcz_quantiles(self._h, int(g_from), int(g_to), nq, _lib.ptr(probs), _lib.ptr(out.q),
-                                          _lib.ptr(out.lower), _lib.ptr(out.upper)))
-        return out if with_order_stats else out.q
-
     def best(self, g_from, g_to):
         """The best draw of generations g_from..g_to (demcz_best): a Best tuple; chain is 0-based and local to this engine."""
         v, c, g = C.c_double(), C.c_int64(), C.c_int64()
@@ -438,12 +518,6 @@ class HipEngine:
         out = np.empty(self.N)
         self._chk(self._L.demcz_accept_ratio(self._h, int(g_from), int(g_to), _lib.ptr(out)))
         return out
-
-    def mean_cov(self, g_from, g_to):
-        mean = np.empty(self.d)
-        cov = np.empty((self.d, self.d), order="F")
-        self._chk(self._L.demcz_mean_cov(self._h, int(g_from), int(g_to), _lib.ptr(mean), _lib.ptr(cov)))
-        return mean, cov
 
     # -- host-closure mode ----------------------------------------------------------------------
     def closure_buffers(self):

@@ -315,6 +315,20 @@ class _Runner:
                 best = b
         return best
 
+    def derive(self, program, g_from, g_to):
+        """``program`` (a ``DerivedProgram``) on every engine of this runner over generations g_from..g_to (the map is per draw,
+        local to each shard's chains): a ``_DerivedRunner`` whose ``rhat``, ``ess`` and ``quantiles`` are the ones above over the
+        derived histories -- partial sums and counts added over shards exactly as for the parameters themselves."""
+        hists = []
+        try:
+            for e in self.engines:
+                hists.append(e.derive(program, g_from, g_to))
+        except Exception:
+            for h in hists:
+                h.close()
+            raise
+        return _DerivedRunner(self, hists, program, g_from, g_to)
+
     def changed(self, g_from, g_to):
         c = sum(e.get_changed(g_from, g_to) for e in self.engines)
         if self.sh is not None and self.sh.world_size > 1:
@@ -418,6 +432,34 @@ class _Runner:
     def close(self):
         for e in self.engines:
             e.close()
+
+
+class _DerivedRunner(_Runner):
+    """The derived histories of a runner's engines (``_Runner.derive``), one per shard in shard order.  ``rhat``, ``ess`` and
+    ``quantiles`` are ``_Runner``'s own code: it needs ``rhat_partial``, ``autocov_sums``, ``select_counts``, ``N`` and ``d`` of an
+    engine, which a ``DerivedHistory`` has.  Nothing that runs, appends or exchanges applies."""
+
+    def __init__(self, parent, histories, program, g_from, g_to):
+        # (not _Runner.__init__: that one configures engines for a run)
+        self.engines = histories
+        self.sh = parent.sh
+        self.K, self.N_total, self.d = parent.K, parent.N_total, program.m
+        self.lag, self.pending = 0, []
+        self.lib_exchange, self.peer_group, self.host_exchange = parent.lib_exchange, parent.peer_group, parent.host_exchange
+        self.names = program.names
+        self.g_from, self.g_to = int(g_from), int(g_to)
+
+    def get(self, g_from=None, g_to=None):
+        """The values of this process's shards, concatenated over chains in shard order: N_local x m x w, column-major."""
+        parts = [h.get(g_from, g_to) for h in self.engines]
+        return parts[0] if len(parts) == 1 else np.asfortranarray(np.concatenate(parts, axis=0))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
 
 
 def make_runner(logobj, Zmat, N, K, Ngeneration, blockindex, eps_scale, X, logp, *, seed, sharding, device_id,

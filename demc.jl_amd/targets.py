@@ -142,5 +142,45 @@ class ProgramTarget:
         return L.demcz_set_program(h, src, opts, _lib.ptr(self.data) if n else None, n)
 
 
+class DerivedProgram:
+    """``m`` functions of every draw, written as HIP C++ and run on the device over a history (``demcz_derive``, include/demcz.h):
+    what Stan calls generated quantities.
+
+    ``source`` defines ``__device__ void demcz_derive(const double* x, double logp, const double* data, int64_t ndata,
+    double* out)``: ``x`` holds the ``DEMCZ_D`` (= ``d``) parameters of one draw, ``logp`` its ``log_obj`` (NaN where the source
+    keeps none), ``data`` the ``ndata`` doubles of ``data`` (device memory, read-only, NULL without data), ``out`` the
+    ``DEMCZ_M`` (= ``m``) results, preset to NaN.  Compiled like a ``ProgramTarget``: ``-O3 -ffp-contract=off`` followed by
+    ``options``.  ``d`` and ``m`` must be in 1..32; ``names`` optionally labels the ``m`` results.
+
+    The function is called once per draw in no particular order, so it must be a pure function of its arguments.
+    Runtime-indexed ``x[j]`` or ``out[k]`` inside the function sends those arrays to scratch memory; loops over the compile-time
+    ``DEMCZ_D`` and ``DEMCZ_M`` unroll and avoid that.
+
+    Used through ``HipEngine.derive``, ``demc.derive_chain`` or a runner's ``derive``; each returns a ``DerivedHistory``.
+    """
+
+    def __init__(self, source: str, d: int, m: int, data=None, options=(), names=None):
+        self.source = str(source)
+        self.d, self.m = int(d), int(m)
+        self.data = None if data is None else np.ascontiguousarray(np.ravel(data), dtype=np.float64)
+        self.options = (options,) if isinstance(options, str) else tuple(str(o) for o in options)
+        self.names = None if names is None else [str(n) for n in names]
+        if self.names is not None and len(self.names) != self.m:
+            raise ValueError("names must hold m labels")
+
+    def _args(self):
+        """(source, options, data pointer or None, ndata) as the C ABI takes them; the data array is kept alive by self."""
+        n = 0 if self.data is None else self.data.size
+        return self.source.encode(), " ".join(self.options).encode(), (_lib.ptr(self.data) if n else None), n
+
+    def check(self):
+        """Compile the program (no device needed); raises ``DemczError`` with the compiler log if it does not compile."""
+        L = _lib.load()
+        src, opts, _, _ = self._args()
+        rc = L.demcz_derive_check(self.d, self.m, src, opts)
+        if rc != 0:
+            raise _lib.DemczError(rc, (L.demcz_last_error(None) or b"").decode())
+
+
 def is_device_target(obj) -> bool:
     return isinstance(obj, (MvNormalTarget, IsoQuadTarget, LinRegSSETarget, ProgramTarget))

@@ -6,7 +6,7 @@ kernels the autostop uses.  ``flatten_chain`` is a pure re-indexing (utils.jl:22
 (utils.jl:120-125) finds the best draw on the device.  Plotting and ``save_res`` are not reproduced (dead code in Julia >= 1.0,
 SURVEY.md Q16).
 Beyond the reference: ``ess_chain``, ``autocov_chain``, ``quantile_chain`` and ``posterior_summary`` (effective sample size and
-quantiles by exact selection).
+quantiles by exact selection), and ``derive_chain`` (functions of the draws, evaluated on the device).
 Checkpoints: the reference only resumes in memory (``prevrun=``); ``save_checkpoint`` /
 ``load_checkpoint`` put the same information in one ``.npz`` file.
 """
@@ -140,6 +140,27 @@ def posterior_summary(chain, device_id=0, probs=None):
     if probs is not None:
         out["quantiles"] = quantile_chain(chain, probs, device_id=device_id)
     return out
+
+
+def derive_chain(chain, log_obj, program, device_id=0):
+    """``program`` (a ``DerivedProgram``) evaluated on every draw of an Npop x Npar x Ngeneration history and its
+    Npop x Ngeneration ``log_obj`` (or None: the program's ``logp`` is NaN) -- a ``DerivedHistory`` on the device, generations
+    1..Ngeneration (demcz_derive_array).  The uploaded arrays are not kept.  Not in the reference."""
+    from .engine import DerivedHistory
+    chain = _lib.f64(chain, "F")
+    N, d, G = chain.shape
+    if program.d != d:
+        raise ValueError("the program's d is not the chain's Npar")
+    lo = None
+    if log_obj is not None:
+        lo = _lib.f64(log_obj, "F")
+        if lo.shape != (N, G):
+            raise ValueError("log_obj must be Npop x Ngeneration")
+    src, opts, data, ndata = program._args()
+    L = _lib.load()
+    out = C.c_void_p()
+    _chk(L.demcz_derive_array(device_id, _lib.ptr(chain), _lib.ptr(lo), N, d, G, program.m, src, opts, data, ndata, C.byref(out)))
+    return DerivedHistory(L, out, N, program.m, 1, G, program.names)
 
 
 def convergence_check(chain, log_obj, figure_path=None, verbose=True, parnames=None, device_id=0):

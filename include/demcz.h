@@ -441,6 +441,46 @@ int32_t demcz_quantiles_array(int32_t device_id, const double* chain, int64_t N,
 int32_t demcz_best_array(int32_t device_id, const double* log_obj, int64_t N, int64_t G, double* bestval, int64_t* chain,
                          int64_t* column);
 
+/* Derived quantities (generated quantities; not in the reference): m user-written functions of every draw of a history window,
+ * evaluated on the device into a DERIVED HISTORY -- a second handle that holds nothing but the N x m x w values and takes every
+ * statistic above unchanged, so that a variance from a log-variance, a contrast of two coefficients or the indicator x[0] > 0
+ * (whose mean is a probability) is summarised without the history leaving the device.  A derive program is HIP C++ that defines
+ *     __device__ void demcz_derive(const double* x, double logp, const double* data, int64_t ndata, double* out);
+ * x: the DEMCZ_D (= d of the source) parameters of one draw; logp: its log_obj, NaN where the source keeps none (arrays given
+ * without log_obj, a derived history); data: the ndata doubles given with the program (device memory, read-only; NULL when
+ * ndata is 0); out: DEMCZ_M (= m) entries, preset to NaN -- an entry the function does not write stays NaN.  DEMCZ_D, DEMCZ_M,
+ * INFINITY and NAN are defined for the program.  Compiled like a program target: --offload-arch=gfx950 -O3 -ffp-contract=off
+ * -I<rocm>/include, then `options` (space-separated, may be NULL); a fused multiply-add happens only where fma() is written.
+ * The unit holds the program and one streaming kernel (one lane per draw), none of the library's window kernels, and shares the
+ * process-wide cache of program targets under a key of its own that includes m.  1 <= d <= 32, 1 <= m <= 32.
+ * The function is called once per draw in no particular order, so it must be a pure function of its arguments.  Indexing x or
+ * out with a run-time value sends those arrays to scratch memory; loops over the compile-time DEMCZ_D and DEMCZ_M unroll and
+ * keep them in registers.
+ *   demcz_derive_check  compiles the program and needs no device.  DEMCZ_OK, or DEMCZ_ERR_INVALID_ARGUMENT with the compiler log
+ *                       (user's line numbers, file "program") in demcz_last_error(NULL); d or m out of range: the same code with a
+ *                       message that names the limit.
+ *   demcz_derive        generations g_from..g_to of h's history (range and state errors are demcz_rhat's; a voided LIVE slab is
+ *                       redone first).  The program is compiled or taken from the cache and loaded on h's device, data copied to
+ *                       memory the derived history owns, the kernel run on h's stream behind what is queued there, and the call
+ *                       returns when it is done.  A compile error is DEMCZ_ERR_INVALID_ARGUMENT with the log in
+ *                       demcz_last_error(h); a failed allocation DEMCZ_ERR_HIP, nothing leaked.  *derived is NULL on every
+ *                       failure.  Works on a sharded handle and on a member of a replica group: the map is per draw, local to
+ *                       the handle's own chains.
+ *   demcz_derive_array  the same from host arrays: chain N x d x G column-major, log_obj N x G or NULL; generations 1..G.  The
+ *                       uploads are freed before it returns; only the derived history stays.
+ * The derived history is a demcz_handle with N chains, m "parameters" and w = g_to-g_from+1 generations that KEEP THEIR NUMBERS:
+ * the statistics are asked for g_from..g_to or any window inside.  It owns its memory, outlives the handle it came from and is
+ * freed by demcz_destroy.  It takes demcz_rhat, demcz_rhat_partial, demcz_autocov_sums, demcz_ess, demcz_select_counts,
+ * demcz_quantiles, demcz_mean_cov, demcz_get_history with log_obj = NULL, demcz_synchronize, demcz_last_error, demcz_destroy and
+ * demcz_derive (a derived history of a derived history; its logp is NaN).  Every other call that takes a handle returns
+ * DEMCZ_ERR_STATE on it, with a message that says so. */
+int32_t demcz_derive_check(int32_t d, int32_t m, const char* source, const char* options);
+int32_t demcz_derive(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t m, const char* source, const char* options,
+                     const double* data, int64_t ndata, demcz_handle** derived);
+int32_t demcz_derive_array(int32_t device_id, const double* chain, const double* log_obj /* may be NULL */,
+                           int64_t N, int32_t d, int64_t G, int32_t m, const char* source, const char* options,
+                           const double* data, int64_t ndata, demcz_handle** derived);
+
 /* Introspection for benchmarks and tests. */
 int32_t demcz_get_info(const demcz_handle* h, int64_t* M, int64_t* launches_window, int32_t* lanes_per_chain);
 

@@ -407,6 +407,45 @@ function extract_best(mc)                                                       
     v[], mc.chain[c[] + 1, :, g[] + 1]
 end
 
+# ---- derived quantities: m functions of every draw, evaluated on the device (include/demcz.h: demcz_derive; not in the reference)
+# `source` defines
+#     __device__ void demcz_derive(const double* x, double logp, const double* data, int64_t ndata, double* out)
+# over the DEMCZ_D = d parameters of a draw and its log_obj; out has DEMCZ_M = m entries, preset to NaN.  The function is called
+# once per draw in no particular order: it must be a pure function of its arguments.
+struct DerivedProgram
+    source::String; d::Int; m::Int; data::Vector{Float64}; options::Vector{String}; names::Vector{String}
+end
+DerivedProgram(source, d, m; data=Float64[], options=String[], names=String[]) =
+    DerivedProgram(String(source), Int(d), Int(m), Vector{Float64}(data), Vector{String}(options), Vector{String}(names))
+check(p::DerivedProgram) = chk(ccall((:demcz_derive_check, libdemcz), Int32, (Int32, Int32, Cstring, Cstring),
+                                     Int32(p.d), Int32(p.m), p.source, join(p.options, " ")))
+# derive(h, p, g_from, g_to) -> the handle of a derived history (N x m x w, generations keep their numbers): it takes rhat, ess,
+# quantiles, mean_cov, get_history without log_obj and derive, and is freed with destroy
+function derive(h, p::DerivedProgram, g_from, g_to)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve p chk(ccall((:demcz_derive, libdemcz), Int32,
+                             (Ptr{Cvoid}, Int64, Int64, Int32, Cstring, Cstring, Ptr{Float64}, Int64, Ref{Ptr{Cvoid}}),
+                             h, g_from, g_to, Int32(p.m), p.source, join(p.options, " "),
+                             isempty(p.data) ? C_NULL : pointer(p.data), length(p.data), out), h)
+    out[]
+end
+# ... from host arrays (generations 1:Ngeneration); log_obj may be `nothing`: the program's logp is then NaN
+function derive_chain(chain::Array{Float64,3}, log_obj::Union{Array{Float64,2},Nothing}, p::DerivedProgram; device_id=0)
+    Npop, Npar, Ngeneration = size(chain)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve p chk(ccall((:demcz_derive_array, libdemcz), Int32,
+                             (Int32, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Int64, Int32, Cstring, Cstring, Ptr{Float64}, Int64, Ref{Ptr{Cvoid}}),
+                             device_id, chain, log_obj === nothing ? C_NULL : log_obj, Npop, Npar, Ngeneration, Int32(p.m), p.source,
+                             join(p.options, " "), isempty(p.data) ? C_NULL : pointer(p.data), length(p.data), out))
+    out[]
+end
+# the values of a derived history: N x m x w
+function derived_values(hd, N, m, g_from, g_to)
+    v = zeros(N, m, g_to - g_from + 1)
+    chk(ccall((:demcz_get_history, libdemcz), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Ptr{Float64}), hd, g_from, g_to, v, C_NULL), hd)
+    v
+end
+
 # ---- checkpoint: what a resumed run needs (the reference resumes in memory only, demcz.jl:18-22) ----------------------------
 struct Checkpoint
     prevrun::MC                 # last generation only: chain[:, :, end:end], log_obj[:, end:end], Xcurrent, log_objcurrent
