@@ -8,6 +8,7 @@
 #include "demcz_kernels_sel.h"
 #include "demcz_select_host.h"
 #include "demcz_slab_plan.h"
+#include "demcz_run_plan.h"
 #include "demcz_kernels_ml.h"
 #include "demcz_kernels_pc.h"
 #include "demcz_kernels_lr.h"
@@ -277,8 +278,6 @@ struct demcz_handle {
     bool timing = false;              // demcz_set_kernel_timing: events around every window-kernel launch
     std::vector<std::pair<hipEvent_t, hipEvent_t>> timed;
     std::vector<int32_t> timed_slabs;    // autostop slabs each bracket covers (demcz_run_checked groups them; 1 otherwise)
-    int32_t bracket_slabs = 1;        // demcz_run_checked -> demcz_run: slabs of the call being made ...
-    int64_t plan_next = 0;            // ... and the generations of the launch that follows it (0: not known)
     std::vector<double> series_start_ms, series_dur_ms;     // of the brackets the last demcz_get_kernel_time summed up
     int64_t timed_launches = 0;
     int64_t live_wg_cap = -1;         // consumer workgroups a LIVE launch may have (all must be resident at once); -1: not asked yet
@@ -331,7 +330,7 @@ struct demcz_handle {
     int32_t live_rearms = 0;          // times the handle went LIVE again
     int64_t rearm_from = -1;          // >= 0: a demcz_run call that starts behind this generation re-arms (no_live is set)
     uint32_t fail_row_hint = 0xffffffffu;   // archive row of the wait that failed (live_failed -> live_rollback), 0xffffffff: unknown
-    struct RecDesc { bool valid = false; int64_t g_first = 0, M = 0, rows = 0; int32_t ngen = 0, boff = 0; } rec_desc[2];
+    RecDesc rec_desc[2];              // what each draw-record buffer holds (demcz_run_plan.h)
     // wave-per-chain split layout: the producer half of a launch is a kernel of its own on a side stream (its own, small
     // register budget: it fills the SIMDs beside the one-wave-per-SIMD consumers instead of sharing their workgroup shape)
     hipStream_t prod_stream = nullptr;
@@ -598,11 +597,12 @@ static int32_t sync_event(demcz_handle* h, hipEvent_t ev, const char* what)
     return wait_deadline(h, [ev]() { return hipEventQuery(ev); }, what);
 }
 
-#define SYNCCHK(h, s)                                                                            \
+#define SYNCCHK_AS(h, s, who)                                                                    \
     do {                                                                                         \
-        int32_t rcs_ = sync_stream((h), (s), __func__);                                          \
+        int32_t rcs_ = sync_stream((h), (s), (who));                                             \
         if (rcs_) return rcs_;                                                                   \
     } while (0)
+#define SYNCCHK(h, s) SYNCCHK_AS(h, s, __func__)
 
 // hipFree / hipMalloc synchronise the whole device: before either, every stream of a sharded handle is waited for HERE, with
 // the deadline -- so that a stalled peer surfaces as DEMCZ_ERR_COMM instead of a runtime call that never returns.
@@ -1557,7 +1557,7 @@ static bool pw_matrix_form(const demcz_handle* h)
 static bool pw_regular(const WindowParams& P, bool live)
 {
     static const bool no_reg = getenv("DEMCZ_NO_PW_REG") != nullptr;
-    return live && !no_reg && P.K % PS_R == 0 && P.to_boundary % PS_R == 0 && P.ngen % PS_R == 0 && P.ngen >= PS_R;
+    return live && !no_reg && regular_passes(P.K, P.to_boundary, P.ngen, PS_R);
 }
 
 // live: the launch runs through K boundaries whose rows later generations of the SAME launch draw from
@@ -1712,24 +1712,24 @@ static bool ps2_applicable(const demcz_handle* h, const WindowParams& P)
     static const bool off = getenv("DEMCZ_NO_PS2") != nullptr;
     if (off || h->split_kind != SPLIT_WAVE || h->prog_wave || P.d < 2 || P.d > 5 || !h->arena || !h->rec_in_arena) return false;
     if (P.temperature && (P.temperature < h->arena_temp || P.temperature >= h->arena_temp + h->arena_gens)) return false;
-    if (P.K % PS2_R != 0 || P.to_boundary % PS2_R != 0 || P.ngen % PS2_R != 0 || P.ngen < PS2_R) return false;
-    if (P.chain && (!h->hist_joint || (double)h->cfg.N * (h->cfg.d + 1) * (double)h->cfg.Gcap * 8.0 >= 4293918720.0)) return false;
+    if (!regular_passes(P.K, P.to_boundary, P.ngen, PS2_R)) return false;
+    if (P.chain && (!h->hist_joint || !hist_offsets_32bit(h->cfg.N, h->cfg.d, h->cfg.Gcap))) return false;
     return true;
 }
 
-static int32_t pc_prepare(demcz_handle* h, WindowParams& P, int64_t cur_rows, int64_t next_g, int64_t next_ngen, int64_t next_M,
-                          int64_t next_rows, int32_t next_boff)
+// (lp: the launch's plan, demcz_run_plan.h -- rows join per boundary at the same rate in this launch and in the next)
+static int32_t pc_prepare(demcz_handle* h, WindowParams& P, const LaunchPlan& lp)
 {
     {
-        int32_t rcr = rec_reserve(h, std::max<int64_t>(P.ngen, next_ngen));
+        int32_t rcr = rec_reserve(h, std::max<int64_t>(P.ngen, lp.next_ngen));
         if (rcr) return rcr;
     }
     P.rec_stride = h->rec_cap;
     const int cur = h->rec_cur;
+    const int64_t cur_rows = lp.next_rows;
     const int32_t cur_boff = P.K - P.to_boundary;
     auto& dc = h->rec_desc[cur];
-    // the row indices in a record were drawn against M + (boundaries passed) * rows: all of that must agree
-    if (!(dc.valid && dc.g_first == P.g_first && dc.ngen >= P.ngen && dc.M == P.M && dc.rows == cur_rows && dc.boff == cur_boff)) {
+    if (!dc.serves(P.g_first, P.ngen, P.M, cur_rows, cur_boff)) {
         WindowParams Q = P;                 // producer-only launch for THIS window
         Q.consumer_blocks = 0;
         Q.rec_out = h->d_rec[cur];
@@ -1742,11 +1742,11 @@ static int32_t pc_prepare(demcz_handle* h, WindowParams& P, int64_t cur_rows, in
     const int per_wg = (h->ps_dual && !h->dual_now) ? PS_CHAINS : h->split_per_wg;      // (an irregular launch of a two-chain handle: one chain per wave)
     P.consumer_blocks = (int32_t)((P.N + per_wg - 1) / per_wg);
     P.rec_out = h->d_rec[cur ^ 1];
-    P.next_g_first = next_g; P.next_ngen = (int32_t)std::max<int64_t>(next_ngen, 0); P.next_M = next_M;
-    P.next_rows = next_rows; P.next_boff = next_boff;
+    P.next_g_first = lp.next_g_first; P.next_ngen = (int32_t)lp.next_ngen; P.next_M = lp.next_M;
+    P.next_rows = lp.next_rows; P.next_boff = lp.next_boff;
     auto& dn = h->rec_desc[cur ^ 1];
-    dn.valid = next_ngen > 0; dn.g_first = next_g; dn.M = next_M; dn.ngen = (int32_t)std::max<int64_t>(next_ngen, 0);
-    dn.rows = next_rows; dn.boff = next_boff;
+    dn.valid = lp.next_ngen > 0; dn.g_first = lp.next_g_first; dn.M = lp.next_M; dn.ngen = (int32_t)lp.next_ngen;
+    dn.rows = lp.next_rows; dn.boff = lp.next_boff;
     h->rec_cur = cur ^ 1;
     return DEMCZ_OK;
 }
@@ -2345,7 +2345,7 @@ static int32_t group_execute(PeerGroup* G, const std::vector<std::vector<demcz_h
         if (rc) break;
         const int K = G->members[0]->cfg.K;
         for (int64_t g = c0.g_from; g <= c0.g_to && rc == DEMCZ_OK;) {
-            const int64_t w_end = std::min<int64_t>(((g - 1) / K + 1) * (int64_t)K, c0.g_to);
+            const int64_t w_end = std::min<int64_t>(boundary_at_or_after(g, K), c0.g_to);       // (plan_launch's schedule with span 0)
             for (size_t mi = 0; mi < G->members.size() && rc == DEMCZ_OK; ++mi) {
                 const auto& c = calls[mi][ic];
                 rc = demcz_run(G->members[mi], g, w_end, c.gamma, c.tempered ? c.temperature.data() + (g - c.g_from) : nullptr);
@@ -2657,9 +2657,24 @@ extern "C" int32_t demcz_pool_trim(int64_t* device_bytes, int64_t* pinned_bytes)
     return DEMCZ_OK;
 }
 
-extern "C" int32_t demcz_run(demcz_handle* h, int64_t g_from, int64_t g_to, double gamma, const double* temperature)
+// what a caller that makes several calls in a row knows beyond the call at hand (demcz_run_checked)
+struct RunHints {
+    int32_t bracket_slabs = 1;        // autostop slabs the call covers (kernel timing: one event bracket per call)
+    int64_t next_ngen = 0;            // generations of the launch that follows the call (0: not known)
+};
+
+// a call that is to be made (a replica group without its hand-off) or made again (a failed LIVE hand-off)
+static void log_run_call(demcz_handle* h, int64_t g_from, int64_t g_to, double gamma, const double* temperature)
 {
-    NOT_DERIVED(h);
+    demcz_handle::RunCall rcall{g_from, g_to, gamma, temperature != nullptr, {}};
+    if (temperature) rcall.temperature.assign(temperature, temperature + (g_to - g_from + 1));
+    h->live_log.push_back(std::move(rcall));
+}
+
+// demcz_run.  The schedule -- where each window launch ends and of what kind it is -- is plan_launch's (demcz_run_plan.h); this is
+// its executor.
+static int32_t run_call(demcz_handle* h, int64_t g_from, int64_t g_to, double gamma, const double* temperature, const RunHints& hints)
+{
     if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
     DEADCHK(h);
     if (!h->has_state) return fail(h, DEMCZ_ERR_STATE, "demcz_run: call demcz_set_state first");
@@ -2687,7 +2702,7 @@ extern "C" int32_t demcz_run(demcz_handle* h, int64_t g_from, int64_t g_to, doub
     const int64_t shards = (sharded || h->peer_mode != 0) ? h->nranks : 1;
     // capacity check for all appends of this call
     {
-        const int64_t nb = g_to / K - (g_from - 1) / K;
+        const int64_t nb = boundaries_in(g_from, g_to, K);
         const int64_t rows = h->cfg.N * shards;
         if (!h->external_append && h->M_app + nb * rows > h->cfg.Mcap)
             return fail(h, DEMCZ_ERR_CAPACITY, "demcz_run: Z row capacity (Mcap) would be exceeded");
@@ -2706,22 +2721,20 @@ extern "C" int32_t demcz_run(demcz_handle* h, int64_t g_from, int64_t g_to, doub
         // the call is only logged here and executed for ALL members in lockstep, one launch per K-window, at the next
         // verification (group_verify) -- by which time every member has been given the same call.
         if (h->lag != 0 || h->external_append) return fail(h, DEMCZ_ERR_STATE, "demcz_run: replica groups run with append lag 0 and library-owned appends");
-        demcz_handle::RunCall rcall{g_from, g_to, gamma, temperature != nullptr, {}};
-        if (temperature) rcall.temperature.assign(temperature, temperature + G);
-        h->live_log.push_back(std::move(rcall));
+        log_run_call(h, g_from, g_to, gamma, temperature);
         return DEMCZ_OK;
     }
     // (a handle with the arena keeps a call's temperatures inside it when they fit: window_kernel_ps2 then reaches them with the
     //  32-bit offsets it reaches everything else with)
     const bool temp_in_arena = temperature && h->arena && h->arena_temp && G <= h->arena_gens;
     if (temperature && temp_in_arena) {
-        SYNCCHK(h, h->stream);              // (earlier windows may still read the region)
+        SYNCCHK_AS(h, h->stream, "demcz_run");              // (earlier windows may still read the region)
         HIPCHK(h, hipMemcpyAsync(h->arena_temp, temperature, (size_t)G * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        SYNCCHK(h, h->stream);              // the caller may reuse its buffer on return
+        SYNCCHK_AS(h, h->stream, "demcz_run");              // the caller may reuse its buffer on return
     } else if (temperature) {
         if (G > h->temp_cap) {
             { int32_t rcq = quiesce_all(h); if (rcq) return rcq; }
-            SYNCCHK(h, h->stream);
+            SYNCCHK_AS(h, h->stream, "demcz_run");
             if (h->dtemp) HIPCHK(h, dev_free(h->cfg.device_id, h->dtemp));
             h->dtemp = nullptr; h->temp_cap = 0;
             // (+ 8: the wave-per-chain consumer fetches a pass's temperatures as whole 16-byte pieces, demcz_kernels_ps.h)
@@ -2731,7 +2744,7 @@ extern "C" int32_t demcz_run(demcz_handle* h, int64_t g_from, int64_t g_to, doub
         }
         // stream-ordered behind earlier windows that still read dtemp
         HIPCHK(h, hipMemcpyAsync(h->dtemp, temperature, (size_t)G * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        SYNCCHK(h, h->stream);   // the caller may reuse its buffer on return
+        SYNCCHK_AS(h, h->stream, "demcz_run");   // the caller may reuse its buffer on return
     }
     WindowParams P;
     P.Z = h->dZ; P.Zw = h->dZ; P.ZS = h->ZS;
@@ -2752,7 +2765,7 @@ extern "C" int32_t demcz_run(demcz_handle* h, int64_t g_from, int64_t g_to, doub
     P.next_rows = 0; P.next_boff = 0; P.rec_stride = 0;
     P.rec_fields = (h->lanes == DEMCZ_LAYOUT_SPLIT && h->split_kind == SPLIT_ML) ? h->cfg.d + 2 : 0;    // lane-per-parameter consumers: record-major
     P.z_bytes = (uint32_t)std::min<size_t>(h->dZ_bytes, 0xffffffffull);
-    P.hist_bytes = (hist && h->hist_joint) ? (uint32_t)std::min<double>((double)h->cfg.N * (h->cfg.d + 1) * (double)h->cfg.Gcap * 8.0, 4294967295.0) : 0u;
+    P.hist_bytes = (hist && h->hist_joint) ? hist_bytes_u32(h->cfg.N, h->cfg.d, h->cfg.Gcap) : 0u;
     P.brows = h->cfg.N * (peer ? shards : 1);
     P.row_off = peer ? (int64_t)h->rank * h->cfg.N : 0;
     P.n_peers = peer ? h->n_peers : 0;
@@ -2771,7 +2784,6 @@ extern "C" int32_t demcz_run(demcz_handle* h, int64_t g_from, int64_t g_to, doub
     P.stamps = h->d_stamps;
 #endif
     const int E = h->lag;
-    int64_t g = g_from;
     if (h->lanes == DEMCZ_LAYOUT_SPLIT) {
         // draw-record buffers: sized ONCE for the longest launch this handle can make -- a LIVE launch spans up
         // to live_span() generations (never more than the run is long: Gcap, when a history is kept), any other
@@ -2806,9 +2818,7 @@ extern "C" int32_t demcz_run(demcz_handle* h, int64_t g_from, int64_t g_to, doub
                 h->snap_pending = true;          // (made by the first launch: launch_window)
                 h->safe_M = h->M; h->safe_M_app = h->M_app; h->safe_g_done = h->g_done;
             }
-            demcz_handle::RunCall rcall{g_from, g_to, gamma, temperature != nullptr, {}};
-            if (temperature) rcall.temperature.assign(temperature, temperature + G);
-            h->live_log.push_back(std::move(rcall));
+            log_run_call(h, g_from, g_to, gamma, temperature);
         }
     }
     // demcz_set_kernel_timing: ONE event pair around the back-to-back window launches of this call (an event
@@ -2824,64 +2834,34 @@ extern "C" int32_t demcz_run(demcz_handle* h, int64_t g_from, int64_t g_to, doub
         HIPCHK(h, hipEventCreate(&tev.b));
         HIPCHK(h, hipEventRecord(tev.a, h->stream));
     }
-    while (g <= g_to) {
-        const int64_t next_boundary = ((g - 1) / K + 1) * K;      // first multiple of K that is >= g
-        // Synchronous schedule: a launch ends at the next K boundary, the kernel boundary is the
-        // grid-wide barrier before the new rows are drawn from.  Deferred schedule: nothing appended
-        // inside a batch becomes visible inside it, so one launch covers the rest of the batch.
-        int64_t w_end = std::min(next_boundary, g_to);
-        if (E > 0 && !h->external_append) {
-            const int64_t jn = next_boundary / K, J = ((jn + E - 1) / E) * E;
-            w_end = std::min(J * (int64_t)K, g_to);
-        }
-        // Split layout on one GPU: the launch runs on through the boundaries; waves hand the appended rows
-        // to each other inside it (LIVE, demcz_kernels_pc.h), so the schedule is still the synchronous one.
-        int64_t live_max = live_span(h);
-        h->dual_now = false;
-        if (h->ps_dual) {
-            // A two-chain handle runs its REGULAR launches (start, boundary distance and length multiples of five; everything
-            // reachable through the arena) on window_kernel_ps2d; anything else takes the general kernel, one chain per wave, and
-            // -- twice the waves: they would not all be resident -- never across a K boundary.
-            const int64_t tb0 = next_boundary - g + 1, rest = g_to - g + 1;
-            const bool temp_ok = !temperature || temp_in_arena;
-            const bool hist_ok = !hist || (double)h->cfg.N * (h->cfg.d + 1) * (double)h->cfg.Gcap * 8.0 < 4293918720.0;
-            const bool reg = K % PS2_R == 0 && tb0 % PS2_R == 0 && rest >= PS2_R && temp_ok && hist_ok && h->arena && h->rec_in_arena;
-            if (reg) {
-                h->dual_now = true;
-                if (live_max > 0) live_max = std::max<int64_t>((std::min(live_max, rest) / PS2_R) * PS2_R, PS2_R);
-                else w_end = g + ((w_end - g + 1) / PS2_R) * PS2_R - 1;       // (a K-window cut short by the call's end: whole passes only)
-            } else {
-                live_max = 0;
-            }
-        }
-        if (live_max > 0) {
-            // How far this launch goes: as far as the records allow -- but no further than the draws that ARE there, where the
-            // launch before prepared fewer than that (a call longer than the last one); and a launch whose draws have to be made
-            // first, with nothing to run beside (the first of a run), stays short: its producer is serial time
-            // (64 MiB of records, the span of every launch until round 3f; profiles/r03f_launch_span.txt).
-            int64_t n = std::min(live_max, g_to - g + 1);
-            const auto& dc = h->rec_desc[h->rec_cur];
-            const int64_t rows_v = h->cfg.N * (peer ? shards : 1);      // (live: immediate visibility; all shards' rows with peers)
-            const int32_t boff = (int32_t)(K - (next_boundary - g + 1));
-            const bool ready = dc.valid && dc.g_first == g + h->rng_offset && dc.M == h->M && dc.rows == rows_v && dc.boff == boff;
-            if (ready && dc.ngen >= K) {
-                if (dc.ngen < n) n = std::max<int64_t>((dc.ngen / K) * K, K);
-            } else {
-                const int64_t per_gen = rec_fields(h) * h->cfg.N * (int64_t)sizeof(double);
-                const int64_t cold = std::max<int64_t>(K, ((int64_t)((h->ps_dual ? 2 * COLD_REC_MIB : COLD_REC_MIB) << 20) / per_gen / K) * K);
-                n = std::min(n, cold);
-            }
-            if (h->dual_now) n = std::max<int64_t>((n / PS2_R) * PS2_R, PS2_R);
-            w_end = g + n - 1;
-        }
+    // what the schedule of this call rests on (plan_launch, demcz_run_plan.h)
+    RunFacts F;
+    F.K = K; F.E = E; F.external_append = h->external_append;
+    F.N = h->cfg.N; F.shards = shards; F.peer = peer;
+    F.g_to = g_to; F.G = G; F.rng_offset = h->rng_offset;
+    F.split = h->lanes == DEMCZ_LAYOUT_SPLIT; F.hist = hist;
+    F.two_chain = h->ps_dual; F.R = PS2_R;
+    F.temp_in_arena = !temperature || temp_in_arena;
+    F.hist_32bit = hist_offsets_32bit(h->cfg.N, h->cfg.d, h->cfg.Gcap);
+    F.arena = h->arena;
+    F.cold_limit = cold_start_limit(K, rec_fields(h) * h->cfg.N * (int64_t)sizeof(double), h->ps_dual);
+    F.next_hint = hints.next_ngen;
+    // (DEMCZ_FORCE_LIVE_KERNEL=1, diagnosis only: the LIVE instantiation also for launches with no boundary inside -- what the
+    //  instantiation itself costs, scripts/live_fixed_cost.py)
+    static const bool force_live = getenv("DEMCZ_FORCE_LIVE_KERNEL") != nullptr;
+    F.force_live = force_live;
+    for (int64_t g = g_from; g <= g_to;) {
+        F.rec_in_arena = h->rec_in_arena;         // (pc_prepare moves the buffers out of the arena should a caller outrun what was reserved)
+        const LaunchPlan lp = plan_launch(F, g, live_span(h), h->M, h->M_app, h->rec_desc[h->rec_cur], h->pending);
+        const int64_t w_end = lp.w_end, nbound = lp.nbound;
+        h->dual_now = lp.dual;
         int32_t rc = admit_pending(h, g);
         if (rc) return rc;
-        const int64_t nbound = w_end / K - (g - 1) / K;           // boundaries inside this launch
         P.M = h->M;
         P.M_append = h->M_app;
         P.g_first = g + h->rng_offset;      // only positions the Philox streams
         P.ngen = (int32_t)(w_end - g + 1);
-        P.to_boundary = (int32_t)(next_boundary - g + 1);
+        P.to_boundary = (int32_t)lp.to_boundary;
         P.slot_first = hist ? (g - h->g0 - 1) : 0;
         P.temperature = temperature ? (temp_in_arena ? h->arena_temp : h->dtemp) + (g - g_from) : nullptr;
         P.do_append = (nbound > 0 && kernel_appends) ? 1 : 0;
@@ -2895,31 +2875,11 @@ extern "C" int32_t demcz_run(demcz_handle* h, int64_t g_from, int64_t g_to, doub
             }
             P.snap = h->d_send[h->batch_buf] + (size_t)h->batch_cnt * h->cfg.N * h->cfg.d;
         }
-        if (h->lanes == DEMCZ_LAYOUT_SPLIT) {
-            // what the launch after this one will be, so that this launch's producer half can prepare
-            // its draws: it starts at w_end + 1, runs to its own boundary / batch end / span, and sees ...
-            const int64_t ng = w_end + 1;
-            const int64_t nb1 = ((ng - 1) / K + 1) * (int64_t)K;       // its first boundary
-            int64_t nend = nb1;
-            if (E > 0 && !h->external_append) nend = ((nend / K + E - 1) / E) * E * (int64_t)K;
-            int64_t nM = h->M, nn = nend - ng + 1;
-            const int64_t rows_n = h->cfg.N * shards;
-            // a next call is taken to be as long as this one -- unless demcz_run_checked knows what follows
-            if (live_max > 0) nn = std::min(live_max, (w_end < g_to) ? g_to - w_end : (h->plan_next > 0 ? h->plan_next : G));
-            if (h->external_append) nn = 0;                      // the caller appends: M is not ours to predict
-            else if (E == 0) nM = h->M_app + nbound * rows_n;                    // ... the rows appended now
-            else for (const auto& pe : h->pending) if (pe.visible_from <= ng) nM = pe.M_after;   // ... or admitted by then
-            const int64_t vis_rows = (E == 0) ? rows_n : 0;      // rows that join per boundary passed inside a launch
-            const int32_t nboff = (int32_t)(K - (nb1 - ng + 1));
-            rc = pc_prepare(h, P, vis_rows, ng + h->rng_offset, nn, nM, vis_rows, nboff);
+        if (F.split) {
+            rc = pc_prepare(h, P, lp);
             if (rc) return rc;
         }
-        // boundaries whose rows generations of this same launch draw from.  With peers EVERY launch is of the LIVE kind: the rows
-        // of the boundary that ended the launch before may still be on their way from another replica's publisher
-        // (DEMCZ_FORCE_LIVE_KERNEL=1, diagnosis only: the LIVE instantiation also for launches with no boundary inside -- what the
-        //  instantiation itself costs, scripts/live_fixed_cost.py)
-        static const bool force_live = getenv("DEMCZ_FORCE_LIVE_KERNEL") != nullptr;
-        const bool live = live_max > 0 && (((w_end - 1) / K - (g - 1) / K) > 0 || peer || force_live);
+        const bool live = lp.live;
         P.live_err = h->d_live_err;
         P.live_spin_limit = h->live_spin_limit ? (int32_t)h->live_spin_limit : LIVE_SPIN_LIMIT;
         if (h->live_fault_polls > 0 && g >= h->live_fault_g) P.live_spin_limit = h->live_fault_polls;
@@ -2947,13 +2907,11 @@ extern "C" int32_t demcz_run(demcz_handle* h, int64_t g_from, int64_t g_to, doub
                 if (kernel_appends) { h->M_app += nbound * rows; h->M = h->M_app; }
                 else { rc = append_after_window(h); if (rc) return rc; }
             } else {
-                // boundary j belongs to the batch closing at J = ceil(j/E)*E; its rows are drawn from
-                // generation (J + E)*K + 1 on -- the same rule on every rank and for any sharding
                 for (int64_t j = (g - 1) / K + 1; j <= w_end / K; ++j) {
-                    const int64_t J = ((j + E - 1) / E) * E;
+                    const int64_t J = lag_batch_of(j, E);
                     h->M_app += rows;
                     if (h->batch_J != J) {
-                        h->pending.push_back({(J + E) * (int64_t)K + 1, h->M_app, nullptr});
+                        h->pending.push_back({lag_visible_from(J, E, K), h->M_app, nullptr});
                         h->batch_J = J;
                     } else {
                         h->pending.back().M_after = h->M_app;
@@ -2971,7 +2929,7 @@ extern "C" int32_t demcz_run(demcz_handle* h, int64_t g_from, int64_t g_to, doub
         HIPCHK(h, hipEventRecord(tev.b, h->stream));
         h->after_launch_ev = tev.b;
         h->timed.emplace_back(tev.a, tev.b);
-        h->timed_slabs.push_back(std::max(h->bracket_slabs, 1));
+        h->timed_slabs.push_back(std::max(hints.bracket_slabs, 1));
         tev.a = tev.b = nullptr;
         h->timed_launches += timed_launches;
     }
@@ -2981,6 +2939,12 @@ extern "C" int32_t demcz_run(demcz_handle* h, int64_t g_from, int64_t g_to, doub
     }
     h->g_done = g_to;
     return DEMCZ_OK;
+}
+
+extern "C" int32_t demcz_run(demcz_handle* h, int64_t g_from, int64_t g_to, double gamma, const double* temperature)
+{
+    NOT_DERIVED(h);
+    return run_call(h, g_from, g_to, gamma, temperature, RunHints{});
 }
 
 extern "C" int32_t demcz_synchronize(demcz_handle* h)
@@ -4749,18 +4713,17 @@ static int32_t run_checked_body(demcz_handle* h, int64_t g_from, int64_t g_to, d
         return cut;
     };
     while (g <= g_to && rc == DEMCZ_OK) {
-        int64_t nxt = std::min(g_to, ((g - 1) / every + 1) * every);
+        int64_t nxt = std::min(g_to, slab_end_at_or_after(g, every));
+        RunHints hints;
         if (grouped) {
             const int64_t ls = live_span(h);
             const int64_t span = ls > 0 ? ls : INT64_MAX;
             nxt = slab_group_end(g, g_to, every, span, cut_now(), max_slabs);
-            h->bracket_slabs = (int32_t)(slab_ends_in(g, nxt, every) + (nxt % every != 0 ? 1 : 0));
+            hints.bracket_slabs = (int32_t)(slab_ends_in(g, nxt, every) + (nxt % every != 0 ? 1 : 0));
             // (what the call's last launch prepares draws for: the first launch of the next group)
-            h->plan_next = nxt < g_to ? std::min<int64_t>(span, slab_group_end(nxt + 1, g_to, every, span, cut_now(), max_slabs) - nxt) : 0;
+            hints.next_ngen = nxt < g_to ? std::min<int64_t>(span, slab_group_end(nxt + 1, g_to, every, span, cut_now(), max_slabs) - nxt) : 0;
         }
-        if (!ahead) rc = demcz_run(h, g, nxt, gamma, temperature ? temperature + (g - g_from) : nullptr);
-        h->bracket_slabs = 1;
-        h->plan_next = 0;
+        if (!ahead) rc = run_call(h, g, nxt, gamma, temperature ? temperature + (g - g_from) : nullptr, hints);
         ahead = false;
         if (rc) break;
         // the checks of the slab ends inside g..nxt (demcz.jl:39-41): windows c0 - every + 1 .. c0, c0 + 1 .. c0 + every, ...
@@ -4784,7 +4747,7 @@ static int32_t run_checked_body(demcz_handle* h, int64_t g_from, int64_t g_to, d
                         break;
                     }
                     M_before = h->M_app;
-                    const int64_t nn = std::min(g_to, (nxt / every + 1) * every);
+                    const int64_t nn = std::min(g_to, slab_end_at_or_after(nxt + 1, every));
                     rc = demcz_run(h, nxt + 1, nn, gamma, nullptr);
                     if (rc) break;
                     ahead = true;
