@@ -121,20 +121,22 @@ def py_fma(a, b, c):
         return math.inf if s > 0 else -math.inf
 
 
-def oracle_sample_logobj(O, logobj, Z0, N, K, G, blocks, eps, gamma, seed, temperature=None):
+def oracle_sample_logobj(O, logobj, Z0, N, K, G, blocks, eps, gamma, seed, temperature=None, X0=None, lp0=None, g_from=1):
     """The oracle's generation loop (synchronous schedule) around a Python log-density: of every block-step only what does not
     depend on the target is taken from the oracle (O.block_step on a problem with a built-in target: the proposal and log u, the
     draw contract's bits); logobj is evaluated on a list of Python floats, and the accept test log u < (lp' - lp) [/ T] and the
     per-generation count (lp_after - lp_before) != 0 are made in NumPy float64, so that +-inf and NaN behave as IEEE says.
-    Returns oracle_sample's dict, and `proposed` (N, G, blocks): the log-density of every proposal, accepted or not."""
+    Returns oracle_sample's dict, and `proposed` (N, G, blocks): the log-density of every proposal, accepted or not.
+    X0, lp0, g_from: carry a run on -- Z0 is then the archive as it stands, X0 / lp0 the chains, and the G generations are
+    g_from .. g_from + G - 1 (temperature[0] is generation g_from's)."""
     Z0 = np.asarray(Z0, dtype=np.float64)
     M0, d = Z0.shape
-    Mcap = M0 + -(-N * G // K)
+    Mcap = M0 + -(-N * G // K) + (N if g_from > 1 else 0)
     blocks = [list(range(d))] if blocks is None else [list(b) for b in blocks]
     prob = O.Problem(N, d, K, Mcap, eps, seed, blocks=blocks, target=dict(kind="iso_quad", mu=np.zeros(d)))
     f = lambda x: np.float64(logobj([float(v) for v in x]))
-    X = np.array(Z0[M0 - N:], order="F")
-    lp = np.array([f(X[c]) for c in range(N)], dtype=np.float64)
+    X = np.array(Z0[M0 - N:] if X0 is None else X0, order="F")
+    lp = np.array([f(X[c]) for c in range(N)], dtype=np.float64) if lp0 is None else np.array(lp0, dtype=np.float64)
     Z = np.zeros((Mcap, d), order="F")
     Z[:M0] = Z0
     M = M0
@@ -143,22 +145,22 @@ def oracle_sample_logobj(O, logobj, Z0, N, K, G, blocks, eps, gamma, seed, tempe
     changed = np.zeros(G, dtype=np.int64)
     proposed = np.zeros((N, G, len(blocks)))
     with np.errstate(all="ignore"):
-        for g in range(1, G + 1):
-            T = None if temperature is None else np.float64(temperature[g - 1])
+        for g in range(g_from, g_from + G):
+            T = None if temperature is None else np.float64(temperature[g - g_from])
             for c in range(N):
                 x, lpc = X[c].copy(), lp[c]
                 for ib in range(len(blocks)):
                     s = O.block_step(prob, Z, M, c, g, ib, gamma, x, 0.0)
-                    lpp = proposed[c, g - 1, ib] = f(s["xprop"])
+                    lpp = proposed[c, g - g_from, ib] = f(s["xprop"])
                     dlt = lpp - lpc
                     if T is not None:
                         dlt = dlt / T
                     if np.float64(s["logu"]) < dlt:
                         x, lpc = s["xprop"].copy(), lpp
                 if (lpc - lp[c]) != 0:
-                    changed[g - 1] += 1
+                    changed[g - g_from] += 1
                 X[c], lp[c] = x, lpc
-            chain[:, :, g - 1], lobj[:, g - 1] = X, lp
+            chain[:, :, g - g_from], lobj[:, g - g_from] = X, lp
             if g % K == 0:
                 Z[M:M + N] = X
                 M += N

@@ -41,7 +41,10 @@ def test_flipped_switches_are_bit_identical_to_the_oracle():
            "tests/test_gpu_dual.py", "tests/test_gpu_live.py::test_forced_handoff_timeout_is_redone_bit_exact",
            "tests/test_gpu_parity.py::test_regression_target_any_dimension_sixteen_lanes",
            "tests/test_gpu_small_wave.py::test_one_chain_per_wave_every_dimension_every_form",
-           "tests/test_gpu_small_wave.py::test_two_chains_per_wave_every_dimension_every_form"]
+           "tests/test_gpu_small_wave.py::test_two_chains_per_wave_every_dimension_every_form",
+           # (MLB_DPP_RECORD = 1, every lane fetching its own record entry: the block kernels of every structure, QB = 5 in all its forms)
+           "tests/test_gpu_block_forms.py::test_split_block_kernels_every_structure_every_form",
+           "tests/test_gpu_block_forms.py::test_fused_block_kernels_every_structure_every_form"]
     r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider"] + sel, cwd=str(ROOT), env=env,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-1000:])
