@@ -53,6 +53,8 @@ SYMBOLS = [
     "demcz_quantile_plan", "demcz_select_counts", "demcz_select_step", "demcz_quantile_finish", "demcz_quantiles",
     "demcz_quantiles_array", "demcz_best", "demcz_best_array",
     "demcz_derive_check", "demcz_derive", "demcz_derive_array",
+    "demcz_rank_to_z", "demcz_rank_normalize", "demcz_rank_normalize_array", "demcz_indicator_le", "demcz_rank_diagnostics",
+    "demcz_rank_diagnostics_array",
 ]
 
 
@@ -213,6 +215,12 @@ def load():
     L.demcz_derive.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_char_p, C.c_char_p, _dp, C.c_int64, C.POINTER(C.c_void_p)]
     L.demcz_derive_array.argtypes = [C.c_int32, _dp, _dp, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_char_p, C.c_char_p, _dp,
                                      C.c_int64, C.POINTER(C.c_void_p)]
+    L.demcz_rank_to_z.argtypes = [C.c_int64, _dp, C.c_int64, _dp]
+    L.demcz_rank_normalize.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, _dp, C.POINTER(C.c_void_p)]
+    L.demcz_rank_normalize_array.argtypes = [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int64, C.c_int32, _dp, C.POINTER(C.c_void_p)]
+    L.demcz_indicator_le.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, _dp, C.POINTER(C.c_void_p)]
+    L.demcz_rank_diagnostics.argtypes = [C.c_void_p, C.c_int64, C.c_int64, _dp, _dp, _dp]
+    L.demcz_rank_diagnostics_array.argtypes = [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int64, _dp, _dp, _dp]
     L.demcz_get_archive_pinned.argtypes =[C.c_void_p, C.POINTER(C.c_void_p), _lp]
     L.demcz_get_kernel_time_series.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _ip]
     L.demcz_set_comm_timeout.argtypes = [C.c_void_p, C.c_int64]

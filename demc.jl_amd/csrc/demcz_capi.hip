@@ -7,6 +7,7 @@
 #include "demcz_kernels_acf.h"
 #include "demcz_kernels_sel.h"
 #include "demcz_select_host.h"
+#include "demcz_kernels_rank.h"
 #include "demcz_slab_plan.h"
 #include "demcz_run_plan.h"
 #include "demcz_kernels_ml.h"
@@ -4514,7 +4515,8 @@ extern "C" int32_t demcz_derive_check(int32_t d, int32_t m, const char* source, 
 namespace {
 // The derived history of N x m x w values on `device`, generations g0 + 1 .. g0 + w, with `data` copied into memory it owns:
 // the ScratchHandle shape on the heap.  On failure everything made so far is freed, nullptr is returned and `why` says what failed.
-demcz_handle* derived_create(int device, int64_t N, int m, int64_t w, int64_t g0, const double* data, int64_t ndata, std::string& why)
+demcz_handle* derived_create(int device, int64_t N, int m, int64_t w, int64_t g0, const double* data, int64_t ndata, std::string& why,
+                             const char* who = "demcz_derive")
 {
     demcz_handle* dh = new demcz_handle;
     dh->cfg.N = N; dh->cfg.d = m; dh->cfg.Gcap = w; dh->cfg.device_id = device; dh->cfg.nobs = ndata;
@@ -4529,7 +4531,7 @@ demcz_handle* derived_create(int device, int64_t N, int m, int64_t w, int64_t g0
     if (e == hipSuccess) { what = "the upload of the program's data"; e = hipStreamSynchronize(dh->stream); }
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        why = std::string("demcz_derive: ") + what + ": " + hipGetErrorString(e);
+        why = std::string(who) + ": " + what + ": " + hipGetErrorString(e);
         free_all(dh);
         delete dh;
         return nullptr;
@@ -4600,6 +4602,282 @@ extern "C" int32_t demcz_derive_array(int32_t device_id, const double* chain, co
     rc = s.open(device_id, N, d, G, chain, log_obj);
     if (rc) return diag_fail(s, rc);
     return diag_fail(s, derive_from(&s.h, 1, G, m, source, options, data, ndata, derived));
+}
+
+// ---- rank-normalised diagnostics (K10, demcz_kernels_rank.h): average ranks, normal scores, indicator columns -----------------
+namespace {
+// Everything a ranking needs besides the two key buffers, carved from ONE pool allocation so that there is one thing to free.
+struct RankScratch {
+    void* base = nullptr;
+    uint64_t *buf0, *buf1;
+    unsigned long long *hist, *nan;
+    unsigned int* tcount;
+    int* info;                      // [RANK_DIGITS + 1][d]: per pass the source buffer of each parameter or -1; last row: where it ends
+    unsigned int* dbase;            // [RANK_DIGITS][d][256]: keys of the parameter with a smaller digit in that pass
+    double* center;
+};
+
+int32_t rank_refuse_sharded(demcz_handle* h, const char* who)
+{
+    if (h->comm && h->nranks > 1)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": a rank needs the draws of every shard: gather the window with "
+                                                   "demcz_get_history on every rank and use the _array form on the whole");
+    return DEMCZ_OK;
+}
+
+// demcz_rank_normalize on a source that holds an N x d x Gcap history (a sampling handle, a derived history, a ScratchHandle)
+int32_t rank_from(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t mode, const double* center, demcz_handle** ranked)
+{
+    const char* who = "demcz_rank_normalize";
+    if (mode != DEMCZ_RANK_Z && mode != DEMCZ_RANK_AVERAGE)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_rank_normalize: mode is DEMCZ_RANK_Z or DEMCZ_RANK_AVERAGE");
+    int32_t rc = rank_refuse_sharded(h, who);
+    if (rc) return rc;
+    rc = check_hist_range(h, g_from, g_to, who);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device_id));
+    rc = live_verify(h);
+    if (rc) return rc;
+    const int64_t N = h->cfg.N, w = g_to - g_from + 1, s0 = g_from - h->g0 - 1, S = N * w;
+    const int d = h->cfg.d;
+    if (S >= ((int64_t)1 << 31) || d > 65535)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_rank_normalize: at most 2^31 - 1 draws per parameter and 65535 parameters");
+    rc = quiesce_all(h);                        // (the allocations below may synchronise the device)
+    if (rc) return rc;
+    const int64_t ntiles = (S + RANK_TILE - 1) / RANK_TILE;
+    std::string err;
+    demcz_handle* dh = derived_create(h->cfg.device_id, N, d, w, g_from - 1, nullptr, 0, err, who);
+    if (!dh) return fail(h, DEMCZ_ERR_HIP, err);
+    // [buf0 | buf1 | hist | nan | center | tcount | dbase | info], every piece a multiple of 8 bytes
+    const size_t nkeys = (size_t)d * S, nhist = (size_t)d * RANK_DIGITS * 256, ntc = (size_t)d * ntiles * 256,
+                 ninfo = (size_t)(RANK_DIGITS + 1) * d;
+    const size_t bytes = 2 * nkeys * 8 + nhist * 8 + (size_t)d * 8 + (size_t)d * 8 + (ntc * 4 + 7) / 8 * 8 + nhist * 4 + (ninfo * 4 + 7) / 8 * 8;
+    RankScratch sc;
+    hipError_t e = dev_malloc(h->cfg.device_id, &sc.base, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        free_all(dh);
+        delete dh;
+        return fail(h, DEMCZ_ERR_HIP, std::string(who) + ": the sort's scratch (two key buffers of N w d words): " + hipGetErrorString(e));
+    }
+    sc.buf0 = static_cast<uint64_t*>(sc.base);
+    sc.buf1 = sc.buf0 + nkeys;
+    sc.hist = reinterpret_cast<unsigned long long*>(sc.buf1 + nkeys);
+    sc.nan = sc.hist + nhist;
+    sc.center = reinterpret_cast<double*>(sc.nan + d);
+    sc.tcount = reinterpret_cast<unsigned int*>(sc.center + d);
+    sc.dbase = reinterpret_cast<unsigned int*>(reinterpret_cast<char*>(sc.tcount) + (ntc * 4 + 7) / 8 * 8);
+    sc.info = reinterpret_cast<int*>(sc.dbase + nhist);              // (nhist = d * 8 * 256 is even)
+
+    std::vector<double> hcenter;                // (host copies live until the stream is synchronised)
+    std::vector<unsigned long long> hhist(nhist);
+    std::vector<int> hinfo(ninfo, -1);
+    std::vector<unsigned int> hbase(nhist);
+    auto body = [&]() -> int32_t {
+        const double* dcenter = nullptr;
+        if (center) {
+            hcenter.assign(center, center + d);
+            HIPCHK(h, hipMemcpyAsync(sc.center, hcenter.data(), (size_t)d * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            dcenter = sc.center;
+        }
+        HIPCHK(h, hipMemsetAsync(sc.hist, 0, (nhist + d) * sizeof(unsigned long long), h->stream));
+        const dim3 grid((unsigned)ntiles, (unsigned)d);
+        hipLaunchKernelGGL(rank_keys_kernel, grid, dim3(RANK_BS), 0, h->stream, (const double*)h->dchain, N, d, s0, S, dcenter, sc.buf0,
+                           sc.hist, sc.nan);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(hhist.data(), sc.hist, nhist * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+        int32_t r2 = sync_stream(h, h->stream, who);
+        if (r2) return r2;
+        // a digit in which all S keys of a parameter agree leaves their order as it is: that parameter sits the pass out
+        std::vector<int> cur((size_t)d, 0);
+        bool any[RANK_DIGITS] = {};
+        for (int b = 0; b < RANK_DIGITS; ++b)
+            for (int p = 0; p < d; ++p) {
+                const unsigned long long* hp = hhist.data() + ((size_t)p * RANK_DIGITS + b) * 256;
+                unsigned int* bp = hbase.data() + ((size_t)b * d + p) * 256;
+                bool one_bin = false;
+                unsigned long long below = 0;
+                for (int k = 0; k < 256; ++k) {
+                    one_bin = one_bin || hp[k] == (unsigned long long)S;
+                    bp[k] = (unsigned int)below;
+                    below += hp[k];
+                }
+                if (one_bin) continue;
+                hinfo[(size_t)b * d + p] = cur[p];
+                cur[p] ^= 1;
+                any[b] = true;
+            }
+        for (int p = 0; p < d; ++p) hinfo[(size_t)RANK_DIGITS * d + p] = cur[p];
+        HIPCHK(h, hipMemcpyAsync(sc.info, hinfo.data(), ninfo * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(sc.dbase, hbase.data(), nhist * sizeof(unsigned int), hipMemcpyHostToDevice, h->stream));
+        for (int b = 0; b < RANK_DIGITS; ++b) {
+            if (!any[b]) continue;
+            const int* info = sc.info + (size_t)b * d;
+            hipLaunchKernelGGL(rank_tile_count_kernel, grid, dim3(RANK_BS), 0, h->stream, (const uint64_t*)sc.buf0, (const uint64_t*)sc.buf1,
+                               S, ntiles, 8 * b, info, sc.tcount);
+            hipLaunchKernelGGL(rank_tile_scan_kernel, dim3(256, (unsigned)d), dim3(256), 0, h->stream, ntiles, info,
+                               (const unsigned int*)(sc.dbase + (size_t)b * d * 256), sc.tcount);
+            hipLaunchKernelGGL(rank_scatter_kernel, grid, dim3(RANK_BS), 0, h->stream, sc.buf0, sc.buf1, S, ntiles, 8 * b, info,
+                               (const unsigned int*)sc.tcount);
+        }
+        hipLaunchKernelGGL(rank_score_kernel, dim3((unsigned)((S + RANK_BS - 1) / RANK_BS), (unsigned)d), dim3(RANK_BS), 0, h->stream,
+                           (const double*)h->dchain, N, d, s0, S, dcenter, (const uint64_t*)sc.buf0, (const uint64_t*)sc.buf1,
+                           (const int*)(sc.info + (size_t)RANK_DIGITS * d), (const unsigned long long*)sc.nan, (int)mode, dh->dchain);
+        HIPCHK(h, hipGetLastError());
+        return sync_stream(h, h->stream, who);
+    };
+    rc = body();
+    if (rc == DEMCZ_ERR_HIP) (void)hipDeviceSynchronize();          // (a kernel may still be writing what is about to be freed)
+    (void)dev_free(h->cfg.device_id, sc.base);
+    if (rc) {
+        free_all(dh);
+        delete dh;
+        return rc;
+    }
+    *ranked = dh;
+    return DEMCZ_OK;
+}
+
+// demcz_indicator_le on such a source: a map per draw, local to the handle's own chains
+int32_t indicator_from(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t nthr, const double* thr, demcz_handle** derived)
+{
+    const char* who = "demcz_indicator_le";
+    int32_t rc = check_hist_range(h, g_from, g_to, who);
+    if (rc) return rc;
+    if (nthr < 1 || nthr > 64 || (int64_t)h->cfg.d * nthr > 65535)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_indicator_le: 1 <= nthr <= 64 and d nthr <= 65535");
+    HIPCHK(h, hipSetDevice(h->cfg.device_id));
+    rc = live_verify(h);
+    if (rc) return rc;
+    rc = quiesce_all(h);
+    if (rc) return rc;
+    const int64_t N = h->cfg.N, w = g_to - g_from + 1, s0 = g_from - h->g0 - 1;
+    const int d = h->cfg.d, m = d * nthr;
+    const int64_t total = N * m * w;
+    std::string err;
+    demcz_handle* dh = derived_create(h->cfg.device_id, N, m, w, g_from - 1, thr, (int64_t)m, err, who);   // (the thresholds: its data)
+    if (!dh) return fail(h, DEMCZ_ERR_HIP, err);
+    const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 8192);
+    hipLaunchKernelGGL(indicator_le_kernel, dim3(blocks), dim3(256), 0, h->stream, (const double*)h->dchain, N, d, s0, total, (int)nthr,
+                       (const double*)dh->d_design, dh->dchain);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) h->err = std::string("demcz_indicator_le: launching indicator_le_kernel: ") + hipGetErrorString(e);
+    rc = (e != hipSuccess) ? DEMCZ_ERR_HIP : sync_stream(h, h->stream, who);
+    if (rc) {
+        if (rc == DEMCZ_ERR_HIP) (void)hipDeviceSynchronize();
+        free_all(dh);
+        delete dh;
+        return rc;
+    }
+    *derived = dh;
+    return DEMCZ_OK;
+}
+
+// a statistic of a derived history made on the way; its error message moves to the handle the caller holds
+int32_t rank_part(demcz_handle* h, demcz_handle* part, int32_t rc)
+{
+    if (rc) h->err = part->err;
+    return rc;
+}
+
+void rank_drop(demcz_handle* dh)
+{
+    if (!dh) return;
+    (void)demcz_destroy(dh);
+}
+
+int32_t rank_diagnostics_from(demcz_handle* h, int64_t g_from, int64_t g_to, double* rhat_rank, double* ess_bulk, double* ess_tail)
+{
+    const char* who = "demcz_rank_diagnostics";
+    int32_t rc = rank_refuse_sharded(h, who);
+    if (rc) return rc;
+    rc = check_hist_range(h, g_from, g_to, who);
+    if (rc) return rc;
+    if (g_to - g_from + 1 < 4) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_rank_diagnostics: window needs at least 4 generations");
+    const int d = h->cfg.d;
+    const double probs[3] = {0.05, 0.5, 0.95};
+    std::vector<double> q((size_t)3 * d), a((size_t)2 * d), b((size_t)d);
+    rc = demcz_quantiles(h, g_from, g_to, 3, probs, q.data(), nullptr, nullptr);
+    if (rc) return rc;
+    demcz_handle *zb = nullptr, *zf = nullptr, *ind = nullptr;
+    if (rhat_rank || ess_bulk) {
+        rc = rank_from(h, g_from, g_to, DEMCZ_RANK_Z, nullptr, &zb);
+        if (!rc && ess_bulk) rc = rank_part(h, zb, demcz_ess(zb, g_from, g_to, 0, ess_bulk, nullptr, nullptr, nullptr, nullptr));
+        if (!rc && rhat_rank) rc = rank_part(h, zb, demcz_rhat(zb, g_from, g_to, a.data()));
+        rank_drop(zb);
+        if (rc) return rc;
+    }
+    if (rhat_rank) {
+        rc = rank_from(h, g_from, g_to, DEMCZ_RANK_Z, q.data() + d, &zf);               // folded at the median
+        if (!rc) rc = rank_part(h, zf, demcz_rhat(zf, g_from, g_to, b.data()));
+        rank_drop(zf);
+        if (rc) return rc;
+        for (int p = 0; p < d; ++p)
+            rhat_rank[p] = (a[p] != a[p] || b[p] != b[p]) ? std::nan("") : std::max(a[p], b[p]);
+    }
+    if (ess_tail) {
+        std::vector<double> thr((size_t)2 * d);
+        for (int p = 0; p < d; ++p) { thr[p] = q[p]; thr[(size_t)d + p] = q[(size_t)2 * d + p]; }
+        rc = indicator_from(h, g_from, g_to, 2, thr.data(), &ind);
+        if (!rc) rc = rank_part(h, ind, demcz_ess(ind, g_from, g_to, 0, a.data(), nullptr, nullptr, nullptr, nullptr));
+        rank_drop(ind);
+        if (rc) return rc;
+        for (int p = 0; p < d; ++p) {
+            const double lo = a[p], hi = a[(size_t)d + p];
+            ess_tail[p] = (lo != lo || hi != hi) ? std::nan("") : std::min(lo, hi);
+        }
+    }
+    return DEMCZ_OK;
+}
+}  // namespace
+
+extern "C" int32_t demcz_rank_normalize(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t mode, const double* center,
+                                        demcz_handle** ranked)
+{
+    if (!h || !ranked) return DEMCZ_ERR_INVALID_ARGUMENT;
+    *ranked = nullptr;
+    DEADCHK(h);
+    return rank_from(h, g_from, g_to, mode, center, ranked);
+}
+
+extern "C" int32_t demcz_rank_normalize_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, int32_t mode,
+                                              const double* center, demcz_handle** ranked)
+{
+    if (!chain || !ranked) return DEMCZ_ERR_INVALID_ARGUMENT;
+    *ranked = nullptr;
+    ScratchHandle s;                            // (the upload: freed when this call returns, only the ranked history stays)
+    int32_t rc = s.open(device_id, N, d, G, chain, nullptr);
+    if (rc) return diag_fail(s, rc);
+    return diag_fail(s, rank_from(&s.h, 1, G, mode, center, ranked));
+}
+
+extern "C" int32_t demcz_indicator_le(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t nthr, const double* thr,
+                                      demcz_handle** derived)
+{
+    if (!h || !derived) return DEMCZ_ERR_INVALID_ARGUMENT;
+    *derived = nullptr;
+    if (!thr) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_indicator_le: thr is NULL");
+    DEADCHK(h);
+    return indicator_from(h, g_from, g_to, nthr, thr, derived);
+}
+
+extern "C" int32_t demcz_rank_diagnostics(demcz_handle* h, int64_t g_from, int64_t g_to, double* rhat_rank, double* ess_bulk,
+                                          double* ess_tail)
+{
+    if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
+    if (!rhat_rank && !ess_bulk && !ess_tail) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_rank_diagnostics: every output is NULL");
+    DEADCHK(h);
+    return rank_diagnostics_from(h, g_from, g_to, rhat_rank, ess_bulk, ess_tail);
+}
+
+extern "C" int32_t demcz_rank_diagnostics_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G,
+                                                double* rhat_rank, double* ess_bulk, double* ess_tail)
+{
+    if (!chain || (!rhat_rank && !ess_bulk && !ess_tail)) return DEMCZ_ERR_INVALID_ARGUMENT;
+    ScratchHandle s;
+    int32_t rc = s.open(device_id, N, d, G, chain, nullptr);
+    if (rc) return diag_fail(s, rc);
+    return diag_fail(s, rank_diagnostics_from(&s.h, 1, G, rhat_rank, ess_bulk, ess_tail));
 }
 
 extern "C" int32_t demcz_get_info(const demcz_handle* h, int64_t* M, int64_t* launches_window, int32_t* lanes_per_chain)

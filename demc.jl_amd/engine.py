@@ -41,6 +41,19 @@ def ess_from_sums(m, n, sums, between):
 Quantiles = namedtuple("Quantiles", "q lower upper")
 # the best draw of a window: max of log_obj, 0-based chain, generation, chain[chain, :, generation]
 Best = namedtuple("Best", "bestval chain generation bestpar")
+# per parameter: rank-normalised split R-hat (the larger of bulk and folded), bulk-ESS and tail-ESS (Vehtari et al. 2021)
+RankDiagnostics = namedtuple("RankDiagnostics", "rhat_rank ess_bulk ess_tail")
+
+
+def rank_to_z(r, S):
+    """demcz_rank_to_z (host code, no device): the normal scores of average ranks r (1 <= r <= S) among S draws, by the operation
+    sequence the device runs (Blom's offsets, Wichura's AS 241)."""
+    r = np.ascontiguousarray(r, dtype=np.float64)
+    z = np.empty(r.shape)
+    rc = _lib.load().demcz_rank_to_z(r.size, _lib.ptr(r), int(S), _lib.ptr(z))
+    if rc != 0:
+        raise DemczError(rc, "demcz_rank_to_z: 1 <= S < 2^50 and every rank in [1, S]")
+    return z
 
 
 def quantile_plan(S, probs):
@@ -204,10 +217,44 @@ class _HistoryStatistics:
         return DerivedHistory(self._L, out, self.N, program.m, int(g_from), int(g_to), program.names, getattr(self, "chain_id0", 0))
 
 
+    def rank_normalize(self, g_from, g_to, center=None, ranks=False):
+        """The normal scores of the exact average ranks of every draw of generations g_from..g_to among all the window's draws of
+        its parameter (demcz_rank_normalize): a ``DerivedHistory`` of d columns.  ``center`` (d values): rank
+        ``fabs(x - center)`` instead of x (the folded form).  ``ranks``: the average ranks themselves."""
+        ctr = None
+        if center is not None:
+            ctr = _lib.f64(center)
+            if ctr.shape != (self.d,):
+                raise ValueError("center must have d entries")
+        out = C.c_void_p()
+        self._chk(self._L.demcz_rank_normalize(self._h, int(g_from), int(g_to), 1 if ranks else 0, _lib.ptr(ctr), C.byref(out)))
+        return DerivedHistory(self._L, out, self.N, self.d, int(g_from), int(g_to), getattr(self, "names", None), getattr(self, "chain_id0", 0))
+
+    def indicator_le(self, g_from, g_to, thr):
+        """The indicators x <= thr of every draw of generations g_from..g_to (demcz_indicator_le): ``thr`` is (d,) or (d, nthr); a
+        ``DerivedHistory`` of d * nthr columns, column p + d * u holding parameter p against thr[p, u].  A NaN draw stays NaN."""
+        thr = np.array(thr, dtype=np.float64, order="F")
+        if thr.ndim == 1:
+            thr = thr.reshape(-1, 1, order="F")
+        if thr.ndim != 2 or thr.shape[0] != self.d:
+            raise ValueError("thr must be (d,) or (d, nthr)")
+        out = C.c_void_p()
+        self._chk(self._L.demcz_indicator_le(self._h, int(g_from), int(g_to), thr.shape[1], _lib.ptr(thr), C.byref(out)))
+        return DerivedHistory(self._L, out, self.N, self.d * thr.shape[1], int(g_from), int(g_to), None, getattr(self, "chain_id0", 0))
+
+    def rank_diagnostics(self, g_from, g_to):
+        """Rank-normalised split R-hat, bulk-ESS and tail-ESS per parameter over generations g_from..g_to (demcz_rank_diagnostics):
+        a RankDiagnostics tuple."""
+        out = RankDiagnostics(np.empty(self.d), np.empty(self.d), np.empty(self.d))
+        self._chk(self._L.demcz_rank_diagnostics(self._h, int(g_from), int(g_to), _lib.ptr(out.rhat_rank), _lib.ptr(out.ess_bulk),
+                                                 _lib.ptr(out.ess_tail)))
+        return out
+
+
 class DerivedHistory(_HistoryStatistics):
     """An N x m x w history of derived quantities on the device (``demcz_derive``): generations ``g_from..g_to``, numbered as in
-    the history it came from.  ``rhat``, ``rhat_partial``, ``autocov_sums``, ``ess``, ``select_counts``, ``quantiles``, ``mean_cov``
-    and ``derive`` are ``HipEngine``'s; nothing else of an engine applies (the library answers ERR_STATE)."""
+    the history it came from.  ``rhat``, ``rhat_partial``, ``autocov_sums``, ``ess``, ``select_counts``, ``quantiles``, ``mean_cov``,
+    ``derive``, ``rank_normalize``, ``indicator_le`` and ``rank_diagnostics`` are ``HipEngine``'s; nothing else of an engine applies (the library answers ERR_STATE)."""
 
     def __init__(self, L, handle, N, m, g_from, g_to, names=None, chain_id0=0):
         self._L, self._h = L, handle
@@ -249,9 +296,10 @@ class DerivedHistory(_HistoryStatistics):
         self._chk(self._L.demcz_get_history(self._h, g_from, g_to, _lib.ptr(out), None))
         return out
 
-    def summary(self, probs=None):
+    def summary(self, probs=None, rank_normalized=False):
         """What ``posterior_summary`` returns for a host array (mean, sd, mcse, ess, rhat, converged and, with ``probs``,
-        quantiles), computed from the handle with no download, plus ``names``."""
+        quantiles; with ``rank_normalized``, rhat_rank, ess_bulk and ess_tail), computed from the handle with no download, plus
+        ``names``."""
         mean, _ = self.mean_cov(self.g_from, self.g_to)
         e = self.ess(self.g_from, self.g_to)
         with np.errstate(all="ignore"):
@@ -259,6 +307,8 @@ class DerivedHistory(_HistoryStatistics):
                        rhat=self.rhat(self.g_from, self.g_to), converged=e.converged)
         if probs is not None:
             out["quantiles"] = self.quantiles(self.g_from, self.g_to, probs)
+        if rank_normalized:
+            out.update(self.rank_diagnostics(self.g_from, self.g_to)._asdict())
         out["names"] = self.names
         return out
 

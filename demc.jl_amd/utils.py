@@ -6,7 +6,8 @@ kernels the autostop uses.  ``flatten_chain`` is a pure re-indexing (utils.jl:22
 (utils.jl:120-125) finds the best draw on the device.  Plotting and ``save_res`` are not reproduced (dead code in Julia >= 1.0,
 SURVEY.md Q16).
 Beyond the reference: ``ess_chain``, ``autocov_chain``, ``quantile_chain`` and ``posterior_summary`` (effective sample size and
-quantiles by exact selection), and ``derive_chain`` (functions of the draws, evaluated on the device).
+quantiles by exact selection), ``derive_chain`` (functions of the draws, evaluated on the device), and
+``rank_normalize_chain`` / ``rank_diagnostics_chain`` (exact ranks on the device: rank-normalised R-hat, bulk- and tail-ESS).
 Checkpoints: the reference only resumes in memory (``prevrun=``); ``save_checkpoint`` /
 ``load_checkpoint`` put the same information in one ``.npz`` file.
 """
@@ -67,7 +68,7 @@ def mean_cov_chain(chain, Npop=None, Ngeneration=None, Npar=None, device_id=0):
 
 def ess_chain(chain, max_lag=0, device_id=0):
     """Effective sample size per parameter of an Npop x Npar x Ngeneration history (BDA3 section 11.5 / Stan, on the split chains
-    of Rhat_gelman, without rank normalisation): an ESS tuple (ess, tau, varplus, pairs, converged).  Not in the reference."""
+    of Rhat_gelman, on the values as they are; rank_diagnostics_chain has the rank-normalised bulk and tail ESS): an ESS tuple (ess, tau, varplus, pairs, converged).  Not in the reference."""
     from .engine import ESS
     chain = _lib.f64(chain, "F")
     N, d, G = chain.shape
@@ -128,10 +129,41 @@ def extract_best(mc, device_id=0):
     return bestval, np.array(mc.chain[c, :, g])
 
 
-def posterior_summary(chain, device_id=0, probs=None):
+def rank_normalize_chain(chain, center=None, ranks=False, device_id=0):
+    """The normal scores of the exact average ranks of every draw of an Npop x Npar x Ngeneration history among all draws of its
+    parameter -- a ``DerivedHistory`` on the device, generations 1..Ngeneration (demcz_rank_normalize_array).  ``center`` (Npar
+    values): rank ``fabs(x - center)``; ``ranks``: the average ranks themselves.  Not in the reference."""
+    from .engine import DerivedHistory
+    chain = _lib.f64(chain, "F")
+    N, d, G = chain.shape
+    ctr = None
+    if center is not None:
+        ctr = _lib.f64(center)
+        if ctr.shape != (d,):
+            raise ValueError("center must have Npar entries")
+    L = _lib.load()
+    out = C.c_void_p()
+    _chk(L.demcz_rank_normalize_array(device_id, _lib.ptr(chain), N, d, G, 1 if ranks else 0, _lib.ptr(ctr), C.byref(out)))
+    return DerivedHistory(L, out, N, d, 1, G)
+
+
+def rank_diagnostics_chain(chain, device_id=0):
+    """RankDiagnostics(rhat_rank, ess_bulk, ess_tail) per parameter of an Npop x Npar x Ngeneration history (Vehtari et al. 2021;
+    demcz_rank_diagnostics_array).  Not in the reference."""
+    from .engine import RankDiagnostics
+    chain = _lib.f64(chain, "F")
+    N, d, G = chain.shape
+    out = RankDiagnostics(np.empty(d), np.empty(d), np.empty(d))
+    _chk(_lib.load().demcz_rank_diagnostics_array(device_id, _lib.ptr(chain), N, d, G, _lib.ptr(out.rhat_rank), _lib.ptr(out.ess_bulk),
+                                                  _lib.ptr(out.ess_tail)))
+    return out
+
+
+def posterior_summary(chain, device_id=0, probs=None, rank_normalized=False):
     """Per parameter: mean, sd = sqrt(var+), mcse = sqrt(var+ / ess), ess, rhat, converged (of the ESS: 0 where the lags ran out
     and ess is an upper bound) -- mean_cov_chain, Rhat_gelman and ess_chain, all reduced on the device.  With `probs`, also
-    quantiles = quantile_chain(chain, probs): Npar x len(probs)."""
+    quantiles = quantile_chain(chain, probs): Npar x len(probs).  With `rank_normalized`, also rhat_rank, ess_bulk and ess_tail
+    (rank_diagnostics_chain)."""
     mean, _ = mean_cov_chain(chain, device_id=device_id)
     e = ess_chain(chain, device_id=device_id)
     with np.errstate(all="ignore"):
@@ -139,6 +171,8 @@ def posterior_summary(chain, device_id=0, probs=None):
                    rhat=Rhat_gelman(chain, device_id=device_id), converged=e.converged)
     if probs is not None:
         out["quantiles"] = quantile_chain(chain, probs, device_id=device_id)
+    if rank_normalized:
+        out.update(rank_diagnostics_chain(chain, device_id=device_id)._asdict())
     return out
 
 

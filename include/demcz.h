@@ -246,7 +246,8 @@ int32_t demcz_rhat_partial(demcz_handle* h, int64_t g_from, int64_t g_to, int32_
                            const double* grand, double* out);
 
 /* Effective sample size per parameter over generations g_from..g_to of the on-device history (BDA3 section 11.5 / the Stan
- * reference manual, without rank normalisation).  The split chains are demcz_rhat's: n = (g_to-g_from+1)/2
+ * reference manual, on the values as they are; for the rank-normalised bulk and tail ESS see demcz_rank_normalize and
+ * demcz_rank_diagnostics below).  The split chains are demcz_rhat's: n = (g_to-g_from+1)/2
  * samples each, m = 2 N of them; the window needs at least 4 generations.  With c_j(t) = 1/n sum_i (x_i - mean_j)(x_{i+t} - mean_j)
  * and A(t) = 1/m sum_j c_j(t): W = A(0) n/(n-1), var+ = A(0) + sum_j (mean_j - grand)^2 / (m-1), rho_t = 1 - (W - A(t))/var+
  * (rho_0 = 1), Geyer's initial monotone sequence over the pairs P_k = rho_2k + rho_2k+1 up to lag L (n-1, or min(n-1, max_lag)
@@ -471,8 +472,9 @@ int32_t demcz_best_array(int32_t device_id, const double* log_obj, int64_t N, in
  * The derived history is a demcz_handle with N chains, m "parameters" and w = g_to-g_from+1 generations that KEEP THEIR NUMBERS:
  * the statistics are asked for g_from..g_to or any window inside.  It owns its memory, outlives the handle it came from and is
  * freed by demcz_destroy.  It takes demcz_rhat, demcz_rhat_partial, demcz_autocov_sums, demcz_ess, demcz_select_counts,
- * demcz_quantiles, demcz_mean_cov, demcz_get_history with log_obj = NULL, demcz_synchronize, demcz_last_error, demcz_destroy and
- * demcz_derive (a derived history of a derived history; its logp is NaN).  Every other call that takes a handle returns
+ * demcz_quantiles, demcz_mean_cov, demcz_get_history with log_obj = NULL, demcz_synchronize, demcz_last_error, demcz_destroy,
+ * demcz_derive (a derived history of a derived history; its logp is NaN) and demcz_rank_normalize, demcz_indicator_le and
+ * demcz_rank_diagnostics (below).  Every other call that takes a handle returns
  * DEMCZ_ERR_STATE on it, with a message that says so. */
 int32_t demcz_derive_check(int32_t d, int32_t m, const char* source, const char* options);
 int32_t demcz_derive(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t m, const char* source, const char* options,
@@ -480,6 +482,46 @@ int32_t demcz_derive(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t m, c
 int32_t demcz_derive_array(int32_t device_id, const double* chain, const double* log_obj /* may be NULL */,
                            int64_t N, int32_t d, int64_t G, int32_t m, const char* source, const char* options,
                            const double* data, int64_t ndata, demcz_handle** derived);
+
+/* Rank-normalised diagnostics (Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021; not in the reference): rank-normalised split
+ * R-hat, bulk-ESS and tail-ESS, from the exact average rank of every draw among all S = N w draws of its parameter (DESIGN.md
+ * sections 3 and 4.14).  Per parameter p the value ranked is v = x (center NULL: bulk) or fabs(x - center[p]) (folded), then
+ * v + 0.0, so that -0.0 ranks as +0.0: ties are ties by ==, +-inf rank like any other value.  The average rank is
+ * r = less + (equal + 1) / 2 (1-based; less: draws with a smaller v, equal: draws with the same v, itself included), the normal
+ * score z = PPND16(u) (Wichura's AS 241) with Blom's u = (r - 0.375) / (S + 0.25), formed from the nearer end: z(S + 1 - r) is
+ * -z(r) to the bit.  A parameter whose window holds a NaN is NaN in every entry; the other parameters are unaffected.
+ *   demcz_rank_to_z           z[i] of average rank r[i] among S draws (1 <= r[i] <= S < 2^50): host code, no device -- the operation
+ *                             sequence the kernel runs, bit for bit.
+ *   demcz_rank_normalize      generations g_from..g_to of h's history into a DERIVED HISTORY (see demcz_derive) of N chains, d columns
+ *                             and generations that keep their numbers: the normal scores (DEMCZ_RANK_Z) or the average ranks
+ *                             themselves (DEMCZ_RANK_AVERAGE, the input of rank plots).  It takes every call a derived history
+ *                             takes; h may be a derived history itself.  Range and state errors are demcz_rhat's; a voided LIVE slab
+ *                             is redone first.  The sort works in 2 S d words of device memory that are returned before the call
+ *                             ends; a failed allocation is DEMCZ_ERR_HIP, nothing leaked.  *ranked is NULL on every failure.
+ *                             At most 2^31 - 1 draws per parameter.
+ *   demcz_indicator_le        the derived history of the d nthr columns out[c, p + d u, g] = (x[c, p, g] <= thr[p + d u]) ? 1 : 0; a NaN
+ *                             draw stays NaN.  1 <= nthr <= 64.  A map per draw: works on a sharded handle.
+ *   demcz_rank_diagnostics    rhat_rank = max(R-hat of the bulk scores, R-hat of the scores folded at the type-7 median), NaN if
+ *                             either is; ess_bulk = demcz_ess of the bulk scores; ess_tail = the smaller demcz_ess of the
+ *                             indicators x <= q(0.05) and x <= q(0.95) (type-7 quantiles, demcz_quantiles), NaN if either is.
+ *                             d values each; any may be NULL but not all.  The window needs at least 4 generations.
+ *   ..._array                 the same from a host array N x d x G column-major, generations 1..G.
+ * A rank needs the draws of every shard, and unlike the quantiles' counts there is no additive shard protocol for it here: on a
+ * handle whose communicator has more than one rank demcz_rank_normalize and demcz_rank_diagnostics return
+ * DEMCZ_ERR_INVALID_ARGUMENT -- gather the window with demcz_get_history and use the _array form. */
+#define DEMCZ_RANK_Z 0        /* normal scores */
+#define DEMCZ_RANK_AVERAGE 1  /* the average ranks themselves (rank plots) */
+int32_t demcz_rank_to_z(int64_t n, const double* r, int64_t S, double* z);
+int32_t demcz_rank_normalize(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t mode,
+                             const double* center /* d values or NULL */, demcz_handle** ranked);
+int32_t demcz_rank_normalize_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G,
+                                   int32_t mode, const double* center, demcz_handle** ranked);
+int32_t demcz_indicator_le(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t nthr,
+                           const double* thr /* d x nthr */, demcz_handle** derived);
+int32_t demcz_rank_diagnostics(demcz_handle* h, int64_t g_from, int64_t g_to,
+                               double* rhat_rank, double* ess_bulk, double* ess_tail);
+int32_t demcz_rank_diagnostics_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G,
+                                     double* rhat_rank, double* ess_bulk, double* ess_tail);
 
 /* Introspection for benchmarks and tests. */
 int32_t demcz_get_info(const demcz_handle* h, int64_t* M, int64_t* launches_window, int32_t* lanes_per_chain);

@@ -446,6 +446,51 @@ function derived_values(hd, N, m, g_from, g_to)
     v
 end
 
+# ---- rank-normalised diagnostics (Vehtari et al. 2021; not in the reference) ------------------------------------------------
+# normal scores of average ranks r (1 <= r <= S) among S draws: host code, the operation sequence the device runs
+function rank_to_z(r::Vector{Float64}, S::Integer)
+    z = zeros(length(r))
+    chk(ccall((:demcz_rank_to_z, libdemcz), Int32, (Int64, Ptr{Float64}, Int64, Ptr{Float64}), length(r), r, S, z))
+    z
+end
+# rank_normalize(h, g_from, g_to) -> the handle of a derived history (N x d x w) with the normal scores of the exact average
+# ranks of every draw among all draws of its parameter; center (d values): rank abs(x - center); ranks=true: the ranks themselves
+function rank_normalize(h, g_from, g_to; center::Union{Vector{Float64},Nothing}=nothing, ranks=false)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    chk(ccall((:demcz_rank_normalize, libdemcz), Int32, (Ptr{Cvoid}, Int64, Int64, Int32, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+              h, g_from, g_to, Int32(ranks ? 1 : 0), center === nothing ? C_NULL : center, out), h)
+    out[]
+end
+function rank_normalize_chain(chain::Array{Float64,3}; center::Union{Vector{Float64},Nothing}=nothing, ranks=false, device_id=0)
+    Npop, Npar, Ngeneration = size(chain)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    chk(ccall((:demcz_rank_normalize_array, libdemcz), Int32, (Int32, Ptr{Float64}, Int64, Int32, Int64, Int32, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+              device_id, chain, Npop, Npar, Ngeneration, Int32(ranks ? 1 : 0), center === nothing ? C_NULL : center, out))
+    out[]
+end
+# indicator_le(h, g_from, g_to, thr) -> derived history of the d * nthr columns (x <= thr[p, u]) ? 1 : 0; thr is d x nthr
+function indicator_le(h, g_from, g_to, thr::Matrix{Float64})
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    chk(ccall((:demcz_indicator_le, libdemcz), Int32, (Ptr{Cvoid}, Int64, Int64, Int32, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+              h, g_from, g_to, Int32(size(thr, 2)), thr, out), h)
+    out[]
+end
+# (rhat_rank, ess_bulk, ess_tail) per parameter: the larger of the bulk and the folded rank-normalised split R-hat, the ESS of
+# the bulk scores, the smaller ESS of the indicators x <= q(0.05) and x <= q(0.95)
+function rank_diagnostics(h, g_from, g_to, d)
+    r = zeros(d); eb = zeros(d); et = zeros(d)
+    chk(ccall((:demcz_rank_diagnostics, libdemcz), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+              h, g_from, g_to, r, eb, et), h)
+    (rhat_rank=r, ess_bulk=eb, ess_tail=et)
+end
+function rank_diagnostics_chain(chain::Array{Float64,3}; device_id=0)
+    Npop, Npar, Ngeneration = size(chain)
+    r = zeros(Npar); eb = zeros(Npar); et = zeros(Npar)
+    chk(ccall((:demcz_rank_diagnostics_array, libdemcz), Int32, (Int32, Ptr{Float64}, Int64, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+              device_id, chain, Npop, Npar, Ngeneration, r, eb, et))
+    (rhat_rank=r, ess_bulk=eb, ess_tail=et)
+end
+
 # ---- checkpoint: what a resumed run needs (the reference resumes in memory only, demcz.jl:18-22) ----------------------------
 struct Checkpoint
     prevrun::MC                 # last generation only: chain[:, :, end:end], log_obj[:, end:end], Xcurrent, log_objcurrent
