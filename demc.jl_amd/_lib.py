@@ -55,6 +55,7 @@ SYMBOLS = [
     "demcz_derive_check", "demcz_derive", "demcz_derive_array",
     "demcz_rank_to_z", "demcz_rank_normalize", "demcz_rank_normalize_array", "demcz_indicator_le", "demcz_rank_diagnostics",
     "demcz_rank_diagnostics_array",
+    "demcz_set_snooker", "demcz_get_snooker",
 ]
 
 
@@ -83,11 +84,11 @@ HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-W
 def sources() -> list:
     """The library's translation units: the C ABI with most kernels (demcz_capi.hip), the eight units that instantiate
     window_kernel_pw for every dimension from 6 to 32 (demcz_pw_inst_<g>.hip, csrc/demcz_pw_dispatch.h), the two with the
-    sixteen-lane regression kernels for every dimension from 2 to 28 (demcz_mlr_inst_<g>.hip, csrc/demcz_mlr_dispatch.h) and the
-    host code of program targets (demcz_program.hip: hipRTC, the kernel headers embedded as text)."""
+    sixteen-lane regression kernels for every dimension from 2 to 28 (demcz_mlr_inst_<g>.hip, csrc/demcz_mlr_dispatch.h), the one
+    with the snooker generation's kernels (demcz_snooker_inst.hip, csrc/demcz_kernels_snooker.h) and the host code of program targets (demcz_program.hip: hipRTC, the kernel headers embedded as text)."""
     csrc = PKG_DIR / "csrc"
     return ([csrc / "demcz_capi.hip"] + sorted(csrc.glob("demcz_pw_inst_*.hip")) + sorted(csrc.glob("demcz_mlr_inst_*.hip"))
-            + [csrc / "demcz_program.hip"])
+            + [csrc / "demcz_snooker_inst.hip", csrc / "demcz_program.hip"])
 
 
 def build_command(out: Path = LIB_PATH) -> list:
@@ -170,6 +171,8 @@ def load():
     L.demcz_append_rows.argtypes = [C.c_void_p, _dp, C.c_int64, C.c_int64]
     L.demcz_rhat_partial.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, _dp, _dp]
     L.demcz_set_rng_offset.argtypes = [C.c_void_p, C.c_int64]
+    L.demcz_set_snooker.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_double]
+    L.demcz_get_snooker.argtypes = [C.c_void_p, _ip, _dp, _dp, _lp]
     L.demcz_set_append_lag.argtypes = [C.c_void_p, C.c_int32]
     L.demcz_rhat_array.argtypes = [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int64, _dp]
     L.demcz_autocov_sums.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _dp]

@@ -16,6 +16,7 @@
 #include "demcz_kernels_ps.h"
 #include "demcz_kernels_ps2.h"
 #include "demcz_kernels_ps2d.h"
+#include "demcz_kernels_snooker.h"
 #include "demcz_pw_dispatch.h"
 #include "demcz_mlr_dispatch.h"
 #include "demcz_program.h"
@@ -163,7 +164,7 @@ enum SplitKind {
 // One window launch's kernel, as window_kernel_of() resolves it: everything that launches, sizes, counts or names a window kernel
 // reads this description and decides nothing about the instantiation itself.
 enum KernelArm { ARM_ONE_LANE, ARM_ML, ARM_ML_COOP, ARM_MLB, ARM_LR16, ARM_PC8, ARM_ML_REC, ARM_MLB_REC, ARM_LR16_REC, ARM_LR8S,
-                 ARM_PS, ARM_PS2, ARM_PS2D, ARM_PW, ARM_PROGRAM_WAVE };
+                 ARM_PS, ARM_PS2, ARM_PS2D, ARM_PW, ARM_PROGRAM_WAVE, ARM_SNOOKER };
 struct WindowKernel {
     const void* fn = nullptr;       // host symbol of a built-in kernel ...
     hipFunction_t mod = nullptr;    // ... or the function of the program's module; neither: not built (or no program yet)
@@ -188,6 +189,7 @@ struct LaunchFacts {
     bool pw_matrix = false;   // pw_matrix_form(h)
     bool coop = false;        // ml_coop(h)
     bool lr16 = false;        // uses_lr16(h)
+    bool snooker = false;     // the launch is one snooker generation (LaunchPlan::snooker)
 };
 
 // A replica group of one process (demcz_peer_group): R handles on one device, each with its own archive replica and shard of
@@ -420,6 +422,12 @@ struct demcz_handle {
     // staging buffer and nothing else -- no state, no archive, no log_obj.  The statistics over dchain and demcz_derive itself
     // take it; every other entry point refuses it (NOT_DERIVED) before it looks at a buffer that is not there.
     bool derived = false;
+    // snooker generations (demcz_set_snooker; one-lane handles): every snooker_every-th generation of the stream numbering is one
+    // snooker step on all d parameters, gamma_s ~ U(snooker_lo, snooker_hi); 0: off
+    int64_t snooker_every = 0;
+    double snooker_lo = 1.2, snooker_hi = 2.2;
+    int64_t snooker_steps = 0;        // snooker launches made in the handle's life
+    bool snooker_now = false;         // the launch being prepared is one (LaunchPlan::snooker)
 };
 
 #define HIPCHK(h, expr)                                                                          \
@@ -1458,7 +1466,9 @@ static int32_t launch_kernel(demcz_handle* h, const WindowKernel& k, int64_t blo
     if (h->cfg.target_kind == DEMCZ_TARGET_PROGRAM && !h->prog_ready)
         return fail(h, DEMCZ_ERR_STATE, "demcz_run: program target: call demcz_set_program first");
     if (!k.fn && !k.mod) return fail(h, DEMCZ_ERR_STATE, "window launch: target / dimension not built for this handle's layout");
-    void* args[] = {const_cast<WindowParams*>(&P)};
+    // (a snooker launch has a second argument; a kernel that takes one never looks at the other)
+    SnookerParams sp{h->snooker_lo, h->snooker_hi};
+    void* args[] = {const_cast<WindowParams*>(&P), &sp};
     if (k.mod) {
         HIPCHK(h, hipModuleLaunchKernel(k.mod, (unsigned)blocks, 1, 1, (unsigned)k.threads, 1, 1, (unsigned)k.dyn_lds, h->stream, args, nullptr));
     } else {
@@ -1816,6 +1826,7 @@ static LaunchFacts launch_facts(const demcz_handle* h, const WindowParams* P, bo
     f.live = live;
     f.temper = P && P->temperature != nullptr;
     f.dual = h->dual_now;
+    f.snooker = h->snooker_now;
     if (h->lanes == DEMCZ_LAYOUT_SPLIT) {
         if (h->split_kind == SPLIT_WAVE && !h->prog_wave) {
             f.ps2 = P && ps2_applicable(h, *P);
@@ -1837,6 +1848,16 @@ static WindowKernel window_kernel_of(const demcz_handle* h, const LaunchFacts& f
     k.live = f.live;
     k.temper = f.temper;
     const int d = h->cfg.d, tk = h->cfg.target_kind;
+    if (f.snooker) {
+        // one snooker generation of a one-lane handle (demcz_set_snooker admits no other layout): snooker_kernel<TARGET, D> where
+        // the one-lane dispatch specialises the dimension, snooker_kernel_generic<TARGET> otherwise, or the program's own
+        k.arm = ARM_SNOOKER;
+        k.threads = WINDOW_BS;
+        k.waves = 1;
+        if (tk == DEMCZ_TARGET_PROGRAM) { if (h->prog_ready) k.mod = h->prog.snooker; }
+        else k.fn = snooker_kernel_fn(tk, d, &k.dyn_lds);
+        return k;
+    }
     if (h->lanes == DEMCZ_LAYOUT_SPLIT) {
         if (h->lr_spec) {
             k.arm = ARM_LR8S;
@@ -2712,6 +2733,9 @@ static int32_t run_call(demcz_handle* h, int64_t g_from, int64_t g_to, double ga
         if (h->external_append && nb == 1 && (g_to % K) != 0)
             return fail(h, DEMCZ_ERR_STATE, "demcz_run: with external append the K boundary must be the last generation of the call");
     }
+    if (h->snooker_every > 0 && h->M < 3)
+        return fail(h, DEMCZ_ERR_STATE, "demcz_run: snooker generations draw three distinct archive rows: the archive has fewer than three "
+                                        "(demcz_set_snooker with every = 0 switches them off)");
     if (h->peer_mode == 3 && h->peers_closed)
         return fail(h, DEMCZ_ERR_STATE, "demcz_run: the peers' archives have been closed (demcz_peer_detach): this handle runs no further generations");
     if (h->peer_mode == 3 && !peer)
@@ -2851,11 +2875,13 @@ static int32_t run_call(demcz_handle* h, int64_t g_from, int64_t g_to, double ga
     //  instantiation itself costs, scripts/live_fixed_cost.py)
     static const bool force_live = getenv("DEMCZ_FORCE_LIVE_KERNEL") != nullptr;
     F.force_live = force_live;
+    F.snooker_every = h->snooker_every;
     for (int64_t g = g_from; g <= g_to;) {
         F.rec_in_arena = h->rec_in_arena;         // (pc_prepare moves the buffers out of the arena should a caller outrun what was reserved)
         const LaunchPlan lp = plan_launch(F, g, live_span(h), h->M, h->M_app, h->rec_desc[h->rec_cur], h->pending);
         const int64_t w_end = lp.w_end, nbound = lp.nbound;
         h->dual_now = lp.dual;
+        h->snooker_now = lp.snooker;
         int32_t rc = admit_pending(h, g);
         if (rc) return rc;
         P.M = h->M;
@@ -2891,8 +2917,10 @@ static int32_t run_call(demcz_handle* h, int64_t g_from, int64_t g_to, double ga
             HIPCHK(h, hipMemsetAsync(P.acc_out, 0, (size_t)h->acc_waves * 2 * sizeof(unsigned int), h->stream));
         if (live) h->err_clean = false;
         rc = launch_window(h, P, live);
+        h->snooker_now = false;
         h->after_launch_ev = nullptr;         // (whatever was recorded before this launch says nothing about it)
         if (rc) return rc;
+        if (lp.snooker) ++h->snooker_steps;
         if (h->d_acc) {
             h->acc_log.push_back({g, w_end, h->acc_next});
             h->acc_next = (h->acc_next + 1) % h->acc_slots;
@@ -3961,6 +3989,7 @@ extern "C" int32_t demcz_peer_group(demcz_handle** handles, int32_t R)
         NOT_DERIVED(m);
         for (int q = 0; q < r; ++q) if (handles[q] == m) return fail(m, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_peer_group: a handle appears twice");
         if (m->comm || m->peer_mode != 0) return fail(m, DEMCZ_ERR_STATE, "demcz_peer_group: handle is already sharded");
+        if (m->snooker_every > 0) return fail(m, DEMCZ_ERR_STATE, "demcz_peer_group: a handle with snooker generations (demcz_set_snooker) does not join a replica group");
         if (m->prog_wave)
             return fail(m, DEMCZ_ERR_STATE, "demcz_peer_group: a program target on DEMCZ_LAYOUT_PROGRAM_WAVE does not join a replica group (sharded "
                                             "in-launch hand-off is not built for programs): shard it from the host or use the one-lane layout");
@@ -4392,6 +4421,42 @@ extern "C" int32_t demcz_set_rng_offset(demcz_handle* h, int64_t generations)
     if (!h->live_log.empty()) { int32_t rcv = live_verify(h); if (rcv) return rcv; }
     h->rng_offset = generations;
     rec_invalidate(h);
+    return DEMCZ_OK;
+}
+
+// Snooker generations.  The choice of move is a fact of the generation, the same for all chains and
+// known to the host: plan_launch cuts a snooker generation into a launch of its own and run_call launches snooker_kernel for it.
+extern "C" int32_t demcz_set_snooker(demcz_handle* h, int32_t every, double gamma_lo, double gamma_hi)
+{
+    NOT_DERIVED(h);
+    if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
+    DEADCHK(h);
+    if (every < 0) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_snooker: every must be >= 0 (0 switches the snooker generations off)");
+    if (!std::isfinite(gamma_lo) || !std::isfinite(gamma_hi) || !(0.0 < gamma_lo && gamma_lo <= gamma_hi))
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_snooker: the bounds of gamma_s must be finite with 0 < gamma_lo <= gamma_hi");
+    if (h->cfg.target_kind == DEMCZ_TARGET_HOST_CALLBACK)
+        return fail(h, DEMCZ_ERR_STATE, "demcz_set_snooker: a host-callback handle proposes through demcz_propose: it has no snooker generations");
+    if (h->peer_mode != 0)
+        return fail(h, DEMCZ_ERR_STATE, "demcz_set_snooker: the handle is in a replica group or has IPC peers: their launches hand rows over "
+                                        "inside them and are not cut at snooker generations");
+    if (h->cfg.d < 2) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_snooker: the snooker step needs d >= 2 (a line through two points of a plane or more)");
+    if (h->lanes != 1)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_snooker: the handle was not created on the one-lane layout (create it with "
+                                                   "lanes_per_chain = 1): the other layouts draw ahead of the chains");
+    h->snooker_every = every;
+    h->snooker_lo = gamma_lo;
+    h->snooker_hi = gamma_hi;
+    return DEMCZ_OK;
+}
+
+extern "C" int32_t demcz_get_snooker(const demcz_handle* h, int32_t* every, double* gamma_lo, double* gamma_hi, int64_t* steps_launched)
+{
+    NOT_DERIVED(h);
+    if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
+    if (every) *every = (int32_t)h->snooker_every;
+    if (gamma_lo) *gamma_lo = h->snooker_lo;
+    if (gamma_hi) *gamma_hi = h->snooker_hi;
+    if (steps_launched) *steps_launched = h->snooker_steps;
     return DEMCZ_OK;
 }
 
@@ -5223,6 +5288,11 @@ extern "C" int32_t demcz_debug_kernel_name(const demcz_handle* h, char* buf, int
     case ARM_LR16: snprintf(tmp, sizeof tmp, "window_kernel_lr16<%d, false, false>", d); break;
     case ARM_ML_COOP: snprintf(tmp, sizeof tmp, "window_kernel_ml<%s, %d, %d, false, false, true>", tg, d, h->lanes); break;
     case ARM_ML: snprintf(tmp, sizeof tmp, "window_kernel_ml<%s, %d, %d>", tg, d, h->lanes); break;
+    case ARM_SNOOKER:
+        if (h->cfg.target_kind == DEMCZ_TARGET_PROGRAM) snprintf(tmp, sizeof tmp, "snooker_kernel<%d, %d> (program)", (int)TARGET_PROGRAM, d);
+        else if (k.dyn_lds) snprintf(tmp, sizeof tmp, "snooker_kernel_generic<%s>", tg);
+        else snprintf(tmp, sizeof tmp, "snooker_kernel<%s, %d>", tg, d);
+        break;
     case ARM_ONE_LANE:
         // Known misreport: a dimension with no specialisation launches window_kernel_generic<TARGET> and is still named
         // window_kernel<TARGET, d, FULL> here (tests and profile scripts match on the string; correcting it is a change of behaviour).

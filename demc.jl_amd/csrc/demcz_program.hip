@@ -6,7 +6,9 @@
 //     #define DEMCZ_D <d> / DEMCZ_PROGRAM_TARGET / DEMCZ_NO_AUX_KERNELS, INFINITY and NAN as <math.h> has them
 //     the user's source                      (#line 1 "program": compiler messages carry the user's own line numbers)
 //     #include "demcz_kernels.h"             (its text and demcz_device.h's are embedded into this library at build time)
-//     explicit instantiations of window_kernel<TARGET_PROGRAM, DEMCZ_D, true / false> and logp_kernel<TARGET_PROGRAM>
+//     #include "demcz_kernels_snooker.h"     (the snooker generation's kernel: a program that cannot be built for it fails here)
+//     explicit instantiations of window_kernel<TARGET_PROGRAM, DEMCZ_D, true / false>, snooker_kernel<TARGET_PROGRAM, DEMCZ_D>
+//     and logp_kernel<TARGET_PROGRAM>
 // The wave unit (UNIT_WAVE, handles created with DEMCZ_LAYOUT_PROGRAM_WAVE; composed and compiled only for them, cached under a
 // key of its own) has the same head, then
 //     #define ML_LRDPP 0 / PW_DDPP 0         (the generated DPP texts of the built-in targets are not part of the unit: the
@@ -51,6 +53,9 @@ const char k_device_h[] = {
     , 0};
 const char k_kernels_h[] = {
 #embed "demcz_kernels.h"
+    , 0};
+const char k_snooker_h[] = {
+#embed "demcz_kernels_snooker.h"
     , 0};
 // the wave unit's headers
 const char k_rec_h[] = {
@@ -120,9 +125,10 @@ std::string compose(int d, int m, const std::string& source, int unit)
     s << "#define DEMCZ_D " << d << "\n#define DEMCZ_PROGRAM_TARGET\n#define DEMCZ_NO_AUX_KERNELS\n"
       << "#include <hip/hip_runtime.h>\n#include <stdint.h>\n" << k_math_macros
       << "#line 1 \"program\"\n" << source << "\n"
-      << "#line 1 \"demcz_program_unit\"\n#include \"demcz_kernels.h\"\n"
+      << "#line 1 \"demcz_program_unit\"\n#include \"demcz_kernels.h\"\n#include \"demcz_kernels_snooker.h\"\n"
       << "template __global__ void demcz::window_kernel<demcz::TARGET_PROGRAM, DEMCZ_D, true>(const demcz::WindowParams);\n"
       << "template __global__ void demcz::window_kernel<demcz::TARGET_PROGRAM, DEMCZ_D, false>(const demcz::WindowParams);\n"
+      << "template __global__ void demcz::snooker_kernel<demcz::TARGET_PROGRAM, DEMCZ_D>(const demcz::WindowParams, const demcz::SnookerParams);\n"
       << "template __global__ void demcz::logp_kernel<demcz::TARGET_PROGRAM>(demcz::TargetParams, int, const double*, int64_t, "
          "int64_t, double*);\n";
     return s.str();
@@ -193,10 +199,13 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
     const char* names[] = {"demcz_device.h", "demcz_kernels.h", "demcz_kernels_rec.h", "demcz_kernels_ml.h", "demcz_mlb_dpp_20_5.inc",
                            "demcz_kernels_pc.h", "demcz_kernels_ps.h", "demcz_kernels_pw.h"};
     const bool wave = unit == demcz_prog::UNIT_WAVE, derive = unit == demcz_prog::UNIT_DERIVE;
+    const char* lane_headers[] = {k_device_h, k_kernels_h, k_snooker_h};
+    const char* lane_names[] = {"demcz_device.h", "demcz_kernels.h", "demcz_kernels_snooker.h"};
     const char* derive_headers[] = {k_derive_h};
     const char* derive_names[] = {"demcz_kernels_derive.h"};
     if (derive) RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_unit_derive.hip", 1, derive_headers, derive_names));
-    else RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), wave ? "demcz_program_wave_unit.hip" : "demcz_program_unit.hip", wave ? 8 : 2, headers, names));
+    else if (wave) RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_program_wave_unit.hip", 8, headers, names));
+    else RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_program_unit.hip", 3, lane_headers, lane_names));
     struct Guard { hiprtcProgram& p; ~Guard() { if (p) (void)hiprtcDestroyProgram(&p); } } guard{prog};
     const std::string ds = std::to_string(d);
     std::vector<std::string> exprs;
@@ -208,7 +217,7 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
             for (int temper = 0; temper < 2; ++temper)
                 exprs.push_back(kn + ds + (live ? ", true" : ", false") + (temper ? ", true>" : ", false>"));
     } else {
-        exprs = {"&demcz::window_kernel<4, " + ds + ", true>", "&demcz::window_kernel<4, " + ds + ", false>"};
+        exprs = {"&demcz::window_kernel<4, " + ds + ", true>", "&demcz::window_kernel<4, " + ds + ", false>", "&demcz::snooker_kernel<4, " + ds + ">"};
     }
     if (!derive) exprs.push_back("&demcz::logp_kernel<4>");
     for (const auto& e : exprs) RTCCHK(hiprtcAddNameExpression(prog, e.c_str()));
@@ -246,7 +255,7 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
     std::vector<std::string*> lowered;
     if (derive) lowered = {&code.derive};
     else if (wave) lowered = {&code.wave[0][0], &code.wave[0][1], &code.wave[1][0], &code.wave[1][1], &code.logp};
-    else lowered = {&code.window_full, &code.window_blocks, &code.logp};
+    else lowered = {&code.window_full, &code.window_blocks, &code.snooker, &code.logp};
     for (size_t i = 0; i < lowered.size(); ++i) {
         const char* nm = nullptr;
         RTCCHK(hiprtcGetLoweredName(prog, exprs[i].c_str(), &nm));
@@ -328,6 +337,7 @@ int32_t get_module(const std::shared_ptr<const Code>& code, int device, Module& 
     } else {
         if (e == hipSuccess) e = hipModuleGetFunction(&m.window_full, m.module, code->window_full.c_str());
         if (e == hipSuccess) e = hipModuleGetFunction(&m.window_blocks, m.module, code->window_blocks.c_str());
+        if (e == hipSuccess) e = hipModuleGetFunction(&m.snooker, m.module, code->snooker.c_str());
     }
     if (code->unit != UNIT_DERIVE && e == hipSuccess) e = hipModuleGetFunction(&m.logp, m.module, code->logp.c_str());
     if (e != hipSuccess) {

@@ -78,6 +78,7 @@ struct RunFacts {
     int64_t cold_limit = 0;         // cold_start_limit
     int64_t next_hint = 0;          // generations of the launch that follows the call (0: not known -- taken to be as long as this call)
     bool force_live = false;        // diagnosis: the LIVE instantiation also for launches with no boundary inside
+    int64_t snooker_every = 0;      // s >= 1: generation g is a snooker generation when (g + rng_offset) % s == 0 (0: none)
 };
 
 struct LaunchPlan {
@@ -89,7 +90,18 @@ struct LaunchPlan {
     // split layouts: the launch after this one, whose draws this launch's producer half prepares
     int64_t next_g_first = 0, next_ngen = 0, next_M = 0, next_rows = 0;
     int32_t next_boff = 0;
+    bool snooker = false;           // the launch is one snooker generation (snooker_kernel, demcz_kernels_snooker.h)
 };
+
+// ---- snooker generations -------------------------------------------------------------------------------------------------------------
+// The same number positions the Philox streams, so a resumed run (rng_offset) makes the choices an uninterrupted one would.
+inline bool snooker_generation(const RunFacts& f, int64_t g) { return f.snooker_every > 0 && (g + f.rng_offset) % f.snooker_every == 0; }
+// the first snooker generation at or after g (callers ask only with snooker_every > 0)
+inline int64_t snooker_at_or_after(const RunFacts& f, int64_t g)
+{
+    const int64_t s = f.snooker_every, r = (g + f.rng_offset) % s;
+    return r == 0 ? g : g + (s - r);
+}
 
 // The launch that starts at generation g.  `span`: what live_span() says a LIVE launch may cover (0: no LIVE launches); M, M_app:
 // rows proposals draw from and rows appended, BEFORE the rows pending at g are admitted; cur: the descriptor of the record buffer
@@ -133,6 +145,12 @@ static LaunchPlan plan_launch(const RunFacts& f, int64_t g, int64_t span, int64_
         }
         if (p.dual) n = std::max<int64_t>((n / f.R) * f.R, f.R);
         w_end = g + n - 1;
+    }
+    // Snooker generations are launches of their own: the move is the same for all chains of a generation and known here, so
+    // no window kernel has to know of it.  (One-lane handles only: span == 0, no split, no two-chain regularity to keep.)
+    if (f.snooker_every > 0) {
+        if (snooker_generation(f, g)) { w_end = g; p.snooker = true; }
+        else w_end = std::min(w_end, snooker_at_or_after(f, g) - 1);
     }
     p.w_end = w_end;
     p.nbound = boundaries_in(g, w_end, K);

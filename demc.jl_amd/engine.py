@@ -415,6 +415,19 @@ class HipEngine(_HistoryStatistics):
     def set_rng_offset(self, generations):
         self._chk(self._L.demcz_set_rng_offset(self._h, int(generations)))
 
+    def set_snooker(self, every, gamma=(1.2, 2.2)):
+        """demcz_set_snooker: every ``every``-th generation (of the stream numbering) is a snooker generation with
+        gamma_s ~ U(gamma[0], gamma[1]); 0 switches them off.  One-lane handles (``lanes_per_chain=1``) only."""
+        lo, hi = gamma
+        self._chk(self._L.demcz_set_snooker(self._h, C.c_int32(int(every)), C.c_double(float(lo)), C.c_double(float(hi))))
+
+    @property
+    def snooker(self):
+        """(every, gamma_lo, gamma_hi, snooker launches made so far) -- demcz_get_snooker."""
+        ev, lo, hi, n = C.c_int32(0), C.c_double(0.0), C.c_double(0.0), C.c_int64(0)
+        self._chk(self._L.demcz_get_snooker(self._h, C.byref(ev), C.byref(lo), C.byref(hi), C.byref(n)))
+        return int(ev.value), float(lo.value), float(hi.value), int(n.value)
+
     def set_history_origin(self, g0):
         self._chk(self._L.demcz_set_history_origin(self._h, int(g0)))
 

@@ -463,10 +463,13 @@ class _DerivedRunner(_Runner):
 
 
 def make_runner(logobj, Zmat, N, K, Ngeneration, blockindex, eps_scale, X, logp, *, seed, sharding, device_id,
-                 engine_factory, lanes_per_chain, stream, rng_offset=0, append_lag=0):
+                 engine_factory, lanes_per_chain, stream, rng_offset=0, append_lag=0, snooker_every=0, snooker_gamma=(1.2, 2.2)):
     M0, d = Zmat.shape
     if M0 < 2:
         raise ValueError("Zmat needs at least 2 rows (two distinct archive rows per proposal, demcz.jl:176-179)")
+    lanes_per_chain = _snooker_layout(logobj, lanes_per_chain, snooker_every)
+    if snooker_every and M0 < 3:
+        raise ValueError("Zmat needs at least 3 rows with snooker generations (three distinct archive rows per snooker step)")
     sh = sharding
     shards = sh.total_shards if sh else 1
     if N % shards:
@@ -485,6 +488,10 @@ def make_runner(logobj, Zmat, N, K, Ngeneration, blockindex, eps_scale, X, logp,
         e.set_state(X[c0:c0 + n_loc], None if logp is None else logp[c0:c0 + n_loc], Zmat)
         if rng_offset:
             e.set_rng_offset(rng_offset)
+        if snooker_every:
+            if not hasattr(e, "set_snooker"):
+                raise ValueError("snooker_every > 0: the engine_factory's engine has no set_snooker")
+            e.set_snooker(snooker_every, snooker_gamma)
         engines.append(e)
     if sh and sh.mode == "peer" and len(engines) > 1:
         type(engines[0]).peer_group(engines)
@@ -493,6 +500,21 @@ def make_runner(logobj, Zmat, N, K, Ngeneration, blockindex, eps_scale, X, logp,
         uid = sh.broadcast_bytes(uid)
         engines[0].comm_init(uid, sh.world_size, sh.rank)
     return _Runner(engines, sh, K, N, d, append_lag=append_lag)
+
+
+def _snooker_layout(logobj, lanes_per_chain, snooker_every):
+    """The layout a run with snooker generations is created on: one lane per chain (the library's choice, 0, becomes 1; the
+    other layouts draw ahead of the chains and are refused), a device target only."""
+    snooker_every = int(snooker_every)
+    if snooker_every < 0:
+        raise ValueError("snooker_every must be >= 0")
+    if snooker_every == 0:
+        return lanes_per_chain
+    if not is_device_target(logobj):
+        raise ValueError("snooker_every > 0 needs a device target: the host-closure mode has no snooker generations")
+    if lanes_per_chain not in (0, 1):
+        raise ValueError("snooker_every > 0 runs on the one-lane layout: lanes_per_chain must be 0 or 1")
+    return 1
 
 
 def blocks_per_generation(blockindex):
@@ -629,8 +651,11 @@ def demcz_sample(logobj, Zmat, N=4, K=10, Ngeneration=5000, Nblocks=1, blockinde
                  prevrun=None, verbose=True, print_step=100, autostop="no", autostop_Rhat=1.01,
                  autostop_every=1000, seed=0, init="last_rows", padded_Z=False, sharding=None, device_id=0,
                  lanes_per_chain=0, stream=None, engine_factory=None, return_runner=False, rng_offset=None,
-                 append_lag=0):
-    """Serial-driver surface of src/demcz.jl: pass a ``DEMCopt`` as the third argument
+                 append_lag=0, snooker_every=0, snooker_gamma=(1.2, 2.2)):
+    """``snooker_every=s > 0``: every s-th generation is a snooker generation of DE-MCzs with gamma_s ~ U(*snooker_gamma)
+    (``HipEngine.set_snooker``; the paper's choice is 10 and (1.2, 2.2)).
+
+    Serial-driver surface of src/demcz.jl: pass a ``DEMCopt`` as the third argument
     (``demcz_sample(logobj, Zmat, opts; prevrun)``, :1-3) or the positional arguments with
     the positional method's defaults (:9).  Returns ``(mc, Z)``."""
     if isinstance(N, DEMCopt):
@@ -652,7 +677,8 @@ def demcz_sample(logobj, Zmat, N=4, K=10, Ngeneration=5000, Nblocks=1, blockinde
         rng_offset = 0 if prevrun is None else _generations_drawn(prevrun, blockindex)
     runner = make_runner(logobj, Zmat, N, K, Ngeneration, blockindex, eps_scale, X, logp, seed=seed,
                           sharding=sharding, device_id=device_id, engine_factory=engine_factory,
-                          lanes_per_chain=lanes_per_chain, stream=stream, rng_offset=rng_offset, append_lag=append_lag)
+                          lanes_per_chain=lanes_per_chain, stream=stream, rng_offset=rng_offset, append_lag=append_lag,
+                          snooker_every=snooker_every, snooker_gamma=snooker_gamma)
     if prevrun is None:
         if not (is_device_target(logobj) and runner.stream_history()):
             runner.prepare_result_arrays(Ngeneration)
@@ -703,8 +729,11 @@ def demcz_sample(logobj, Zmat, N=4, K=10, Ngeneration=5000, Nblocks=1, blockinde
 def demcz_anneal(logobj, Zmat, N=4, K=10, Ngeneration=5000, Nblocks=1, blockindex=None, eps_scale=None, γ=2.38, *,
                  prevrun=None, verbose=True, print_step=100, temperaturefun=tempbaseline, T0=3, TN=0.0,
                  adaptγ=None, seed=0, init="last_rows", padded_Z=False, compat_serial_temp=False, sharding=None,
-                 device_id=0, lanes_per_chain=0, stream=None, engine_factory=None, rng_offset=None, append_lag=0):
-    """Simulated-annealing variant, src/demcz_anneal.jl:14-65: tempered accept
+                 device_id=0, lanes_per_chain=0, stream=None, engine_factory=None, rng_offset=None, append_lag=0,
+                 snooker_every=0, snooker_gamma=(1.2, 2.2)):
+    """``snooker_every`` / ``snooker_gamma``: as in ``demcz_sample`` (the Jacobian term of a snooker step is not tempered).
+
+    Simulated-annealing variant, src/demcz_anneal.jl:14-65: tempered accept
     ``log(u) < (lp' - lp)/T(ig)`` (:172-178), ``T(ig) = temperaturefun(ig, Ngeneration, T0, TN)``,
     gamma adapted from the windowed acceptance ratio every ``adapt_every`` generations (:48-57).
 
@@ -728,7 +757,8 @@ def demcz_anneal(logobj, Zmat, N=4, K=10, Ngeneration=5000, Nblocks=1, blockinde
         rng_offset = 0 if prevrun is None else _generations_drawn(prevrun, blockindex)
     runner = make_runner(logobj, Zmat, N, K, Ngeneration, blockindex, eps_scale, X, logp, seed=seed,
                           sharding=sharding, device_id=device_id, engine_factory=engine_factory,
-                          lanes_per_chain=lanes_per_chain, stream=stream, rng_offset=rng_offset, append_lag=append_lag)
+                          lanes_per_chain=lanes_per_chain, stream=stream, rng_offset=rng_offset, append_lag=append_lag,
+                          snooker_every=snooker_every, snooker_gamma=snooker_gamma)
     if prevrun is None:
         if not (is_device_target(logobj) and runner.stream_history()):
             runner.prepare_result_arrays(Ngeneration)

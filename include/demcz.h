@@ -421,6 +421,25 @@ int32_t demcz_set_append_lag(demcz_handle* h, int32_t batches);
  * like the reference's restarted `ig`. */
 int32_t demcz_set_rng_offset(demcz_handle* h, int64_t generations);
 
+/* Snooker generations: the second updater of DE-MCzs (ter Braak & Vrugt 2008).  Off by default.  With every = s >= 1,
+ * generation g is a snooker generation when (g + rng_offset) % s == 0 -- the number that positions the Philox streams, so a
+ * resumed run (demcz_set_rng_offset) makes the choices an uninterrupted one would.  In a snooker generation every chain makes
+ * ONE step on all d parameters, whatever the block structure, in place of the generation's block-steps: it jumps along the line
+ * from an archive row a through its state x, x' = x + gamma_s ((z1 - z2) . e / e . e) e with e = x - a, z1, z2, a three distinct
+ * archive rows, gamma_s ~ U(gamma_lo, gamma_hi), and accepts with log u < (logp(x') - logp(x)) / T + (d - 1)/2 log(|x' - a|^2 /
+ * |x - a|^2); a step whose |x - a|^2 or |x' - a|^2 is not a positive normal double is rejected (DESIGN.md section 3 has the
+ * arithmetic, operation by operation).  History, changed counts and the K-boundary append are those of any generation.  A
+ * snooker generation is a launch of its own (snooker_kernel); demcz_run, demcz_run_checked, caller-owned appends
+ * (demcz_set_external_append) and the RCCL exchange work as before.  The paper's choice: every = 10, (1.2, 2.2).
+ * May be called after demcz_create and again between runs (every = 0 switches off).
+ * DEMCZ_ERR_INVALID_ARGUMENT: every < 0; bounds not finite or not 0 < gamma_lo <= gamma_hi; d < 2; the handle was not created
+ * on the one-lane layout (lanes_per_chain = 1 -- the other layouts draw ahead of the chains).  DEMCZ_ERR_STATE: a host-callback
+ * handle, a derived history, a handle in a replica group or with IPC peers.  demcz_run with snooker generations on and fewer
+ * than three archive rows returns DEMCZ_ERR_STATE before anything is enqueued. */
+int32_t demcz_set_snooker(demcz_handle* h, int32_t every, double gamma_lo, double gamma_hi);
+/* What was set, and the snooker launches made in the handle's life (any pointer may be NULL). */
+int32_t demcz_get_snooker(const demcz_handle* h, int32_t* every, double* gamma_lo, double* gamma_hi, int64_t* steps_launched);
+
 /* Stateless diagnostics on caller (host) arrays, for code that post-processes returned histories
  * the way the reference's examples do (test/example_normpdf.jl:35-47): the array is uploaded, reduced
  * on the device, and nothing is kept.

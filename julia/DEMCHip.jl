@@ -108,6 +108,16 @@ run!(h, g_from, g_to, γ, temperature=nothing) =
     chk(ccall((:demcz_run, libdemcz), Int32, (Ptr{Cvoid}, Int64, Int64, Float64, Ptr{Float64}),
               h, g_from, g_to, γ, temperature === nothing ? C_NULL : temperature), h)
 set_rng_offset(h, g) = chk(ccall((:demcz_set_rng_offset, libdemcz), Int32, (Ptr{Cvoid}, Int64), h, g), h)
+# snooker generations of DE-MCzs (one-lane handles, lanes_per_chain = 1): every `every`-th generation of the stream numbering is one
+# snooker step on all parameters with γs ~ U(γ_lo, γ_hi); every = 0 switches them off.  The paper's choice: 10, (1.2, 2.2).
+set_snooker!(h, every, γ_lo=1.2, γ_hi=2.2) =
+    chk(ccall((:demcz_set_snooker, libdemcz), Int32, (Ptr{Cvoid}, Int32, Float64, Float64), h, every, γ_lo, γ_hi), h)
+# (every, γ_lo, γ_hi, snooker launches made so far)
+function get_snooker(h)
+    ev = Ref{Int32}(0); lo = Ref{Float64}(0.0); hi = Ref{Float64}(0.0); n = Ref{Int64}(0)
+    chk(ccall((:demcz_get_snooker, libdemcz), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Float64}, Ref{Float64}, Ref{Int64}), h, ev, lo, hi, n), h)
+    Int(ev[]), lo[], hi[], Int(n[])
+end
 # the loop demcz.jl:30-55 (generations + the R-hat test every `every`) as ONE call; returns the generation it stopped at
 function run_checked!(h, g_from, g_to, γ, every, threshold)
     g_stop = Ref{Int64}(0); n = Ref{Int32}(0)
