@@ -56,6 +56,8 @@ SYMBOLS = [
     "demcz_rank_to_z", "demcz_rank_normalize", "demcz_rank_normalize_array", "demcz_indicator_le", "demcz_rank_diagnostics",
     "demcz_rank_diagnostics_array",
     "demcz_set_snooker", "demcz_get_snooker",
+    "demcz_pointwise_check", "demcz_pointwise", "demcz_pointwise_array", "demcz_psis_tail_length", "demcz_gpd_fit",
+    "demcz_loo_columns", "demcz_loo_columns_array", "demcz_loo", "demcz_loo_array",
 ]
 
 
@@ -224,6 +226,19 @@ def load():
     L.demcz_indicator_le.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, _dp, C.POINTER(C.c_void_p)]
     L.demcz_rank_diagnostics.argtypes = [C.c_void_p, C.c_int64, C.c_int64, _dp, _dp, _dp]
     L.demcz_rank_diagnostics_array.argtypes = [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int64, _dp, _dp, _dp]
+    _vpp = C.POINTER(C.c_void_p)
+    L.demcz_pointwise_check.argtypes = [C.c_int32, C.c_char_p, C.c_char_p]
+    L.demcz_pointwise.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_char_p, C.c_char_p, _dp, C.c_int64, _vpp]
+    L.demcz_pointwise_array.argtypes = [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_char_p, C.c_char_p,
+                                        _dp, C.c_int64, _vpp]
+    L.demcz_psis_tail_length.argtypes = [C.c_int64, C.c_double, _lp]
+    L.demcz_gpd_fit.argtypes = [C.c_int64, _dp, _dp, _dp, _dp]
+    L.demcz_loo_columns.argtypes = [C.c_void_p, C.c_int64, C.c_int64, _dp, _dp, _dp, _lp, _dp, _dp]
+    L.demcz_loo_columns_array.argtypes = [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int64, _dp, _dp, _dp, _lp, _dp, _dp]
+    L.demcz_loo.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_char_p, C.c_char_p, _dp, C.c_int64, _dp, _dp, _dp, _lp,
+                            _dp, _dp]
+    L.demcz_loo_array.argtypes = [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_char_p, C.c_char_p, _dp, C.c_int64,
+                                  _dp, _dp, _dp, _lp, _dp, _dp]
     L.demcz_get_archive_pinned.argtypes =[C.c_void_p, C.POINTER(C.c_void_p), _lp]
     L.demcz_get_kernel_time_series.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _ip]
     L.demcz_set_comm_timeout.argtypes = [C.c_void_p, C.c_int64]

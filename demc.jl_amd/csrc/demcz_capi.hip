@@ -8,6 +8,7 @@
 #include "demcz_kernels_sel.h"
 #include "demcz_select_host.h"
 #include "demcz_kernels_rank.h"
+#include "demcz_kernels_loo.h"
 #include "demcz_slab_plan.h"
 #include "demcz_run_plan.h"
 #include "demcz_kernels_ml.h"
@@ -465,7 +466,7 @@ static int32_t refuse_derived(const demcz_handle* h, const char* who)
     if (!h || !h->derived) return DEMCZ_OK;
     return fail(const_cast<demcz_handle*>(h), DEMCZ_ERR_STATE,
                 std::string(who) + ": the handle is a derived history (demcz_derive): it takes the statistics over its values, demcz_get_history "
-                                   "without log_obj, demcz_derive, demcz_synchronize and demcz_destroy, and nothing else");
+                                   "without log_obj, demcz_derive, demcz_pointwise, demcz_loo, demcz_synchronize and demcz_destroy, and nothing else");
 }
 // first statement of every entry point a derived history does not take (a NULL handle is left to the function's own check)
 #define NOT_DERIVED(h)                                                                           \
@@ -4690,6 +4691,110 @@ int32_t rank_refuse_sharded(demcz_handle* h, const char* who)
     return DEMCZ_OK;
 }
 
+// The keys-only sort of the d columns of a window, shared by demcz_rank_normalize and demcz_loo_columns: the scratch and the host
+// copies that have to live until the stream is synchronised.
+struct RankSort {
+    RankScratch sc;
+    int64_t ntiles = 0;
+    size_t nhist = 0, ninfo = 0;
+    const double* dcenter = nullptr;            // sc.center once the centres are uploaded, else null
+    std::vector<double> hcenter;
+    std::vector<unsigned long long> hhist;
+    std::vector<int> hinfo;
+    std::vector<unsigned int> hbase;
+};
+
+// the scratch layout of a sort of d columns of S keys; the caller frees rs.sc.base with dev_free
+int32_t rank_sort_alloc(demcz_handle* h, int d, int64_t S, const char* who, RankSort& rs)
+{
+    RankScratch& sc = rs.sc;
+    const int64_t ntiles = rs.ntiles = (S + RANK_TILE - 1) / RANK_TILE;
+    // [buf0 | buf1 | hist | nan | center | tcount | dbase | info], every piece a multiple of 8 bytes
+    const size_t nkeys = (size_t)d * S, nhist = (size_t)d * RANK_DIGITS * 256, ntc = (size_t)d * ntiles * 256,
+                 ninfo = (size_t)(RANK_DIGITS + 1) * d;
+    const size_t bytes = 2 * nkeys * 8 + nhist * 8 + (size_t)d * 8 + (size_t)d * 8 + (ntc * 4 + 7) / 8 * 8 + nhist * 4 + (ninfo * 4 + 7) / 8 * 8;
+    hipError_t e = dev_malloc(h->cfg.device_id, &sc.base, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        sc.base = nullptr;
+        return fail(h, DEMCZ_ERR_HIP, std::string(who) + ": the sort's scratch (two key buffers of N w d words): " + hipGetErrorString(e));
+    }
+    sc.buf0 = static_cast<uint64_t*>(sc.base);
+    sc.buf1 = sc.buf0 + nkeys;
+    sc.hist = reinterpret_cast<unsigned long long*>(sc.buf1 + nkeys);
+    sc.nan = sc.hist + nhist;
+    sc.center = reinterpret_cast<double*>(sc.nan + d);
+    sc.tcount = reinterpret_cast<unsigned int*>(sc.center + d);
+    sc.dbase = reinterpret_cast<unsigned int*>(reinterpret_cast<char*>(sc.tcount) + (ntc * 4 + 7) / 8 * 8);
+    sc.info = reinterpret_cast<int*>(sc.dbase + nhist);              // (nhist = d * 8 * 256 is even)
+    rs.nhist = nhist;
+    rs.ninfo = ninfo;
+    rs.hhist.assign(nhist, 0ull);
+    rs.hinfo.assign(ninfo, -1);
+    rs.hbase.assign(nhist, 0u);
+    return DEMCZ_OK;
+}
+
+// keys, histograms, the host's sit-out table and the eight passes, queued on h's stream (which is synchronised once, for the
+// histograms).  Afterwards column p's keys stand ascending in buf0 or buf1 as sc.info's last row says, its NaN count in sc.nan.
+int32_t rank_sort_run(demcz_handle* h, int64_t N, int d, int64_t s0, int64_t S, const double* center, const char* who, RankSort& rs)
+{
+    RankScratch& sc = rs.sc;
+    const int64_t ntiles = rs.ntiles;
+    const size_t nhist = rs.nhist, ninfo = rs.ninfo;
+    std::vector<unsigned long long>& hhist = rs.hhist;
+    std::vector<int>& hinfo = rs.hinfo;
+    std::vector<unsigned int>& hbase = rs.hbase;
+    const double* dcenter = nullptr;
+    if (center) {
+        rs.hcenter.assign(center, center + d);
+        HIPCHK(h, hipMemcpyAsync(sc.center, rs.hcenter.data(), (size_t)d * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        dcenter = sc.center;
+    }
+    rs.dcenter = dcenter;
+    HIPCHK(h, hipMemsetAsync(sc.hist, 0, (nhist + d) * sizeof(unsigned long long), h->stream));
+    const dim3 grid((unsigned)ntiles, (unsigned)d);
+    hipLaunchKernelGGL(rank_keys_kernel, grid, dim3(RANK_BS), 0, h->stream, (const double*)h->dchain, N, d, s0, S, dcenter, sc.buf0,
+                       sc.hist, sc.nan);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(hhist.data(), sc.hist, nhist * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    int32_t r2 = sync_stream(h, h->stream, who);
+    if (r2) return r2;
+    // a digit in which all S keys of a parameter agree leaves their order as it is: that parameter sits the pass out
+    std::vector<int> cur((size_t)d, 0);
+    bool any[RANK_DIGITS] = {};
+    for (int b = 0; b < RANK_DIGITS; ++b)
+        for (int p = 0; p < d; ++p) {
+            const unsigned long long* hp = hhist.data() + ((size_t)p * RANK_DIGITS + b) * 256;
+            unsigned int* bp = hbase.data() + ((size_t)b * d + p) * 256;
+            bool one_bin = false;
+            unsigned long long below = 0;
+            for (int k = 0; k < 256; ++k) {
+                one_bin = one_bin || hp[k] == (unsigned long long)S;
+                bp[k] = (unsigned int)below;
+                below += hp[k];
+            }
+            if (one_bin) continue;
+            hinfo[(size_t)b * d + p] = cur[p];
+            cur[p] ^= 1;
+            any[b] = true;
+        }
+    for (int p = 0; p < d; ++p) hinfo[(size_t)RANK_DIGITS * d + p] = cur[p];
+    HIPCHK(h, hipMemcpyAsync(sc.info, hinfo.data(), ninfo * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(sc.dbase, hbase.data(), nhist * sizeof(unsigned int), hipMemcpyHostToDevice, h->stream));
+    for (int b = 0; b < RANK_DIGITS; ++b) {
+        if (!any[b]) continue;
+        const int* info = sc.info + (size_t)b * d;
+        hipLaunchKernelGGL(rank_tile_count_kernel, grid, dim3(RANK_BS), 0, h->stream, (const uint64_t*)sc.buf0, (const uint64_t*)sc.buf1,
+                           S, ntiles, 8 * b, info, sc.tcount);
+        hipLaunchKernelGGL(rank_tile_scan_kernel, dim3(256, (unsigned)d), dim3(256), 0, h->stream, ntiles, info,
+                           (const unsigned int*)(sc.dbase + (size_t)b * d * 256), sc.tcount);
+        hipLaunchKernelGGL(rank_scatter_kernel, grid, dim3(RANK_BS), 0, h->stream, sc.buf0, sc.buf1, S, ntiles, 8 * b, info,
+                           (const unsigned int*)sc.tcount);
+    }
+    return DEMCZ_OK;
+}
+
 // demcz_rank_normalize on a source that holds an N x d x Gcap history (a sampling handle, a derived history, a ScratchHandle)
 int32_t rank_from(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t mode, const double* center, demcz_handle** ranked)
 {
@@ -4709,91 +4814,29 @@ int32_t rank_from(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t mode, c
         return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_rank_normalize: at most 2^31 - 1 draws per parameter and 65535 parameters");
     rc = quiesce_all(h);                        // (the allocations below may synchronise the device)
     if (rc) return rc;
-    const int64_t ntiles = (S + RANK_TILE - 1) / RANK_TILE;
     std::string err;
     demcz_handle* dh = derived_create(h->cfg.device_id, N, d, w, g_from - 1, nullptr, 0, err, who);
     if (!dh) return fail(h, DEMCZ_ERR_HIP, err);
-    // [buf0 | buf1 | hist | nan | center | tcount | dbase | info], every piece a multiple of 8 bytes
-    const size_t nkeys = (size_t)d * S, nhist = (size_t)d * RANK_DIGITS * 256, ntc = (size_t)d * ntiles * 256,
-                 ninfo = (size_t)(RANK_DIGITS + 1) * d;
-    const size_t bytes = 2 * nkeys * 8 + nhist * 8 + (size_t)d * 8 + (size_t)d * 8 + (ntc * 4 + 7) / 8 * 8 + nhist * 4 + (ninfo * 4 + 7) / 8 * 8;
-    RankScratch sc;
-    hipError_t e = dev_malloc(h->cfg.device_id, &sc.base, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
+    RankSort rs;
+    rc = rank_sort_alloc(h, d, S, who, rs);
+    if (rc) {
         free_all(dh);
         delete dh;
-        return fail(h, DEMCZ_ERR_HIP, std::string(who) + ": the sort's scratch (two key buffers of N w d words): " + hipGetErrorString(e));
+        return rc;
     }
-    sc.buf0 = static_cast<uint64_t*>(sc.base);
-    sc.buf1 = sc.buf0 + nkeys;
-    sc.hist = reinterpret_cast<unsigned long long*>(sc.buf1 + nkeys);
-    sc.nan = sc.hist + nhist;
-    sc.center = reinterpret_cast<double*>(sc.nan + d);
-    sc.tcount = reinterpret_cast<unsigned int*>(sc.center + d);
-    sc.dbase = reinterpret_cast<unsigned int*>(reinterpret_cast<char*>(sc.tcount) + (ntc * 4 + 7) / 8 * 8);
-    sc.info = reinterpret_cast<int*>(sc.dbase + nhist);              // (nhist = d * 8 * 256 is even)
-
-    std::vector<double> hcenter;                // (host copies live until the stream is synchronised)
-    std::vector<unsigned long long> hhist(nhist);
-    std::vector<int> hinfo(ninfo, -1);
-    std::vector<unsigned int> hbase(nhist);
     auto body = [&]() -> int32_t {
-        const double* dcenter = nullptr;
-        if (center) {
-            hcenter.assign(center, center + d);
-            HIPCHK(h, hipMemcpyAsync(sc.center, hcenter.data(), (size_t)d * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            dcenter = sc.center;
-        }
-        HIPCHK(h, hipMemsetAsync(sc.hist, 0, (nhist + d) * sizeof(unsigned long long), h->stream));
-        const dim3 grid((unsigned)ntiles, (unsigned)d);
-        hipLaunchKernelGGL(rank_keys_kernel, grid, dim3(RANK_BS), 0, h->stream, (const double*)h->dchain, N, d, s0, S, dcenter, sc.buf0,
-                           sc.hist, sc.nan);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(hhist.data(), sc.hist, nhist * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-        int32_t r2 = sync_stream(h, h->stream, who);
+        int32_t r2 = rank_sort_run(h, N, d, s0, S, center, who, rs);
         if (r2) return r2;
-        // a digit in which all S keys of a parameter agree leaves their order as it is: that parameter sits the pass out
-        std::vector<int> cur((size_t)d, 0);
-        bool any[RANK_DIGITS] = {};
-        for (int b = 0; b < RANK_DIGITS; ++b)
-            for (int p = 0; p < d; ++p) {
-                const unsigned long long* hp = hhist.data() + ((size_t)p * RANK_DIGITS + b) * 256;
-                unsigned int* bp = hbase.data() + ((size_t)b * d + p) * 256;
-                bool one_bin = false;
-                unsigned long long below = 0;
-                for (int k = 0; k < 256; ++k) {
-                    one_bin = one_bin || hp[k] == (unsigned long long)S;
-                    bp[k] = (unsigned int)below;
-                    below += hp[k];
-                }
-                if (one_bin) continue;
-                hinfo[(size_t)b * d + p] = cur[p];
-                cur[p] ^= 1;
-                any[b] = true;
-            }
-        for (int p = 0; p < d; ++p) hinfo[(size_t)RANK_DIGITS * d + p] = cur[p];
-        HIPCHK(h, hipMemcpyAsync(sc.info, hinfo.data(), ninfo * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(sc.dbase, hbase.data(), nhist * sizeof(unsigned int), hipMemcpyHostToDevice, h->stream));
-        for (int b = 0; b < RANK_DIGITS; ++b) {
-            if (!any[b]) continue;
-            const int* info = sc.info + (size_t)b * d;
-            hipLaunchKernelGGL(rank_tile_count_kernel, grid, dim3(RANK_BS), 0, h->stream, (const uint64_t*)sc.buf0, (const uint64_t*)sc.buf1,
-                               S, ntiles, 8 * b, info, sc.tcount);
-            hipLaunchKernelGGL(rank_tile_scan_kernel, dim3(256, (unsigned)d), dim3(256), 0, h->stream, ntiles, info,
-                               (const unsigned int*)(sc.dbase + (size_t)b * d * 256), sc.tcount);
-            hipLaunchKernelGGL(rank_scatter_kernel, grid, dim3(RANK_BS), 0, h->stream, sc.buf0, sc.buf1, S, ntiles, 8 * b, info,
-                               (const unsigned int*)sc.tcount);
-        }
+        const RankScratch& sc = rs.sc;
         hipLaunchKernelGGL(rank_score_kernel, dim3((unsigned)((S + RANK_BS - 1) / RANK_BS), (unsigned)d), dim3(RANK_BS), 0, h->stream,
-                           (const double*)h->dchain, N, d, s0, S, dcenter, (const uint64_t*)sc.buf0, (const uint64_t*)sc.buf1,
+                           (const double*)h->dchain, N, d, s0, S, rs.dcenter, (const uint64_t*)sc.buf0, (const uint64_t*)sc.buf1,
                            (const int*)(sc.info + (size_t)RANK_DIGITS * d), (const unsigned long long*)sc.nan, (int)mode, dh->dchain);
         HIPCHK(h, hipGetLastError());
         return sync_stream(h, h->stream, who);
     };
     rc = body();
     if (rc == DEMCZ_ERR_HIP) (void)hipDeviceSynchronize();          // (a kernel may still be writing what is about to be freed)
-    (void)dev_free(h->cfg.device_id, sc.base);
+    (void)dev_free(h->cfg.device_id, rs.sc.base);
     if (rc) {
         free_all(dh);
         delete dh;
@@ -4943,6 +4986,232 @@ extern "C" int32_t demcz_rank_diagnostics_array(int32_t device_id, const double*
     int32_t rc = s.open(device_id, N, d, G, chain, nullptr);
     if (rc) return diag_fail(s, rc);
     return diag_fail(s, rank_diagnostics_from(&s.h, 1, G, rhat_rank, ess_bulk, ess_tail));
+}
+
+// ---- PSIS-LOO and WAIC (demcz_kernels_pointwise.h, K11 demcz_kernels_loo.h, demcz_loo_host.h) -----------------------------------
+extern "C" int32_t demcz_pointwise_check(int32_t d, const char* source, const char* options)
+{
+    std::shared_ptr<const demcz_prog::Code> code;
+    std::string err;
+    if (demcz_prog::get_code(d, source, options, demcz_prog::UNIT_POINTWISE, code, err) != 0) return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, err);
+    return DEMCZ_OK;
+}
+
+namespace {
+// demcz_pointwise on a source that holds an N x d x Gcap history (a sampling handle, a derived history, a ScratchHandle)
+int32_t pointwise_from(demcz_handle* h, int64_t g_from, int64_t g_to, int64_t obs_from, int32_t mc, const char* source, const char* options,
+                       const double* data, int64_t ndata, demcz_handle** derived)
+{
+    int32_t rc = check_hist_range(h, g_from, g_to, "demcz_pointwise");
+    if (rc) return rc;
+    if (ndata < 0 || (ndata > 0 && !data)) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_pointwise: need ndata >= 0 and data for ndata > 0");
+    if (mc < 1 || mc > LOO_MAX_CHUNK || obs_from < 0)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "pointwise program: mc must be in 1.." + std::to_string(LOO_MAX_CHUNK) + " and obs_from >= 0");
+    HIPCHK(h, hipSetDevice(h->cfg.device_id));
+    rc = live_verify(h);
+    if (rc) return rc;
+    std::shared_ptr<const demcz_prog::Code> code;
+    std::string err;
+    if (demcz_prog::get_code(h->cfg.d, source, options, demcz_prog::UNIT_POINTWISE, code, err) != 0) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, err);
+    demcz_prog::Module mod;
+    if (demcz_prog::get_module(code, h->cfg.device_id, mod, err) != 0) return fail(h, DEMCZ_ERR_HIP, err);
+    rc = quiesce_all(h);                        // (a sharded handle: the allocations below synchronise the device)
+    if (rc) return rc;
+    int64_t N = h->cfg.N, w = g_to - g_from + 1, s0 = g_from - h->g0 - 1, total = N * w;
+    demcz_handle* dh = derived_create(h->cfg.device_id, N, mc, w, g_from - 1, data, ndata, err, "demcz_pointwise");
+    if (!dh) return fail(h, DEMCZ_ERR_HIP, err);
+    const double* chain = h->dchain;
+    const double* ddata = ndata > 0 ? dh->d_design : nullptr;
+    double* out = dh->dchain;
+    int mcount = mc;
+    void* args[] = {&chain, &N, &s0, &total, &ddata, &ndata, &obs_from, &mcount, &out};
+    const unsigned blocks = (unsigned)std::min<int64_t>((total + DERIVE_THREADS - 1) / DERIVE_THREADS, DERIVE_MAX_WG);
+    hipError_t e = hipModuleLaunchKernel(mod.derive, blocks, 1, 1, DERIVE_THREADS, 1, 1, 0, h->stream, args, nullptr);
+    if (e != hipSuccess) h->err = std::string("demcz_pointwise: launching pointwise_kernel: ") + hipGetErrorString(e);
+    rc = (e != hipSuccess) ? DEMCZ_ERR_HIP : sync_stream(h, h->stream, "demcz_pointwise");
+    if (rc) {
+        if (rc == DEMCZ_ERR_HIP) (void)hipDeviceSynchronize();      // (the kernel may still be writing what is about to be freed)
+        free_all(dh);
+        delete dh;
+        return rc;
+    }
+    *derived = dh;
+    return DEMCZ_OK;
+}
+
+// demcz_loo_columns on such a source: the d columns of the window are the log-likelihoods of d observations
+int32_t loo_columns_from(demcz_handle* h, int64_t g_from, int64_t g_to, const double* r_eff, double* elpd_loo, double* pareto_k,
+                         int64_t* n_tail, double* lppd, double* p_waic)
+{
+    const char* who = "demcz_loo_columns";
+    int32_t rc = rank_refuse_sharded(h, who);
+    if (rc) return rc;
+    rc = check_hist_range(h, g_from, g_to, who);
+    if (rc) return rc;
+    const int64_t N = h->cfg.N, w = g_to - g_from + 1, s0 = g_from - h->g0 - 1, S = N * w;
+    const int d = h->cfg.d;
+    if (r_eff)
+        for (int p = 0; p < d; ++p)
+            if (!(r_eff[p] > 0.0) || !(r_eff[p] < INFINITY))
+                return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_loo_columns: every r_eff must be in (0, inf)");
+    HIPCHK(h, hipSetDevice(h->cfg.device_id));
+    rc = live_verify(h);
+    if (rc) return rc;
+    if (S >= ((int64_t)1 << 31) || d > 65535)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_loo_columns: at most 2^31 - 1 draws per column and 65535 columns");
+    rc = quiesce_all(h);                        // (the allocations below may synchronise the device)
+    if (rc) return rc;
+    RankSort rs;
+    rc = rank_sort_alloc(h, d, S, who, rs);
+    if (rc) return rc;
+    // [fit | part | out (4 d doubles) | n_tail (d) | r_eff (d)], every piece a multiple of 8 bytes
+    const int64_t ntiles = (S + LOO_TILE - 1) / LOO_TILE;
+    const size_t fit_bytes = ((size_t)d * sizeof(LooFit) + 7) / 8 * 8, npart = (size_t)d * ntiles * LOO_NPART;
+    void* base = nullptr;
+    hipError_t e = dev_malloc(h->cfg.device_id, &base, fit_bytes + npart * 8 + (size_t)6 * d * 8);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        (void)dev_free(h->cfg.device_id, rs.sc.base);
+        return fail(h, DEMCZ_ERR_HIP, std::string(who) + ": the fit table and the tile sums: " + hipGetErrorString(e));
+    }
+    LooFit* fit = static_cast<LooFit*>(base);
+    double* part = reinterpret_cast<double*>(static_cast<char*>(base) + fit_bytes);
+    double* dout = part + npart;
+    long long* dtail = reinterpret_cast<long long*>(dout + (size_t)4 * d);
+    double* dreff = reinterpret_cast<double*>(dtail + d);
+    std::vector<double> hout((size_t)4 * d), hreff;
+    std::vector<long long> htail((size_t)d);
+    auto body = [&]() -> int32_t {
+        int32_t r2 = rank_sort_run(h, N, d, s0, S, nullptr, who, rs);
+        if (r2) return r2;
+        const RankScratch& sc = rs.sc;
+        const int* where = sc.info + (size_t)RANK_DIGITS * d;
+        const double* reff = nullptr;
+        if (r_eff) {
+            hreff.assign(r_eff, r_eff + d);
+            HIPCHK(h, hipMemcpyAsync(dreff, hreff.data(), (size_t)d * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            reff = dreff;
+        }
+        hipLaunchKernelGGL(psis_fit_kernel, dim3((unsigned)d), dim3(LOO_BS), 0, h->stream, sc.buf0, sc.buf1, where,
+                           (const unsigned long long*)sc.nan, reff, S, fit);
+        hipLaunchKernelGGL(loo_sum_kernel, dim3((unsigned)ntiles, (unsigned)d), dim3(LOO_BS), 0, h->stream, (const uint64_t*)sc.buf0,
+                           (const uint64_t*)sc.buf1, where, (const LooFit*)fit, S, ntiles, part);
+        hipLaunchKernelGGL(loo_finish_kernel, dim3((unsigned)((d + 63) / 64)), dim3(64), 0, h->stream, (const LooFit*)fit, (const double*)part,
+                           S, ntiles, d, dout, dtail);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(hout.data(), dout, hout.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(htail.data(), dtail, htail.size() * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+        return sync_stream(h, h->stream, who);
+    };
+    rc = body();
+    if (rc == DEMCZ_ERR_HIP) (void)hipDeviceSynchronize();          // (a kernel may still be writing what is about to be freed)
+    (void)dev_free(h->cfg.device_id, base);
+    (void)dev_free(h->cfg.device_id, rs.sc.base);
+    if (rc) return rc;
+    for (int p = 0; p < d; ++p) {
+        if (elpd_loo) elpd_loo[p] = hout[p];
+        if (pareto_k) pareto_k[p] = hout[(size_t)d + p];
+        if (lppd) lppd[p] = hout[(size_t)2 * d + p];
+        if (p_waic) p_waic[p] = hout[(size_t)3 * d + p];
+        if (n_tail) n_tail[p] = (int64_t)htail[p];
+    }
+    return DEMCZ_OK;
+}
+
+// demcz_loo on such a source: chunks of observations, each evaluated, reduced and dropped
+int32_t loo_from(demcz_handle* h, int64_t g_from, int64_t g_to, int64_t nobs, const char* source, const char* options, const double* data,
+                 int64_t ndata, const double* r_eff, double* elpd_loo, double* pareto_k, int64_t* n_tail, double* lppd, double* p_waic)
+{
+    const char* who = "demcz_loo";
+    int32_t rc = rank_refuse_sharded(h, who);
+    if (rc) return rc;
+    rc = check_hist_range(h, g_from, g_to, who);
+    if (rc) return rc;
+    if (nobs < 1) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_loo: nobs must be at least 1");
+    if (r_eff)
+        for (int64_t i = 0; i < nobs; ++i)
+            if (!(r_eff[i] > 0.0) || !(r_eff[i] < INFINITY))
+                return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_loo: every r_eff must be in (0, inf)");
+    const int mc = loo_chunk_width(h->cfg.N * (g_to - g_from + 1), LOO_SCRATCH_BUDGET);
+    const int64_t nchunks = loo_chunk_count(nobs, mc);
+    for (int64_t i = 0; i < nchunks; ++i) {
+        int64_t from = 0;
+        int count = 0;
+        loo_chunk(nobs, mc, i, &from, &count);
+        demcz_handle* dh = nullptr;
+        rc = pointwise_from(h, g_from, g_to, from, count, source, options, data, ndata, &dh);
+        if (rc) return rc;
+        rc = rank_part(h, dh, loo_columns_from(dh, g_from, g_to, r_eff ? r_eff + from : nullptr, elpd_loo ? elpd_loo + from : nullptr,
+                                               pareto_k ? pareto_k + from : nullptr, n_tail ? n_tail + from : nullptr,
+                                               lppd ? lppd + from : nullptr, p_waic ? p_waic + from : nullptr));
+        rank_drop(dh);
+        if (rc) return rc;
+    }
+    return DEMCZ_OK;
+}
+}  // namespace
+
+extern "C" int32_t demcz_pointwise(demcz_handle* h, int64_t g_from, int64_t g_to, int64_t obs_from, int32_t mc, const char* source,
+                                   const char* options, const double* data, int64_t ndata, demcz_handle** derived)
+{
+    if (!h || !derived) return DEMCZ_ERR_INVALID_ARGUMENT;
+    *derived = nullptr;
+    DEADCHK(h);
+    return pointwise_from(h, g_from, g_to, obs_from, mc, source, options, data, ndata, derived);
+}
+
+extern "C" int32_t demcz_pointwise_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, int64_t obs_from,
+                                         int32_t mc, const char* source, const char* options, const double* data, int64_t ndata,
+                                         demcz_handle** derived)
+{
+    if (!chain || !derived) return DEMCZ_ERR_INVALID_ARGUMENT;
+    *derived = nullptr;
+    int32_t rc = demcz_pointwise_check(d, source, options);     // (compiled before anything is uploaded)
+    if (rc) return rc;
+    ScratchHandle s;
+    rc = s.open(device_id, N, d, G, chain, nullptr);
+    if (rc) return diag_fail(s, rc);
+    return diag_fail(s, pointwise_from(&s.h, 1, G, obs_from, mc, source, options, data, ndata, derived));
+}
+
+extern "C" int32_t demcz_loo_columns(demcz_handle* h, int64_t g_from, int64_t g_to, const double* r_eff, double* elpd_loo,
+                                     double* pareto_k, int64_t* n_tail, double* lppd, double* p_waic)
+{
+    if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
+    DEADCHK(h);
+    return loo_columns_from(h, g_from, g_to, r_eff, elpd_loo, pareto_k, n_tail, lppd, p_waic);
+}
+
+extern "C" int32_t demcz_loo_columns_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, const double* r_eff,
+                                           double* elpd_loo, double* pareto_k, int64_t* n_tail, double* lppd, double* p_waic)
+{
+    if (!chain) return DEMCZ_ERR_INVALID_ARGUMENT;
+    ScratchHandle s;
+    int32_t rc = s.open(device_id, N, d, G, chain, nullptr);
+    if (rc) return diag_fail(s, rc);
+    return diag_fail(s, loo_columns_from(&s.h, 1, G, r_eff, elpd_loo, pareto_k, n_tail, lppd, p_waic));
+}
+
+extern "C" int32_t demcz_loo(demcz_handle* h, int64_t g_from, int64_t g_to, int64_t nobs, const char* source, const char* options,
+                             const double* data, int64_t ndata, const double* r_eff, double* elpd_loo, double* pareto_k,
+                             int64_t* n_tail, double* lppd, double* p_waic)
+{
+    if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
+    DEADCHK(h);
+    return loo_from(h, g_from, g_to, nobs, source, options, data, ndata, r_eff, elpd_loo, pareto_k, n_tail, lppd, p_waic);
+}
+
+extern "C" int32_t demcz_loo_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, int64_t nobs,
+                                   const char* source, const char* options, const double* data, int64_t ndata, const double* r_eff,
+                                   double* elpd_loo, double* pareto_k, int64_t* n_tail, double* lppd, double* p_waic)
+{
+    if (!chain) return DEMCZ_ERR_INVALID_ARGUMENT;
+    int32_t rc = demcz_pointwise_check(d, source, options);     // (compiled before anything is uploaded)
+    if (rc) return rc;
+    ScratchHandle s;
+    rc = s.open(device_id, N, d, G, chain, nullptr);
+    if (rc) return diag_fail(s, rc);
+    return diag_fail(s, loo_from(&s.h, 1, G, nobs, source, options, data, ndata, r_eff, elpd_loo, pareto_k, n_tail, lppd, p_waic));
 }
 
 extern "C" int32_t demcz_get_info(const demcz_handle* h, int64_t* M, int64_t* launches_window, int32_t* lanes_per_chain)

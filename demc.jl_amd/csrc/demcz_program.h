@@ -20,7 +20,8 @@ constexpr int MAX_DERIVE_M = demcz::DERIVE_MAX_M;
 // consumers of the split layout (DEMCZ_LAYOUT_PROGRAM_WAVE: window_kernel_ps for d = 2..5, window_kernel_pw for d = 6..32).
 // A derive program (demcz_derive, include/demcz.h) has a unit of its own: the user's demcz_derive and derive_kernel of
 // demcz_kernels_derive.h, nothing else.
-enum { UNIT_ONE_LANE = 0, UNIT_WAVE = 1, UNIT_DERIVE = 2 };
+// A pointwise program (demcz_pointwise) likewise: the user's demcz_loglik and pointwise_kernel of demcz_kernels_pointwise.h.
+enum { UNIT_ONE_LANE = 0, UNIT_WAVE = 1, UNIT_DERIVE = 2, UNIT_POINTWISE = 3 };
 constexpr int WAVE_MIN_D = 2;
 
 // One compiled program: the gfx950 code object and the mangled names of its kernels.
@@ -32,7 +33,7 @@ struct Code {
     std::string logp;             // logp_kernel<TARGET_PROGRAM>: the initial log_objcurrent (both units)
     std::string wave[2][2];       // UNIT_WAVE: window_kernel_ps / _pw<TARGET_PROGRAM, d, LIVE, TEMPER>, [LIVE][TEMPER] (the one-lane
                                   // kernels are not in that unit, and these not in the one-lane unit)
-    std::string derive;           // UNIT_DERIVE: derive_kernel, the only kernel of that unit
+    std::string derive;           // UNIT_DERIVE: derive_kernel, the only kernel of that unit; UNIT_POINTWISE: pointwise_kernel
     int d = 0;
     int m = 0;                    // UNIT_DERIVE: derived quantities per draw (DEMCZ_M)
     int unit = UNIT_ONE_LANE;
@@ -43,13 +44,14 @@ struct Module {
     hipModule_t module = nullptr;
     hipFunction_t window_full = nullptr, window_blocks = nullptr, snooker = nullptr, logp = nullptr;
     hipFunction_t wave[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    hipFunction_t derive = nullptr;
+    hipFunction_t derive = nullptr;   // (UNIT_POINTWISE: pointwise_kernel)
     std::shared_ptr<const Code> code;
 };
 
 // Compile `source` for dimension d into `unit` (or take it from the process-wide cache, whose key includes the unit).  Needs no
 // device.  Returns 0, or 1 with the compiler log (or what else went wrong) in err.  m: UNIT_DERIVE only, 1..32 (part of the key).
-int32_t get_code(int d, const char* source, const char* options, int unit, std::shared_ptr<const Code>& out, std::string& err, int m = 0);// Load a code object on `device` (or take it from the cache).  Returns 0, or 2 (a HIP error) with the message in err.
+int32_t get_code(int d, const char* source, const char* options, int unit, std::shared_ptr<const Code>& out, std::string& err, int m = 0);
+// Load a code object on `device` (or take it from the cache).  Returns 0, or 2 (a HIP error) with the message in err.
 int32_t get_module(const std::shared_ptr<const Code>& code, int device, Module& out, std::string& err);
 
 }  // namespace demcz_prog

@@ -21,6 +21,9 @@
 // The derive unit (UNIT_DERIVE, demcz_derive): #define DEMCZ_D <d> / DEMCZ_M <m> / DEMCZ_DERIVE_UNIT, INFINITY and NAN, the
 // user's source (#line 1 "program"), #include "demcz_kernels_derive.h" and nothing else of the library: derive_kernel is its
 // only kernel, and the unit compiles in a fraction of the time a program target takes.
+// The pointwise unit (UNIT_POINTWISE, demcz_pointwise) is the derive unit with DEMCZ_POINTWISE_UNIT in place of DEMCZ_DERIVE_UNIT
+// and DEMCZ_M, the user's demcz_loglik, and demcz_kernels_pointwise.h (which includes demcz_kernels_derive.h for the launch
+// constants): pointwise_kernel is its only kernel.  Same options, same caches.
 // Compile options: --offload-arch=gfx950 -O3 -ffp-contract=off -I<rocm>/include, the library's own layout switches (not for
 // the derive unit, which sees no struct of the library's), then the user's.  Code objects are cached per (composed text,
 // options), loaded modules per (code object, device); both for the life of the process.
@@ -80,6 +83,10 @@ const char k_pw_h[] = {
 const char k_derive_h[] = {
 #embed "demcz_kernels_derive.h"
     , 0};
+// the pointwise unit's header (on top of the derive unit's)
+const char k_pointwise_h[] = {
+#embed "demcz_kernels_pointwise.h"
+    , 0};
 #pragma clang diagnostic pop
 
 // -D switches of the library build that change the layout of WindowParams: the program's kernels must see the same struct
@@ -106,6 +113,13 @@ std::string compose(int d, int m, const std::string& source, int unit)
           << "#include <hip/hip_runtime.h>\n#include <stdint.h>\n" << k_math_macros
           << "#line 1 \"program\"\n" << source << "\n"
           << "#line 1 \"demcz_unit_derive\"\n#include \"demcz_kernels_derive.h\"\n";
+        return s.str();
+    }
+    if (unit == demcz_prog::UNIT_POINTWISE) {
+        s << "#define DEMCZ_D " << d << "\n#define DEMCZ_POINTWISE_UNIT\n"
+          << "#include <hip/hip_runtime.h>\n#include <stdint.h>\n" << k_math_macros
+          << "#line 1 \"program\"\n" << source << "\n"
+          << "#line 1 \"demcz_unit_pointwise\"\n#include \"demcz_kernels_pointwise.h\"\n";
         return s.str();
     }
     if (unit == demcz_prog::UNIT_WAVE) {
@@ -189,7 +203,10 @@ std::string trim_log(std::string log)
     } while (0)
 
 // what a failed call says first: which of the two kinds of program it was about
-const char* who_of(int unit) { return unit == demcz_prog::UNIT_DERIVE ? "derive program: " : "program target: "; }
+const char* who_of(int unit)
+{
+    return unit == demcz_prog::UNIT_DERIVE ? "derive program: " : unit == demcz_prog::UNIT_POINTWISE ? "pointwise program: " : "program target: ";
+}
 
 bool compile(const std::string& text, const std::vector<std::string>& opts, int d, int m, int unit, demcz_prog::Code& code, std::string& err)
 {
@@ -198,19 +215,23 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
     const char* headers[] = {k_device_h, k_kernels_h, k_rec_h, k_ml_h, k_mlb_inc, k_pc_h, k_ps_h, k_pw_h};
     const char* names[] = {"demcz_device.h", "demcz_kernels.h", "demcz_kernels_rec.h", "demcz_kernels_ml.h", "demcz_mlb_dpp_20_5.inc",
                            "demcz_kernels_pc.h", "demcz_kernels_ps.h", "demcz_kernels_pw.h"};
-    const bool wave = unit == demcz_prog::UNIT_WAVE, derive = unit == demcz_prog::UNIT_DERIVE;
+    const bool pointwise = unit == demcz_prog::UNIT_POINTWISE;
+    const bool wave = unit == demcz_prog::UNIT_WAVE, derive = unit == demcz_prog::UNIT_DERIVE || pointwise;   // (derive: a streaming unit)
     const char* lane_headers[] = {k_device_h, k_kernels_h, k_snooker_h};
     const char* lane_names[] = {"demcz_device.h", "demcz_kernels.h", "demcz_kernels_snooker.h"};
     const char* derive_headers[] = {k_derive_h};
     const char* derive_names[] = {"demcz_kernels_derive.h"};
-    if (derive) RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_unit_derive.hip", 1, derive_headers, derive_names));
+    const char* pointwise_headers[] = {k_derive_h, k_pointwise_h};
+    const char* pointwise_names[] = {"demcz_kernels_derive.h", "demcz_kernels_pointwise.h"};
+    if (pointwise) RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_unit_pointwise.hip", 2, pointwise_headers, pointwise_names));
+    else if (derive) RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_unit_derive.hip", 1, derive_headers, derive_names));
     else if (wave) RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_program_wave_unit.hip", 8, headers, names));
     else RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_program_unit.hip", 3, lane_headers, lane_names));
     struct Guard { hiprtcProgram& p; ~Guard() { if (p) (void)hiprtcDestroyProgram(&p); } } guard{prog};
     const std::string ds = std::to_string(d);
     std::vector<std::string> exprs;
     if (derive) {
-        exprs = {"&demcz::derive_kernel"};
+        exprs = {pointwise ? "&demcz::pointwise_kernel" : "&demcz::derive_kernel"};
     } else if (wave) {
         const std::string kn = (d <= 5) ? "&demcz::window_kernel_ps<4, " : "&demcz::window_kernel_pw<4, ";
         for (int live = 0; live < 2; ++live)
@@ -236,7 +257,10 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
         if (!derive && text.find("demcz_logobj") == std::string::npos)   // (the library's own call is in demcz_kernels.h, not in `text`)
             err += "; the program does not define demcz_logobj -- it must define "
                    "__device__ double demcz_logobj(const double* x, const double* data, int64_t ndata)";
-        if (derive && text.find("demcz_derive") == std::string::npos)    // (... and derive_kernel's in demcz_kernels_derive.h)
+        if (pointwise && text.find("demcz_loglik") == std::string::npos)
+            err += "; the program does not define demcz_loglik -- it must define "
+                   "__device__ double demcz_loglik(const double* x, const double* data, int64_t ndata, int64_t i)";
+        if (derive && !pointwise && text.find("demcz_derive") == std::string::npos)    // (... and derive_kernel's in demcz_kernels_derive.h)
             err += "; the program does not define demcz_derive -- it must define "
                    "__device__ void demcz_derive(const double* x, double logp, const double* data, int64_t ndata, double* out)";
         err += ":\n" + trim_log(log);
@@ -248,7 +272,7 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
     RTCCHK(hiprtcGetCode(prog, code.object.data()));
     if (const char* dump = getenv("DEMCZ_PROGRAM_DUMP"); dump && *dump) {
         // diagnosis (scripts/kernel_regs.py, llvm-objdump): the code object as a file in that directory
-        const std::string path = std::string(dump) + "/demcz_program_" + (derive ? "derive" : wave ? "wave" : "lane") + "_d" + ds + "_" +
+        const std::string path = std::string(dump) + "/demcz_program_" + (pointwise ? "pointwise" : derive ? "derive" : wave ? "wave" : "lane") + "_d" + ds + "_" +
                                  std::to_string(std::hash<std::string>{}(text) % 1000000007ull) + ".co";
         if (FILE* f = fopen(path.c_str(), "wb")) { (void)fwrite(code.object.data(), 1, code.object.size(), f); fclose(f); }
     }
@@ -274,7 +298,7 @@ namespace demcz_prog {
 
 int32_t get_code(int d, const char* source, const char* options, int unit, std::shared_ptr<const Code>& out, std::string& err, int m)
 {
-    if (unit != UNIT_ONE_LANE && unit != UNIT_WAVE && unit != UNIT_DERIVE) {
+    if (unit != UNIT_ONE_LANE && unit != UNIT_WAVE && unit != UNIT_DERIVE && unit != UNIT_POINTWISE) {
         err = "program target: lanes_per_chain must be 0, 1 or DEMCZ_LAYOUT_PROGRAM_WAVE";
         return 1;
     }
@@ -299,7 +323,7 @@ int32_t get_code(int d, const char* source, const char* options, int unit, std::
     std::string inc;
     if (!rocm_include(inc, err)) return 1;
     std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-I" + inc};
-    if (unit != UNIT_DERIVE)
+    if (unit != UNIT_DERIVE && unit != UNIT_POINTWISE)
         for (const char* const* s = k_layout_switches; *s; ++s) opts.push_back(*s);
     for (auto& o : split_options(options)) opts.push_back(o);
     // (the text is the key: it names the unit's kernel header and, for a derive unit, DEMCZ_M)
@@ -328,7 +352,8 @@ int32_t get_module(const std::shared_ptr<const Code>& code, int device, Module& 
     Module m;
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipModuleLoadData(&m.module, code->object.data());
-    if (code->unit == UNIT_DERIVE) {
+    const bool streaming = code->unit == UNIT_DERIVE || code->unit == UNIT_POINTWISE;
+    if (streaming) {
         if (e == hipSuccess) e = hipModuleGetFunction(&m.derive, m.module, code->derive.c_str());
     } else if (code->unit == UNIT_WAVE) {
         for (int live = 0; live < 2; ++live)
@@ -339,7 +364,7 @@ int32_t get_module(const std::shared_ptr<const Code>& code, int device, Module& 
         if (e == hipSuccess) e = hipModuleGetFunction(&m.window_blocks, m.module, code->window_blocks.c_str());
         if (e == hipSuccess) e = hipModuleGetFunction(&m.snooker, m.module, code->snooker.c_str());
     }
-    if (code->unit != UNIT_DERIVE && e == hipSuccess) e = hipModuleGetFunction(&m.logp, m.module, code->logp.c_str());
+    if (!streaming && e == hipSuccess) e = hipModuleGetFunction(&m.logp, m.module, code->logp.c_str());
     if (e != hipSuccess) {
         if (m.module) (void)hipModuleUnload(m.module);
         err = std::string(who_of(code->unit)) + "loading the code object: " + hipGetErrorString(e);

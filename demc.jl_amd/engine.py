@@ -45,6 +45,73 @@ Best = namedtuple("Best", "bestval chain generation bestpar")
 RankDiagnostics = namedtuple("RankDiagnostics", "rhat_rank ess_bulk ess_tail")
 
 
+# PSIS-LOO and WAIC (demcz_loo, demcz_loo_columns).  Per observation: elpd_loo_i, pareto_k, n_tail, lppd_i, p_waic_i,
+# p_loo_i = lppd_i - elpd_loo_i and elpd_waic_i = lppd_i - p_waic_i; the totals elpd_loo, p_loo, elpd_waic, p_waic; se_elpd_loo and
+# se_elpd_waic = sqrt(nobs var(pointwise, divisor nobs - 1)); k_threshold = min(1 - 1 / log10(S), 0.7) of the S draws; bad_k: the
+# observations with pareto_k above it; names
+LOO = namedtuple("LOO", "elpd_loo_i pareto_k n_tail lppd_i p_waic_i p_loo_i elpd_waic_i elpd_loo p_loo elpd_waic p_waic se_elpd_loo "
+                        "se_elpd_waic k_threshold bad_k names")
+
+
+def _pointwise_se(v):
+    """sqrt(nobs * var(v, divisor nobs - 1)); NaN for one observation."""
+    v = np.asarray(v, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        return float(np.sqrt(v.size * np.var(v, ddof=1))) if v.size > 1 else float("nan")
+
+
+def loo_record(elpd_loo_i, pareto_k, n_tail, lppd_i, p_waic_i, S, names=None):
+    """The ``LOO`` record of the five per-observation outputs of demcz_loo / demcz_loo_columns over S draws (host code)."""
+    elpd_loo_i, pareto_k, lppd_i, p_waic_i = (np.asarray(a, dtype=np.float64) for a in (elpd_loo_i, pareto_k, lppd_i, p_waic_i))
+    with np.errstate(all="ignore"):
+        p_loo_i = lppd_i - elpd_loo_i
+        elpd_waic_i = lppd_i - p_waic_i
+        thr = min(1.0 - 1.0 / np.log10(float(S)), 0.7) if S > 1 else float("-inf")
+    return LOO(elpd_loo_i, pareto_k, np.asarray(n_tail, dtype=np.int64), lppd_i, p_waic_i, p_loo_i, elpd_waic_i,
+               float(elpd_loo_i.sum()), float(p_loo_i.sum()), float(elpd_waic_i.sum()), float(p_waic_i.sum()),
+               _pointwise_se(elpd_loo_i), _pointwise_se(elpd_waic_i), float(thr), np.flatnonzero(pareto_k > thr),
+               list(names) if names is not None else None)
+
+
+def loo_compare(a, b):
+    """(elpd_diff, se_diff) of two ``LOO`` records of the same observations, a minus b: the sum of the paired differences of
+    elpd_loo_i and sqrt(nobs * var(differences, divisor nobs - 1)).  Host code."""
+    if a.elpd_loo_i.shape != b.elpd_loo_i.shape:
+        raise ValueError("the two records must cover the same observations")
+    diff = a.elpd_loo_i - b.elpd_loo_i
+    return float(diff.sum()), _pointwise_se(diff)
+
+
+def psis_tail_length(S, r_eff=1.0):
+    """demcz_psis_tail_length (host code, no device): M = ceil(min(S / 5, 3 sqrt(S / r_eff)))."""
+    M = C.c_int64()
+    rc = _lib.load().demcz_psis_tail_length(int(S), float(r_eff), C.byref(M))
+    if rc != 0:
+        raise DemczError(rc, "demcz_psis_tail_length: S >= 1 and r_eff in (0, inf)")
+    return M.value
+
+
+def gpd_fit(x_ascending):
+    """demcz_gpd_fit (host code, no device): (k, sigma, khat) of n >= 5 exceedances in ascending order."""
+    x = np.ascontiguousarray(x_ascending, dtype=np.float64)
+    k, sigma, khat = C.c_double(), C.c_double(), C.c_double()
+    rc = _lib.load().demcz_gpd_fit(x.size, _lib.ptr(x), C.byref(k), C.byref(sigma), C.byref(khat))
+    if rc != 0:
+        raise DemczError(rc, "demcz_gpd_fit: at least 5 exceedances")
+    return k.value, sigma.value, khat.value
+
+
+def _loo_outputs(n):
+    return np.empty(n), np.empty(n), np.zeros(n, dtype=np.int64), np.empty(n), np.empty(n)
+
+
+def _r_eff_arg(r_eff, n):
+    if r_eff is None:
+        return None
+    r = np.ascontiguousarray(np.broadcast_to(np.asarray(r_eff, dtype=np.float64), (n,)))
+    return r
+
+
 def rank_to_z(r, S):
     """demcz_rank_to_z (host code, no device): the normal scores of average ranks r (1 <= r <= S) among S draws, by the operation
     sequence the device runs (Blom's offsets, Wichura's AS 241)."""
@@ -242,6 +309,44 @@ class _HistoryStatistics:
         self._chk(self._L.demcz_indicator_le(self._h, int(g_from), int(g_to), thr.shape[1], _lib.ptr(thr), C.byref(out)))
         return DerivedHistory(self._L, out, self.N, self.d * thr.shape[1], int(g_from), int(g_to), None, getattr(self, "chain_id0", 0))
 
+    def pointwise(self, program, g_from, g_to, obs_from=0, obs_to=None):
+        """The log-likelihoods of observations obs_from .. obs_to - 1 (default: to the program's last; at most 32 of them) of
+        ``program`` (a ``PointwiseProgram``) at every draw of generations g_from..g_to, on the device (demcz_pointwise): a
+        ``DerivedHistory`` with one column per observation.  Its ``ess`` over the draws' ``N w`` gives an ``r_eff``."""
+        if program.d != self.d:
+            raise ValueError("the program's d is not the history's")
+        obs_from = int(obs_from)
+        obs_to = program.nobs if obs_to is None else int(obs_to)
+        if not 0 <= obs_from < obs_to <= program.nobs:
+            raise ValueError("need 0 <= obs_from < obs_to <= nobs")
+        src, opts, data, ndata = program._args()
+        out = C.c_void_p()
+        self._chk(self._L.demcz_pointwise(self._h, int(g_from), int(g_to), obs_from, obs_to - obs_from, src, opts, data, ndata, C.byref(out)))
+        names = None if program.names is None else program.names[obs_from:obs_to]
+        return DerivedHistory(self._L, out, self.N, obs_to - obs_from, int(g_from), int(g_to), names, getattr(self, "chain_id0", 0))
+
+    def loo_columns(self, g_from, g_to, r_eff=None):
+        """PSIS-LOO and WAIC with the d columns of this history taken as the pointwise log-likelihoods of d observations over
+        generations g_from..g_to (demcz_loo_columns): a ``LOO`` record.  ``r_eff``: a value or d values in (0, inf)."""
+        e, k, n, l, w = _loo_outputs(self.d)
+        r = _r_eff_arg(r_eff, self.d)
+        self._chk(self._L.demcz_loo_columns(self._h, int(g_from), int(g_to), _lib.ptr(r), _lib.ptr(e), _lib.ptr(k), _lib.ptr(n, _lib._lp),
+                                            _lib.ptr(l), _lib.ptr(w)))
+        return loo_record(e, k, n, l, w, self.N * (int(g_to) - int(g_from) + 1), getattr(self, "names", None))
+
+    def loo(self, program, g_from, g_to, r_eff=None):
+        """PSIS-LOO and WAIC of ``program`` (a ``PointwiseProgram``) over generations g_from..g_to (demcz_loo): the observations
+        are evaluated, reduced and dropped in chunks on the device; a ``LOO`` record.  ``r_eff``: a value or nobs values."""
+        if program.d != self.d:
+            raise ValueError("the program's d is not the history's")
+        nobs = program.nobs
+        e, k, n, l, w = _loo_outputs(nobs)
+        r = _r_eff_arg(r_eff, nobs)
+        src, opts, data, ndata = program._args()
+        self._chk(self._L.demcz_loo(self._h, int(g_from), int(g_to), nobs, src, opts, data, ndata, _lib.ptr(r), _lib.ptr(e), _lib.ptr(k),
+                                    _lib.ptr(n, _lib._lp), _lib.ptr(l), _lib.ptr(w)))
+        return loo_record(e, k, n, l, w, self.N * (int(g_to) - int(g_from) + 1), program.names)
+
     def rank_diagnostics(self, g_from, g_to):
         """Rank-normalised split R-hat, bulk-ESS and tail-ESS per parameter over generations g_from..g_to (demcz_rank_diagnostics):
         a RankDiagnostics tuple."""
@@ -254,7 +359,7 @@ class _HistoryStatistics:
 class DerivedHistory(_HistoryStatistics):
     """An N x m x w history of derived quantities on the device (``demcz_derive``): generations ``g_from..g_to``, numbered as in
     the history it came from.  ``rhat``, ``rhat_partial``, ``autocov_sums``, ``ess``, ``select_counts``, ``quantiles``, ``mean_cov``,
-    ``derive``, ``rank_normalize``, ``indicator_le`` and ``rank_diagnostics`` are ``HipEngine``'s; nothing else of an engine applies (the library answers ERR_STATE)."""
+    ``derive``, ``rank_normalize``, ``indicator_le``, ``rank_diagnostics``, ``pointwise``, ``loo_columns`` and ``loo`` are ``HipEngine``'s; nothing else of an engine applies (the library answers ERR_STATE)."""
 
     def __init__(self, L, handle, N, m, g_from, g_to, names=None, chain_id0=0):
         self._L, self._h = L, handle

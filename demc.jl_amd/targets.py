@@ -182,5 +182,45 @@ class DerivedProgram:
             raise _lib.DemczError(rc, (L.demcz_last_error(None) or b"").decode())
 
 
+class PointwiseProgram:
+    """The log-likelihood of every observation at a draw, written as HIP C++ and run on the device over a history
+    (``demcz_pointwise`` and ``demcz_loo``, include/demcz.h): the input of PSIS-LOO and WAIC.
+
+    ``source`` defines ``__device__ double demcz_loglik(const double* x, const double* data, int64_t ndata, int64_t i)``: ``x``
+    holds the ``DEMCZ_D`` (= ``d``) parameters of one draw, ``data`` the ``ndata`` doubles of ``data`` (device memory,
+    read-only, NULL without data), ``i`` the observation, ``0 <= i < nobs``.  Compiled like a ``DerivedProgram``:
+    ``-O3 -ffp-contract=off`` followed by ``options``.  ``d`` must be in 1..32; ``names`` optionally labels the observations.
+
+    It must be a pure function of its arguments.  A lane keeps its draw in registers while it walks the observations; indexing
+    ``x`` with a run-time value sends it to scratch memory, loops over the compile-time ``DEMCZ_D`` unroll and avoid that.
+
+    Used through ``HipEngine.pointwise`` and ``HipEngine.loo``, ``demc.pointwise_chain`` and ``demc.loo_chain``.
+    """
+
+    def __init__(self, source: str, d: int, nobs: int, data=None, options=(), names=None):
+        self.source = str(source)
+        self.d, self.nobs = int(d), int(nobs)
+        if self.nobs < 1:
+            raise ValueError("nobs must be at least 1")
+        self.data = None if data is None else np.ascontiguousarray(np.ravel(data), dtype=np.float64)
+        self.options = (options,) if isinstance(options, str) else tuple(str(o) for o in options)
+        self.names = None if names is None else [str(n) for n in names]
+        if self.names is not None and len(self.names) != self.nobs:
+            raise ValueError("names must hold nobs labels")
+
+    def _args(self):
+        """(source, options, data pointer or None, ndata) as the C ABI takes them; the data array is kept alive by self."""
+        n = 0 if self.data is None else self.data.size
+        return self.source.encode(), " ".join(self.options).encode(), (_lib.ptr(self.data) if n else None), n
+
+    def check(self):
+        """Compile the program (no device needed); raises ``DemczError`` with the compiler log if it does not compile."""
+        L = _lib.load()
+        src, opts, _, _ = self._args()
+        rc = L.demcz_pointwise_check(self.d, src, opts)
+        if rc != 0:
+            raise _lib.DemczError(rc, (L.demcz_last_error(None) or b"").decode())
+
+
 def is_device_target(obj) -> bool:
     return isinstance(obj, (MvNormalTarget, IsoQuadTarget, LinRegSSETarget, ProgramTarget))

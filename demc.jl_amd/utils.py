@@ -197,6 +197,57 @@ def derive_chain(chain, log_obj, program, device_id=0):
     return DerivedHistory(L, out, N, program.m, 1, G, program.names)
 
 
+def pointwise_chain(chain, program, obs_from=0, obs_to=None, device_id=0):
+    """The log-likelihoods of observations obs_from .. obs_to - 1 (at most 32) of ``program`` (a ``PointwiseProgram``) at every
+    draw of an Npop x Npar x Ngeneration history -- a ``DerivedHistory`` on the device, generations 1..Ngeneration
+    (demcz_pointwise_array).  Not in the reference."""
+    from .engine import DerivedHistory
+    chain = _lib.f64(chain, "F")
+    N, d, G = chain.shape
+    if program.d != d:
+        raise ValueError("the program's d is not the chain's Npar")
+    obs_from = int(obs_from)
+    obs_to = program.nobs if obs_to is None else int(obs_to)
+    if not 0 <= obs_from < obs_to <= program.nobs:
+        raise ValueError("need 0 <= obs_from < obs_to <= nobs")
+    src, opts, data, ndata = program._args()
+    L = _lib.load()
+    out = C.c_void_p()
+    _chk(L.demcz_pointwise_array(device_id, _lib.ptr(chain), N, d, G, obs_from, obs_to - obs_from, src, opts, data, ndata, C.byref(out)))
+    names = None if program.names is None else program.names[obs_from:obs_to]
+    return DerivedHistory(L, out, N, obs_to - obs_from, 1, G, names)
+
+
+def loo_columns_chain(loglik, r_eff=None, names=None, device_id=0):
+    """PSIS-LOO and WAIC of an Npop x nobs x Ngeneration array of pointwise log-likelihoods computed elsewhere
+    (demcz_loo_columns_array): a ``LOO`` record.  ``r_eff``: a value or nobs values in (0, inf).  Not in the reference."""
+    from .engine import loo_record, _loo_outputs, _r_eff_arg
+    loglik = _lib.f64(loglik, "F")
+    N, nobs, G = loglik.shape
+    e, k, n, l, w = _loo_outputs(nobs)
+    r = _r_eff_arg(r_eff, nobs)
+    _chk(_lib.load().demcz_loo_columns_array(device_id, _lib.ptr(loglik), N, nobs, G, _lib.ptr(r), _lib.ptr(e), _lib.ptr(k),
+                                             _lib.ptr(n, _lib._lp), _lib.ptr(l), _lib.ptr(w)))
+    return loo_record(e, k, n, l, w, N * G, names)
+
+
+def loo_chain(chain, program, r_eff=None, device_id=0):
+    """PSIS-LOO and WAIC of ``program`` (a ``PointwiseProgram``) over every draw of an Npop x Npar x Ngeneration history
+    (demcz_loo_array): a ``LOO`` record.  Not in the reference."""
+    from .engine import loo_record, _loo_outputs, _r_eff_arg
+    chain = _lib.f64(chain, "F")
+    N, d, G = chain.shape
+    if program.d != d:
+        raise ValueError("the program's d is not the chain's Npar")
+    nobs = program.nobs
+    e, k, n, l, w = _loo_outputs(nobs)
+    r = _r_eff_arg(r_eff, nobs)
+    src, opts, data, ndata = program._args()
+    _chk(_lib.load().demcz_loo_array(device_id, _lib.ptr(chain), N, d, G, nobs, src, opts, data, ndata, _lib.ptr(r), _lib.ptr(e),
+                                     _lib.ptr(k), _lib.ptr(n, _lib._lp), _lib.ptr(l), _lib.ptr(w)))
+    return loo_record(e, k, n, l, w, N * G, program.names)
+
+
 def convergence_check(chain, log_obj, figure_path=None, verbose=True, parnames=None, device_id=0):
     """(accept_ratio, Rhat) as src/utils.jl:34-94 returns them (the plotting part is commented out
     in the reference and is not reproduced)."""

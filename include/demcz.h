@@ -492,8 +492,8 @@ int32_t demcz_best_array(int32_t device_id, const double* log_obj, int64_t N, in
  * the statistics are asked for g_from..g_to or any window inside.  It owns its memory, outlives the handle it came from and is
  * freed by demcz_destroy.  It takes demcz_rhat, demcz_rhat_partial, demcz_autocov_sums, demcz_ess, demcz_select_counts,
  * demcz_quantiles, demcz_mean_cov, demcz_get_history with log_obj = NULL, demcz_synchronize, demcz_last_error, demcz_destroy,
- * demcz_derive (a derived history of a derived history; its logp is NaN) and demcz_rank_normalize, demcz_indicator_le and
- * demcz_rank_diagnostics (below).  Every other call that takes a handle returns
+ * demcz_derive (a derived history of a derived history; its logp is NaN) and demcz_rank_normalize, demcz_indicator_le,
+ * demcz_rank_diagnostics, demcz_pointwise, demcz_loo_columns and demcz_loo (below).  Every other call that takes a handle returns
  * DEMCZ_ERR_STATE on it, with a message that says so. */
 int32_t demcz_derive_check(int32_t d, int32_t m, const char* source, const char* options);
 int32_t demcz_derive(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t m, const char* source, const char* options,
@@ -541,6 +541,63 @@ int32_t demcz_rank_diagnostics(demcz_handle* h, int64_t g_from, int64_t g_to,
                                double* rhat_rank, double* ess_bulk, double* ess_tail);
 int32_t demcz_rank_diagnostics_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G,
                                      double* rhat_rank, double* ess_bulk, double* ess_tail);
+
+/* PSIS-LOO and WAIC (Vehtari, Gelman & Gabry 2017; Vehtari, Simpson, Gelman, Yao & Gabry 2024; the generalised-Pareto fit of
+ * Zhang & Stephens 2009; not in the reference): how well the model predicts each observation it was fitted to, from the history
+ * on the device (DESIGN.md sections 3 and 4.16).  Three layers, each with an entry point of its own.
+ *
+ * 1. Pointwise log-likelihoods.  A pointwise program is HIP C++ that defines
+ *     __device__ double demcz_loglik(const double* x, const double* data, int64_t ndata, int64_t i);
+ * the log-likelihood of observation i at the draw x[0..DEMCZ_D), a pure function of its arguments.  It is compiled like a derive
+ * program (same options, same caches; DEMCZ_D, INFINITY and NAN are defined) into a unit with one streaming kernel: a lane loads
+ * its draw once and walks the observations of the chunk, whose bounds are the same in every lane.  1 <= d <= 32.
+ *   demcz_pointwise_check  compiles the program and needs no device; errors as demcz_derive_check's.
+ *   demcz_pointwise        observations obs_from .. obs_from + mc - 1 (1 <= mc <= 32; the caller keeps them below its number of
+ *                          observations) at every draw of generations g_from..g_to: a DERIVED HISTORY (see demcz_derive) of mc
+ *                          columns whose generations keep their numbers.  Refusals and error codes are demcz_derive's.
+ *   demcz_pointwise_array  the same from a host array N x d x G column-major; generations 1..G.
+ *
+ * 2. demcz_loo_columns treats the d columns of h's history -- a sampling handle, a derived history -- as the log-likelihoods a of d
+ * observations over the window's S = N w draws, each column on its own.  With the column sorted, a_0 <= a_1 <= ..., and
+ * lw_j = a_0 - a_j: M = ceil(min(S / 5, 3 sqrt(S / r_eff))) (r_eff: d values in (0, inf), or NULL for 1); the cutoff
+ * c = max(lw_M, log DBL_MIN); the tail the n elements with lw > c, strictly (ties at the cutoff shorten it); for n >= 5 the
+ * generalised-Pareto fit of the exceedances exp(lw) - exp(c) gives k and sigma, and the tail's weights are replaced by the
+ * fit's quantiles, capped at 0.  Outputs, d values each, any may be NULL:
+ *   elpd_loo   log sum exp(lw' + a) - log sum exp(lw')          pareto_k   (n k + 5) / (n + 10); +inf where n < 5 or k is not finite
+ *   n_tail     n                                                 lppd       log mean exp(a)
+ *   p_waic     the sample variance of a, divisor S - 1 (NaN at S = 1)
+ * A column with a NaN or an infinite entry is NaN in every output with n_tail 0; the other columns are unaffected.  A constant
+ * column gives n_tail 0, pareto_k +inf, elpd_loo = lppd = the constant and p_waic 0.  No floating-point atomics: the same call
+ * gives the same bits, and a column's results do not depend on the columns beside it.  Range and state errors are demcz_rhat's;
+ * like demcz_rank_normalize it sorts in 2 S d words of scratch, takes at most 2^31 - 1 draws per column and refuses a handle
+ * whose communicator has more than one rank.  demcz_loo_columns_array: the same from a host array N x d x G.
+ *   demcz_psis_tail_length  *M of S draws: host code, no device.
+ *   demcz_gpd_fit           k, sigma and the regularised khat of n >= 5 exceedances in ascending order: host code, no device,
+ *                           the per-term functions of the kernel with the sums in index order.
+ *
+ * 3. demcz_loo: the outputs above for observations 0..nobs-1 of a pointwise program, in chunks of observations -- demcz_pointwise,
+ * demcz_loo_columns, the chunk dropped -- of the largest width <= 32 whose scratch (24 bytes per draw and observation) fits
+ * 4 GiB.  r_eff: nobs values or NULL.  The results are demcz_loo_columns's of the same columns, bit for bit.  demcz_loo_array: the
+ * same from a host array.  The relative efficiency of an observation is not computed here: demcz_ess of demcz_pointwise's
+ * history gives it. */
+int32_t demcz_pointwise_check(int32_t d, const char* source, const char* options);
+int32_t demcz_pointwise(demcz_handle* h, int64_t g_from, int64_t g_to, int64_t obs_from, int32_t mc, const char* source,
+                        const char* options, const double* data, int64_t ndata, demcz_handle** derived);
+int32_t demcz_pointwise_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, int64_t obs_from,
+                              int32_t mc, const char* source, const char* options, const double* data, int64_t ndata,
+                              demcz_handle** derived);
+int32_t demcz_psis_tail_length(int64_t S, double r_eff, int64_t* M);
+int32_t demcz_gpd_fit(int64_t n, const double* x_ascending, double* k, double* sigma, double* khat);
+int32_t demcz_loo_columns(demcz_handle* h, int64_t g_from, int64_t g_to, const double* r_eff /* NULL or d values */,
+                          double* elpd_loo, double* pareto_k, int64_t* n_tail, double* lppd, double* p_waic);
+int32_t demcz_loo_columns_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, const double* r_eff,
+                                double* elpd_loo, double* pareto_k, int64_t* n_tail, double* lppd, double* p_waic);
+int32_t demcz_loo(demcz_handle* h, int64_t g_from, int64_t g_to, int64_t nobs, const char* source, const char* options,
+                  const double* data, int64_t ndata, const double* r_eff /* NULL or nobs values */,
+                  double* elpd_loo, double* pareto_k, int64_t* n_tail, double* lppd, double* p_waic);
+int32_t demcz_loo_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, int64_t nobs,
+                        const char* source, const char* options, const double* data, int64_t ndata, const double* r_eff,
+                        double* elpd_loo, double* pareto_k, int64_t* n_tail, double* lppd, double* p_waic);
 
 /* Introspection for benchmarks and tests. */
 int32_t demcz_get_info(const demcz_handle* h, int64_t* M, int64_t* launches_window, int32_t* lanes_per_chain);
