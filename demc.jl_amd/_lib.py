@@ -58,6 +58,8 @@ SYMBOLS = [
     "demcz_set_snooker", "demcz_get_snooker",
     "demcz_pointwise_check", "demcz_pointwise", "demcz_pointwise_array", "demcz_psis_tail_length", "demcz_gpd_fit",
     "demcz_loo_columns", "demcz_loo_columns_array", "demcz_loo", "demcz_loo_array",
+    "demcz_bridge_check", "demcz_bridge_posterior", "demcz_bridge_posterior_array", "demcz_bridge_proposal",
+    "demcz_bridge_proposal_program", "demcz_bridge_iterate", "demcz_bridge", "demcz_bridge_array",
 ]
 
 
@@ -87,10 +89,11 @@ def sources() -> list:
     """The library's translation units: the C ABI with most kernels (demcz_capi.hip), the eight units that instantiate
     window_kernel_pw for every dimension from 6 to 32 (demcz_pw_inst_<g>.hip, csrc/demcz_pw_dispatch.h), the two with the
     sixteen-lane regression kernels for every dimension from 2 to 28 (demcz_mlr_inst_<g>.hip, csrc/demcz_mlr_dispatch.h), the one
-    with the snooker generation's kernels (demcz_snooker_inst.hip, csrc/demcz_kernels_snooker.h) and the host code of program targets (demcz_program.hip: hipRTC, the kernel headers embedded as text)."""
+    with the snooker generation's kernels (demcz_snooker_inst.hip, csrc/demcz_kernels_snooker.h), the one with the bridge-sampling
+    kernels for every dimension from 1 to 32 (demcz_bridge_inst.hip, csrc/demcz_kernels_bridge.h) and the host code of program targets (demcz_program.hip: hipRTC, the kernel headers embedded as text)."""
     csrc = PKG_DIR / "csrc"
     return ([csrc / "demcz_capi.hip"] + sorted(csrc.glob("demcz_pw_inst_*.hip")) + sorted(csrc.glob("demcz_mlr_inst_*.hip"))
-            + [csrc / "demcz_snooker_inst.hip", csrc / "demcz_program.hip"])
+            + [csrc / "demcz_snooker_inst.hip", csrc / "demcz_bridge_inst.hip", csrc / "demcz_program.hip"])
 
 
 def build_command(out: Path = LIB_PATH) -> list:
@@ -239,6 +242,18 @@ def load():
                             _dp, _dp]
     L.demcz_loo_array.argtypes = [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_char_p, C.c_char_p, _dp, C.c_int64,
                                   _dp, _dp, _dp, _lp, _dp, _dp]
+    _bridge_out = [_dp, _dp, _lp, _ip, _lp, _lp, _dp, _lp, _dp, _dp, _dp]
+    L.demcz_bridge_check.argtypes = [C.c_int32, C.c_char_p, C.c_char_p]
+    L.demcz_bridge_posterior.argtypes = [C.c_void_p, C.c_int64, C.c_int64, _dp, _dp, _vpp]
+    L.demcz_bridge_posterior_array.argtypes = [C.c_int32, _dp, _dp, C.c_int64, C.c_int32, C.c_int64, _dp, _dp, _vpp]
+    L.demcz_bridge_proposal.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, _dp, _dp, _vpp, _vpp]
+    L.demcz_bridge_proposal_program.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_uint64, _dp, _dp, C.c_char_p, C.c_char_p,
+                                                _dp, C.c_int64, _vpp, _vpp]
+    L.demcz_bridge_iterate.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_double,
+                                       C.c_int64, _dp, _lp, _ip, _dp, _lp, _vpp]
+    L.demcz_bridge.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_double, C.c_double, C.c_int64] + _bridge_out
+    L.demcz_bridge_array.argtypes = [C.c_int32, _dp, _dp, C.c_int64, C.c_int32, C.c_int64, C.c_char_p, C.c_char_p, _dp, C.c_int64,
+                                     C.c_uint64, C.c_double, C.c_double, C.c_int64] + _bridge_out
     L.demcz_get_archive_pinned.argtypes =[C.c_void_p, C.POINTER(C.c_void_p), _lp]
     L.demcz_get_kernel_time_series.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _ip]
     L.demcz_set_comm_timeout.argtypes = [C.c_void_p, C.c_int64]

@@ -9,6 +9,7 @@
 #include "demcz_select_host.h"
 #include "demcz_kernels_rank.h"
 #include "demcz_kernels_loo.h"
+#include "demcz_kernels_bridge.h"
 #include "demcz_slab_plan.h"
 #include "demcz_run_plan.h"
 #include "demcz_kernels_ml.h"
@@ -30,6 +31,7 @@
 #include <cstdlib>
 #include <deque>
 #include <mutex>
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -416,6 +418,7 @@ struct demcz_handle {
     // cfg.nobs (the TargetParams slots only the regression reads)
     bool prog_ready = false;
     demcz_prog::Module prog;
+    std::string prog_source, prog_options;   // the program's text, for the units compiled later (demcz_bridge: UNIT_BRIDGE)
     // created with DEMCZ_LAYOUT_PROGRAM_WAVE: lanes == DEMCZ_LAYOUT_SPLIT, split_kind == SPLIT_WAVE, and the consumer is the program's own
     // window_kernel_ps / _pw<TARGET_PROGRAM, d, LIVE, TEMPER> (prog.wave); records, producer, LIVE machinery: the library's
     bool prog_wave = false;
@@ -466,7 +469,7 @@ static int32_t refuse_derived(const demcz_handle* h, const char* who)
     if (!h || !h->derived) return DEMCZ_OK;
     return fail(const_cast<demcz_handle*>(h), DEMCZ_ERR_STATE,
                 std::string(who) + ": the handle is a derived history (demcz_derive): it takes the statistics over its values, demcz_get_history "
-                                   "without log_obj, demcz_derive, demcz_pointwise, demcz_loo, demcz_synchronize and demcz_destroy, and nothing else");
+                                   "without log_obj, demcz_derive, demcz_pointwise, demcz_loo, demcz_bridge_iterate, demcz_synchronize and demcz_destroy, and nothing else");
 }
 // first statement of every entry point a derived history does not take (a NULL handle is left to the function's own check)
 #define NOT_DERIVED(h)                                                                           \
@@ -1440,6 +1443,8 @@ extern "C" int32_t demcz_set_program(demcz_handle* h, const char* source, const 
     h->d_design = dd;               // (freed with the handle; TargetParams::design / nobs carry it to the kernels)
     h->cfg.nobs = ndata;
     h->prog = mod;
+    h->prog_source = source;
+    h->prog_options = options ? options : "";
     h->prog_ready = true;
     h->live_wg_cap = -1;            // (wave layout: residency is the program's own kernel's)
     return DEMCZ_OK;
@@ -5212,6 +5217,524 @@ extern "C" int32_t demcz_loo_array(int32_t device_id, const double* chain, int64
     rc = s.open(device_id, N, d, G, chain, nullptr);
     if (rc) return diag_fail(s, rc);
     return diag_fail(s, loo_from(&s.h, 1, G, nobs, source, options, data, ndata, r_eff, elpd_loo, pareto_k, n_tail, lppd, p_waic));
+}
+
+// ---- the marginal likelihood by bridge sampling (K12, demcz_kernels_bridge.h; DESIGN.md sections 3 and 4.17) ---------------------
+extern "C" int32_t demcz_bridge_check(int32_t d, const char* source, const char* options)
+{
+    std::shared_ptr<const demcz_prog::Code> code;
+    std::string err;
+    if (demcz_prog::get_code(d, source, options, demcz_prog::UNIT_BRIDGE, code, err) != 0) return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, err);
+    return DEMCZ_OK;
+}
+
+namespace {
+// dm_log of demcz_device.h on the host: the same operations on the same bits
+double bridge_dm_log_host(double x)
+{
+    const double LN2_HI = 6.93147180369123816490e-01, LN2_LO = 1.90821492927058770002e-10;
+    const double LG1 = 6.666666666666735130e-01, LG2 = 3.999999999940941908e-01, LG3 = 2.857142874366239149e-01,
+                 LG4 = 2.222219843214978396e-01, LG5 = 1.818357216161805012e-01, LG6 = 1.531383769920937332e-01,
+                 LG7 = 1.479819860511658591e-01;
+    uint64_t b;
+    std::memcpy(&b, &x, 8);
+    uint32_t hx = (uint32_t)(b >> 32);
+    const uint32_t lx = (uint32_t)b;
+    hx += 0x3ff00000u - 0x3fe6a09eu;
+    const int k = (int)(hx >> 20) - 0x3ff;
+    hx = (hx & 0x000fffffu) + 0x3fe6a09eu;
+    const uint64_t rb = ((uint64_t)hx << 32) | lx;
+    double xr;
+    std::memcpy(&xr, &rb, 8);
+    const double f = xr - 1.0, hfsq = (0.5 * f) * f, s = f / (2.0 + f), z = s * s, w = z * z;
+    const double t1 = w * (LG2 + w * (LG4 + w * LG6)), t2 = z * (LG1 + w * (LG3 + w * (LG5 + w * LG7)));
+    const double R = t2 + t1, dk = (double)k;
+    return ((((s * (hfsq + R)) + (dk * LN2_LO)) - hfsq) + f) + (dk * LN2_HI);
+}
+
+// The proposal as the kernels read it: [m | L row-major lower] (bridge_ml_words(d) doubles) and c_g.  L: d x d column-major, its
+// lower triangle; a diagonal entry that is not a positive normal number is refused with the parameter's index.
+int32_t bridge_pack(demcz_handle* h, int d, const double* mean, const double* L, const char* who, std::vector<double>& mL, double& cg)
+{
+    if (d < 1 || d > BRIDGE_MAX_D)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": d must be in 1.." + std::to_string(BRIDGE_MAX_D));
+    mL.resize((size_t)bridge_ml_words(d));
+    for (int p = 0; p < d; ++p) mL[p] = mean[p];
+    cg = 0.0;
+    for (int p = 0; p < d; ++p) {
+        for (int q = 0; q <= p; ++q) mL[(size_t)d + p * (p + 1) / 2 + q] = L[(size_t)p + (size_t)d * q];
+        const double lpp = L[(size_t)p + (size_t)d * p];
+        if (!(lpp >= DBL_MIN) || !(lpp < INFINITY))
+            return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": the diagonal of L must be positive and finite; it is not at parameter " +
+                                                       std::to_string(p));
+        cg += bridge_dm_log_host(lpp);
+    }
+    cg += (0.5 * (double)d) * 1.8378770664093453;        // log 2 pi
+    return DEMCZ_OK;
+}
+
+// L of V = L L^T in plain double, row by row, every inner product in index order; V and L d x d column-major
+int32_t bridge_cholesky(demcz_handle* h, int d, const double* V, double* L, const char* who)
+{
+    for (size_t i = 0; i < (size_t)d * d; ++i) L[i] = 0.0;
+    for (int p = 0; p < d; ++p) {
+        for (int q = 0; q < p; ++q) {
+            double acc = V[(size_t)p + (size_t)d * q];
+            for (int k = 0; k < q; ++k) acc = acc - L[(size_t)p + (size_t)d * k] * L[(size_t)q + (size_t)d * k];
+            L[(size_t)p + (size_t)d * q] = acc / L[(size_t)q + (size_t)d * q];
+        }
+        double acc = V[(size_t)p + (size_t)d * p];
+        for (int k = 0; k < p; ++k) acc = acc - L[(size_t)p + (size_t)d * k] * L[(size_t)p + (size_t)d * k];
+        if (!(acc > 0.0) || !(acc < INFINITY))
+            return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": the fit window's covariance is not positive definite: the pivot of parameter " +
+                                                       std::to_string(p) + " is " + std::to_string(acc) +
+                                                       " (a constant or linearly dependent parameter; a longer window or more chains)");
+        L[(size_t)p + (size_t)d * p] = std::sqrt(acc);
+    }
+    return DEMCZ_OK;
+}
+
+void bridge_free(demcz_handle*& dh)
+{
+    if (!dh) return;
+    free_all(dh);
+    delete dh;
+    dh = nullptr;
+}
+
+unsigned bridge_blocks(int64_t total) { return (unsigned)std::min<int64_t>((total + DERIVE_THREADS - 1) / DERIVE_THREADS, DERIVE_MAX_WG); }
+
+// demcz_bridge_posterior on a source with a chain and a log_obj history (a sampling handle, a ScratchHandle)
+int32_t bridge_posterior_from(demcz_handle* h, int64_t g_from, int64_t g_to, const double* mean, const double* L, demcz_handle** derived)
+{
+    const char* who = "demcz_bridge_posterior";
+    int32_t rc = check_hist_range(h, g_from, g_to, who);
+    if (rc) return rc;
+    if (!h->dlogobj || !h->dchain) return fail(h, DEMCZ_ERR_STATE, std::string(who) + ": the source keeps no log_obj history");
+    const int d = h->cfg.d;
+    std::vector<double> mL;
+    double cg = 0.0;
+    rc = bridge_pack(h, d, mean, L, who, mL, cg);
+    if (rc) return rc;
+    const void* fn = bridge_posterior_fn(d);
+    if (!fn) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": no kernel for this d");
+    HIPCHK(h, hipSetDevice(h->cfg.device_id));
+    rc = live_verify(h);
+    if (rc) return rc;
+    rc = quiesce_all(h);                        // (the allocations below may synchronise the device)
+    if (rc) return rc;
+    int64_t N = h->cfg.N, w = g_to - g_from + 1, s0 = g_from - h->g0 - 1, total = N * w;
+    std::string err;
+    // (the proposal rides in the derived history's data slot: freed with it)
+    demcz_handle* dh = derived_create(h->cfg.device_id, N, 1, w, g_from - 1, mL.data(), (int64_t)mL.size(), err, who);
+    if (!dh) return fail(h, DEMCZ_ERR_HIP, err);
+    const double* chain = h->dchain;
+    const double* logobj = h->dlogobj;
+    const double* dmL = dh->d_design;
+    double* out = dh->dchain;
+    void* args[] = {&chain, &logobj, &N, &s0, &total, &dmL, &cg, &out};
+    hipError_t e = hipLaunchKernel(fn, dim3(bridge_blocks(total)), dim3(DERIVE_THREADS), args, 0, h->stream);
+    if (e != hipSuccess) h->err = std::string(who) + ": launching bridge_posterior_kernel: " + hipGetErrorString(e);
+    rc = (e != hipSuccess) ? DEMCZ_ERR_HIP : sync_stream(h, h->stream, who);
+    if (rc) {
+        if (rc == DEMCZ_ERR_HIP) (void)hipDeviceSynchronize();      // (the kernel may still be writing what is about to be freed)
+        bridge_free(dh);
+        return rc;
+    }
+    *derived = dh;
+    return DEMCZ_OK;
+}
+
+// What evaluates the target at the proposal's draws: a built-in target's kernel with its parameters, or a program's bridge unit
+struct BridgeTarget {
+    const void* fn = nullptr;                   // built-in: bridge_proposal_kernel<T, d>
+    TargetParams tp{};
+    hipFunction_t prog = nullptr;               // program: bridge_proposal_program_kernel
+    const double* data = nullptr;               // program: device memory that outlives the call, or null: `hdata` is uploaded
+    const double* hdata = nullptr;
+    int64_t ndata = 0;
+};
+
+// the handle's own target
+int32_t bridge_target_of(demcz_handle* h, const char* who, BridgeTarget& t)
+{
+    const int d = h->cfg.d;
+    if (d < 1 || d > BRIDGE_MAX_D)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": d must be in 1.." + std::to_string(BRIDGE_MAX_D));
+    if (h->cfg.target_kind == DEMCZ_TARGET_PROGRAM) {
+        if (!h->prog_ready) return fail(h, DEMCZ_ERR_STATE, "program target: call demcz_set_program first");
+        std::shared_ptr<const demcz_prog::Code> code;
+        std::string err;
+        if (demcz_prog::get_code(d, h->prog_source.c_str(), h->prog_options.c_str(), demcz_prog::UNIT_BRIDGE, code, err) != 0)
+            return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, err);
+        demcz_prog::Module mod;
+        if (demcz_prog::get_module(code, h->cfg.device_id, mod, err) != 0) return fail(h, DEMCZ_ERR_HIP, err);
+        t.prog = mod.derive;
+        t.data = h->cfg.nobs > 0 ? h->d_design : nullptr;
+        t.ndata = h->cfg.nobs;
+        return DEMCZ_OK;
+    }
+    if (h->cfg.target_kind == DEMCZ_TARGET_HOST_CALLBACK)
+        return fail(h, DEMCZ_ERR_STATE, std::string(who) + ": a host-closure handle has no target on the device: bridge sampling needs a "
+                                                           "built-in or a program target");
+    t.fn = bridge_proposal_fn(h->cfg.target_kind, d);
+    if (!t.fn) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": no kernel for this target and d");
+    t.tp = target_params(h);
+    return DEMCZ_OK;
+}
+
+// a program given as text
+int32_t bridge_target_program(demcz_handle* h, int d, const char* source, const char* options, const double* data, int64_t ndata,
+                              const char* who, BridgeTarget& t)
+{
+    if (ndata < 0 || (ndata > 0 && !data)) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": need ndata >= 0 and data for ndata > 0");
+    std::shared_ptr<const demcz_prog::Code> code;
+    std::string err;
+    if (demcz_prog::get_code(d, source, options, demcz_prog::UNIT_BRIDGE, code, err) != 0) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, err);
+    demcz_prog::Module mod;
+    if (demcz_prog::get_module(code, h->cfg.device_id, mod, err) != 0) return fail(h, DEMCZ_ERR_HIP, err);
+    t.prog = mod.derive;
+    t.hdata = data;
+    t.ndata = ndata;
+    return DEMCZ_OK;
+}
+
+// demcz_bridge_proposal on h's device and stream: Np x wp draws of N(mean, L L^T), a2 and on request the draws
+int32_t bridge_proposal_from(demcz_handle* h, int d, const BridgeTarget& t, int64_t Np, int64_t wp, uint64_t seed, const double* mean,
+                             const double* L, demcz_handle** logratio, demcz_handle** draws)
+{
+    const char* who = "demcz_bridge_proposal";
+    if (Np < 1 || wp < 1 || Np > ((int64_t)1 << 40) / wp)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": need Np >= 1, wp >= 1 and at most 2^40 draws");
+    std::vector<double> mL;
+    double cg = 0.0;
+    int32_t rc = bridge_pack(h, d, mean, L, who, mL, cg);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device_id));
+    rc = quiesce_all(h);                        // (the allocations below may synchronise the device)
+    if (rc) return rc;
+    std::string err;
+    // the proposal and, behind it, a program's data ride in the a2 history's data slot
+    std::vector<double> slot(mL);
+    if (t.hdata && t.ndata > 0) slot.insert(slot.end(), t.hdata, t.hdata + t.ndata);
+    demcz_handle* da = derived_create(h->cfg.device_id, Np, 1, wp, 0, slot.data(), (int64_t)slot.size(), err, who);
+    if (!da) return fail(h, DEMCZ_ERR_HIP, err);
+    demcz_handle* dx = nullptr;
+    if (draws) {
+        dx = derived_create(h->cfg.device_id, Np, d, wp, 0, nullptr, 0, err, who);
+        if (!dx) { bridge_free(da); return fail(h, DEMCZ_ERR_HIP, err); }
+    }
+    int64_t N = Np, total = Np * wp, ndata = t.ndata;
+    const double* dmL = da->d_design;
+    const double* ddata = t.data ? t.data : (t.hdata && t.ndata > 0) ? da->d_design + mL.size() : nullptr;
+    double* a2 = da->dchain;
+    double* xs = dx ? dx->dchain : nullptr;
+    hipError_t e;
+    if (t.prog) {
+        void* args[] = {&N, &total, &seed, &dmL, &cg, &ddata, &ndata, &a2, &xs};
+        e = hipModuleLaunchKernel(t.prog, bridge_blocks(total), 1, 1, DERIVE_THREADS, 1, 1, 0, h->stream, args, nullptr);
+    } else {
+        TargetParams tp = t.tp;
+        void* args[] = {&tp, &N, &total, &seed, &dmL, &cg, &a2, &xs};
+        e = hipLaunchKernel(t.fn, dim3(bridge_blocks(total)), dim3(DERIVE_THREADS), args, 0, h->stream);
+    }
+    if (e != hipSuccess) h->err = std::string(who) + ": launching bridge_proposal_kernel: " + hipGetErrorString(e);
+    rc = (e != hipSuccess) ? DEMCZ_ERR_HIP : sync_stream(h, h->stream, who);
+    if (rc) {
+        if (rc == DEMCZ_ERR_HIP) (void)hipDeviceSynchronize();      // (the kernel may still be writing what is about to be freed)
+        bridge_free(da);
+        bridge_free(dx);
+        return rc;
+    }
+    *logratio = da;
+    if (draws) *draws = dx;
+    return DEMCZ_OK;
+}
+
+// updates queued between two synchronisations (DEMCZ_BRIDGE_BATCH: 1..64; the result does not depend on it)
+int bridge_batch()
+{
+    if (const char* s = getenv("DEMCZ_BRIDGE_BATCH"); s && *s) {
+        const long v = strtol(s, nullptr, 10);
+        if (v >= 1 && v <= 64) return (int)v;
+    }
+    return 4;
+}
+
+struct BridgeResult {
+    double logml = NAN, moments[4] = {NAN, NAN, NAN, NAN};
+    int64_t iterations = 0, n_nan = 0;
+    int32_t converged = 0;
+};
+
+int32_t bridge_iterate_from(demcz_handle* post, int64_t g_from, int64_t g_to, demcz_handle* prop, int64_t gp_from, int64_t gp_to, double neff,
+                            double tol, int64_t max_iter, BridgeResult& res, demcz_handle** f2)
+{
+    const char* who = "demcz_bridge_iterate";
+    int32_t rc = check_hist_range(post, g_from, g_to, who);
+    if (rc) return rc;
+    rc = check_hist_range(prop, gp_from, gp_to, who);
+    if (rc) { post->err = prop->err; return rc; }
+    if (post->cfg.d != 1 || prop->cfg.d != 1 || !post->dchain || !prop->dchain)
+        return fail(post, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": both histories must have one column");
+    if (post->cfg.device_id != prop->cfg.device_id)
+        return fail(post, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": the two histories must be on one device");
+    if ((post->comm && post->nranks > 1) || (prop->comm && prop->nranks > 1)) return rank_refuse_sharded(post->comm ? post : prop, who);
+    if (!(tol >= 0.0) || max_iter < 1 || neff != neff)
+        return fail(post, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": need tol >= 0, max_iter >= 1 and neff a number");
+    int64_t n1 = post->cfg.N * (g_to - g_from + 1), n2 = prop->cfg.N * (gp_to - gp_from + 1);
+    HIPCHK(post, hipSetDevice(post->cfg.device_id));
+    rc = live_verify(post);
+    if (rc) return rc;
+    rc = live_verify(prop);
+    if (rc) { post->err = prop->err; return rc; }
+    rc = quiesce_all(post);
+    if (rc) return rc;
+    rc = sync_stream(prop, prop->stream, who);  // (what wrote a2 ran on its own stream)
+    if (rc) { post->err = prop->err; return rc; }
+    const double ne = (neff > 0.0) ? neff : (double)n1;
+    double s1 = ne / (ne + (double)n2), s2 = 1.0 - s1;
+    const double* a1 = post->dchain + post->cfg.N * (g_from - post->g0 - 1);
+    const double* a2 = prop->dchain + prop->cfg.N * (gp_from - prop->g0 - 1);
+    int64_t ntiles = (std::max(n1, n2) + BRIDGE_TILE - 1) / BRIDGE_TILE;
+    std::string err;
+    demcz_handle* df = nullptr;
+    if (f2) {
+        df = derived_create(post->cfg.device_id, post->cfg.N, 1, g_to - g_from + 1, g_from - 1, nullptr, 0, err, who);
+        if (!df) return fail(post, DEMCZ_ERR_HIP, err);
+    }
+    // [state | part (2 ntiles BRIDGE_NPART doubles)]
+    const size_t st_bytes = (sizeof(BridgeState) + 7) / 8 * 8;
+    void* base = nullptr;
+    hipError_t e = dev_malloc(post->cfg.device_id, &base, st_bytes + (size_t)2 * ntiles * BRIDGE_NPART * 8);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        bridge_free(df);
+        return fail(post, DEMCZ_ERR_HIP, std::string(who) + ": the tile sums: " + hipGetErrorString(e));
+    }
+    BridgeState* st = static_cast<BridgeState*>(base);
+    double* part = reinterpret_cast<double*>(static_cast<char*>(base) + st_bytes);
+    double* f2out = df ? df->dchain : nullptr;
+    BridgeState hs;
+    const int batch = bridge_batch();
+    hipStream_t s = post->stream;
+    auto body = [&]() -> int32_t {
+        HIPCHK(post, hipMemsetAsync(st, 0, st_bytes, s));
+        int64_t tiles1 = (n1 + BRIDGE_TILE - 1) / BRIDGE_TILE;               // (<= ntiles: the maxima fit in part)
+        for (int stage = 0; stage < 2; ++stage) {
+            void* args[] = {&a1, &n1, &tiles1, &stage, &part, &st};
+            HIPCHK(post, hipLaunchKernel(bridge_rho0_fn(), dim3(stage ? 1u : (unsigned)tiles1), dim3(BRIDGE_BS), args, 0, s));
+        }
+        long long mi = (long long)max_iter;
+        auto round = [&](int final) -> hipError_t {
+            double* fo = final ? f2out : nullptr;
+            void* sa[] = {&a2, &n2, &a1, &n1, &s1, &s2, &final, &st, &part, &fo};
+            hipError_t e2 = hipLaunchKernel(bridge_sum_fn(), dim3((unsigned)ntiles, 2), dim3(BRIDGE_BS), sa, 0, s);
+            if (e2 != hipSuccess) return e2;
+            void* fa[] = {&part, &ntiles, &n2, &n1, &tol, &mi, &final, &st};
+            return hipLaunchKernel(bridge_finish_fn(), dim3(1), dim3(64), fa, 0, s);
+        };
+        for (int64_t queued = 0;;) {
+            for (int b = 0; b < batch && queued < max_iter; ++b, ++queued) HIPCHK(post, round(0));
+            HIPCHK(post, hipMemcpyAsync(&hs, st, sizeof(BridgeState), hipMemcpyDeviceToHost, s));
+            int32_t r2 = sync_stream(post, s, who);
+            if (r2) return r2;
+            if (hs.done || queued >= max_iter) break;
+        }
+        HIPCHK(post, round(1));
+        HIPCHK(post, hipMemcpyAsync(&hs, st, sizeof(BridgeState), hipMemcpyDeviceToHost, s));
+        return sync_stream(post, s, who);
+    };
+    rc = body();
+    if (rc == DEMCZ_ERR_HIP) (void)hipDeviceSynchronize();          // (a kernel may still be writing what is about to be freed)
+    (void)dev_free(post->cfg.device_id, base);
+    if (rc) {
+        bridge_free(df);
+        return rc;
+    }
+    res.logml = hs.rho;
+    res.iterations = (int64_t)hs.iterations;
+    res.converged = hs.converged;
+    res.n_nan = (int64_t)hs.n_nan;
+    const bool ok = hs.rho == hs.rho;
+    res.moments[0] = ok ? hs.mean[0] : NAN;
+    res.moments[1] = ok ? hs.var[0] : NAN;
+    res.moments[2] = ok ? hs.mean[1] : NAN;
+    res.moments[3] = ok ? hs.var[1] : NAN;
+    if (f2) *f2 = df;
+    return DEMCZ_OK;
+}
+
+struct BridgeOut {
+    double *logml, *se_logml;
+    int64_t* iterations;
+    int32_t* converged;
+    int64_t *n_post, *n_prop;
+    double* neff;
+    int64_t* n_nan;
+    double *ess_f2, *mean, *L;
+};
+
+// the whole pipeline on a source with chain and log_obj; `t` evaluates the target
+int32_t bridge_from(demcz_handle* h, const BridgeTarget& t, int64_t g_from, int64_t g_to, uint64_t seed, double neff, double tol,
+                    int64_t max_iter, const BridgeOut& o)
+{
+    const char* who = "demcz_bridge";
+    int32_t rc = rank_refuse_sharded(h, who);
+    if (rc) return rc;
+    rc = check_hist_range(h, g_from, g_to, who);
+    if (rc) return rc;
+    const int64_t w = g_to - g_from + 1, hw = w / 2, N = h->cfg.N;
+    if (w < 4) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_bridge: window needs at least 4 generations");
+    const int d = h->cfg.d;
+    if (d > BRIDGE_MAX_D) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_bridge: d must be in 1.." + std::to_string(BRIDGE_MAX_D));
+    std::vector<double> m((size_t)d), V((size_t)d * d), L((size_t)d * d);
+    rc = demcz_mean_cov(h, g_from, g_from + hw - 1, m.data(), V.data());
+    if (rc) return rc;
+    rc = bridge_cholesky(h, d, V.data(), L.data(), who);
+    if (rc) return rc;
+    demcz_handle *post = nullptr, *prop = nullptr, *f2 = nullptr;
+    BridgeResult res;
+    double ess = NAN;
+    rc = bridge_posterior_from(h, g_from + hw, g_to, m.data(), L.data(), &post);
+    if (!rc) rc = bridge_proposal_from(h, d, t, N, w - hw, seed, m.data(), L.data(), &prop, nullptr);
+    if (!rc) rc = bridge_iterate_from(post, g_from + hw, g_to, prop, 1, w - hw, neff, tol, max_iter, res, &f2);
+    if (rc && post && !post->err.empty() && h->err.empty()) h->err = post->err;
+    if (!rc && res.logml == res.logml && w - hw >= 4) {
+        int32_t conv = 0;
+        rc = rank_part(h, f2, demcz_ess(f2, g_from + hw, g_to, 0, &ess, nullptr, nullptr, nullptr, &conv));
+    }
+    rank_drop(f2);
+    rank_drop(prop);
+    rank_drop(post);
+    if (rc) return rc;
+    const int64_t n1 = N * (w - hw), n2 = n1;
+    double se = NAN;
+    if (res.logml == res.logml) {
+        const double re2 = res.moments[1] / ((double)n2 * (res.moments[0] * res.moments[0])) +
+                           res.moments[3] / (ess * (res.moments[2] * res.moments[2]));
+        se = std::sqrt(re2);
+    }
+    if (o.logml) *o.logml = res.logml;
+    if (o.se_logml) *o.se_logml = se;
+    if (o.iterations) *o.iterations = res.iterations;
+    if (o.converged) *o.converged = res.converged;
+    if (o.n_post) *o.n_post = n1;
+    if (o.n_prop) *o.n_prop = n2;
+    if (o.neff) *o.neff = (neff > 0.0) ? neff : (double)n1;
+    if (o.n_nan) *o.n_nan = res.n_nan;
+    if (o.ess_f2) *o.ess_f2 = ess;
+    if (o.mean) std::copy(m.begin(), m.end(), o.mean);
+    if (o.L) std::copy(L.begin(), L.end(), o.L);
+    return DEMCZ_OK;
+}
+}  // namespace
+
+extern "C" int32_t demcz_bridge_posterior(demcz_handle* h, int64_t g_from, int64_t g_to, const double* mean, const double* L,
+                                          demcz_handle** derived)
+{
+    if (derived) *derived = nullptr;
+    NOT_DERIVED(h);
+    if (!h || !derived || !mean || !L) return DEMCZ_ERR_INVALID_ARGUMENT;
+    DEADCHK(h);
+    return bridge_posterior_from(h, g_from, g_to, mean, L, derived);
+}
+
+extern "C" int32_t demcz_bridge_posterior_array(int32_t device_id, const double* chain, const double* log_obj, int64_t N, int32_t d,
+                                                int64_t G, const double* mean, const double* L, demcz_handle** derived)
+{
+    if (derived) *derived = nullptr;
+    if (!chain || !log_obj || !derived || !mean || !L) return DEMCZ_ERR_INVALID_ARGUMENT;
+    ScratchHandle s;
+    int32_t rc = s.open(device_id, N, d, G, chain, log_obj);
+    if (rc) return diag_fail(s, rc);
+    return diag_fail(s, bridge_posterior_from(&s.h, 1, G, mean, L, derived));
+}
+
+extern "C" int32_t demcz_bridge_proposal(demcz_handle* h, int64_t Np, int64_t wp, uint64_t seed, const double* mean, const double* L,
+                                         demcz_handle** logratio, demcz_handle** draws)
+{
+    if (logratio) *logratio = nullptr;
+    if (draws) *draws = nullptr;
+    NOT_DERIVED(h);
+    if (!h || !logratio || !mean || !L) return DEMCZ_ERR_INVALID_ARGUMENT;
+    DEADCHK(h);
+    BridgeTarget t;
+    int32_t rc = bridge_target_of(h, "demcz_bridge_proposal", t);
+    if (rc) return rc;
+    return bridge_proposal_from(h, h->cfg.d, t, Np, wp, seed, mean, L, logratio, draws);
+}
+
+extern "C" int32_t demcz_bridge_proposal_program(int32_t device_id, int32_t d, int64_t Np, int64_t wp, uint64_t seed, const double* mean,
+                                                 const double* L, const char* source, const char* options, const double* data,
+                                                 int64_t ndata, demcz_handle** logratio, demcz_handle** draws)
+{
+    if (logratio) *logratio = nullptr;
+    if (draws) *draws = nullptr;
+    if (!logratio || !mean || !L) return DEMCZ_ERR_INVALID_ARGUMENT;
+    int32_t rc = demcz_bridge_check(d, source, options);        // (compiled before a device is touched)
+    if (rc) return rc;
+    ScratchHandle s;
+    rc = s.open(device_id, 1, d, 1, nullptr, nullptr);
+    if (rc) return diag_fail(s, rc);
+    BridgeTarget t;
+    rc = bridge_target_program(&s.h, d, source, options, data, ndata, "demcz_bridge_proposal_program", t);
+    if (rc) return diag_fail(s, rc);
+    return diag_fail(s, bridge_proposal_from(&s.h, d, t, Np, wp, seed, mean, L, logratio, draws));
+}
+
+extern "C" int32_t demcz_bridge_iterate(demcz_handle* post, int64_t g_from, int64_t g_to, demcz_handle* prop, int64_t gp_from,
+                                        int64_t gp_to, double neff, double tol, int64_t max_iter, double* logml, int64_t* iterations,
+                                        int32_t* converged, double* moments, int64_t* n_nan, demcz_handle** f2)
+{
+    if (f2) *f2 = nullptr;
+    if (!post || !prop) return DEMCZ_ERR_INVALID_ARGUMENT;
+    DEADCHK(post);
+    DEADCHK(prop);
+    BridgeResult res;
+    int32_t rc = bridge_iterate_from(post, g_from, g_to, prop, gp_from, gp_to, neff, tol, max_iter, res, f2);
+    if (rc) return rc;
+    if (logml) *logml = res.logml;
+    if (iterations) *iterations = res.iterations;
+    if (converged) *converged = res.converged;
+    if (moments) std::copy(res.moments, res.moments + 4, moments);
+    if (n_nan) *n_nan = res.n_nan;
+    return DEMCZ_OK;
+}
+
+extern "C" int32_t demcz_bridge(demcz_handle* h, int64_t g_from, int64_t g_to, uint64_t seed, double neff, double tol, int64_t max_iter,
+                                double* logml, double* se_logml, int64_t* iterations, int32_t* converged, int64_t* n_post,
+                                int64_t* n_prop, double* neff_used, int64_t* n_nan, double* ess_f2, double* mean_out, double* L_out)
+{
+    NOT_DERIVED(h);
+    if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
+    DEADCHK(h);
+    int32_t rc = rank_refuse_sharded(h, "demcz_bridge");
+    if (rc) return rc;
+    BridgeTarget t;
+    rc = bridge_target_of(h, "demcz_bridge", t);
+    if (rc) return rc;
+    const BridgeOut o{logml, se_logml, iterations, converged, n_post, n_prop, neff_used, n_nan, ess_f2, mean_out, L_out};
+    return bridge_from(h, t, g_from, g_to, seed, neff, tol, max_iter, o);
+}
+
+extern "C" int32_t demcz_bridge_array(int32_t device_id, const double* chain, const double* log_obj, int64_t N, int32_t d, int64_t G,
+                                      const char* source, const char* options, const double* data, int64_t ndata, uint64_t seed,
+                                      double neff, double tol, int64_t max_iter, double* logml, double* se_logml, int64_t* iterations,
+                                      int32_t* converged, int64_t* n_post, int64_t* n_prop, double* neff_used, int64_t* n_nan,
+                                      double* ess_f2, double* mean_out, double* L_out)
+{
+    if (!chain || !log_obj) return DEMCZ_ERR_INVALID_ARGUMENT;
+    int32_t rc = demcz_bridge_check(d, source, options);        // (compiled before anything is uploaded)
+    if (rc) return rc;
+    ScratchHandle s;
+    rc = s.open(device_id, N, d, G, chain, log_obj);
+    if (rc) return diag_fail(s, rc);
+    BridgeTarget t;
+    rc = bridge_target_program(&s.h, d, source, options, data, ndata, "demcz_bridge_array", t);
+    if (rc) return diag_fail(s, rc);
+    const BridgeOut o{logml, se_logml, iterations, converged, n_post, n_prop, neff_used, n_nan, ess_f2, mean_out, L_out};
+    return diag_fail(s, bridge_from(&s.h, t, 1, G, seed, neff, tol, max_iter, o));
 }
 
 extern "C" int32_t demcz_get_info(const demcz_handle* h, int64_t* M, int64_t* launches_window, int32_t* lanes_per_chain)

@@ -21,7 +21,9 @@ constexpr int MAX_DERIVE_M = demcz::DERIVE_MAX_M;
 // A derive program (demcz_derive, include/demcz.h) has a unit of its own: the user's demcz_derive and derive_kernel of
 // demcz_kernels_derive.h, nothing else.
 // A pointwise program (demcz_pointwise) likewise: the user's demcz_loglik and pointwise_kernel of demcz_kernels_pointwise.h.
-enum { UNIT_ONE_LANE = 0, UNIT_WAVE = 1, UNIT_DERIVE = 2, UNIT_POINTWISE = 3 };
+// A program target's bridge unit (demcz_bridge_proposal): the user's demcz_logobj and bridge_proposal_program_kernel of
+// demcz_kernels_bridge.h.
+enum { UNIT_ONE_LANE = 0, UNIT_WAVE = 1, UNIT_DERIVE = 2, UNIT_POINTWISE = 3, UNIT_BRIDGE = 4 };
 constexpr int WAVE_MIN_D = 2;
 
 // One compiled program: the gfx950 code object and the mangled names of its kernels.
@@ -33,7 +35,8 @@ struct Code {
     std::string logp;             // logp_kernel<TARGET_PROGRAM>: the initial log_objcurrent (both units)
     std::string wave[2][2];       // UNIT_WAVE: window_kernel_ps / _pw<TARGET_PROGRAM, d, LIVE, TEMPER>, [LIVE][TEMPER] (the one-lane
                                   // kernels are not in that unit, and these not in the one-lane unit)
-    std::string derive;           // UNIT_DERIVE: derive_kernel, the only kernel of that unit; UNIT_POINTWISE: pointwise_kernel
+    std::string derive;           // UNIT_DERIVE: derive_kernel, the only kernel of that unit; UNIT_POINTWISE: pointwise_kernel;
+                                  // UNIT_BRIDGE: bridge_proposal_program_kernel
     int d = 0;
     int m = 0;                    // UNIT_DERIVE: derived quantities per draw (DEMCZ_M)
     int unit = UNIT_ONE_LANE;
@@ -44,7 +47,7 @@ struct Module {
     hipModule_t module = nullptr;
     hipFunction_t window_full = nullptr, window_blocks = nullptr, snooker = nullptr, logp = nullptr;
     hipFunction_t wave[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    hipFunction_t derive = nullptr;   // (UNIT_POINTWISE: pointwise_kernel)
+    hipFunction_t derive = nullptr;   // (UNIT_POINTWISE: pointwise_kernel; UNIT_BRIDGE: bridge_proposal_program_kernel)
     std::shared_ptr<const Code> code;
 };
 

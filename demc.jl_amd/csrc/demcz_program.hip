@@ -24,6 +24,9 @@
 // The pointwise unit (UNIT_POINTWISE, demcz_pointwise) is the derive unit with DEMCZ_POINTWISE_UNIT in place of DEMCZ_DERIVE_UNIT
 // and DEMCZ_M, the user's demcz_loglik, and demcz_kernels_pointwise.h (which includes demcz_kernels_derive.h for the launch
 // constants): pointwise_kernel is its only kernel.  Same options, same caches.
+// The bridge unit (UNIT_BRIDGE, demcz_bridge_proposal): DEMCZ_D, DEMCZ_BRIDGE_UNIT, the user's demcz_logobj exactly as a program
+// target defines it, then demcz_device.h (Philox, dm_log, the Box-Muller pair) and demcz_kernels_bridge.h, whose
+// bridge_proposal_program_kernel is its only kernel.  No struct of the library's is in it.  A key of its own in the same caches.
 // Compile options: --offload-arch=gfx950 -O3 -ffp-contract=off -I<rocm>/include, the library's own layout switches (not for
 // the derive unit, which sees no struct of the library's), then the user's.  Code objects are cached per (composed text,
 // options), loaded modules per (code object, device); both for the life of the process.
@@ -87,6 +90,10 @@ const char k_derive_h[] = {
 const char k_pointwise_h[] = {
 #embed "demcz_kernels_pointwise.h"
     , 0};
+// the bridge unit's header (on top of demcz_device.h and the derive unit's launch constants)
+const char k_bridge_h[] = {
+#embed "demcz_kernels_bridge.h"
+    , 0};
 #pragma clang diagnostic pop
 
 // -D switches of the library build that change the layout of WindowParams: the program's kernels must see the same struct
@@ -120,6 +127,13 @@ std::string compose(int d, int m, const std::string& source, int unit)
           << "#include <hip/hip_runtime.h>\n#include <stdint.h>\n" << k_math_macros
           << "#line 1 \"program\"\n" << source << "\n"
           << "#line 1 \"demcz_unit_pointwise\"\n#include \"demcz_kernels_pointwise.h\"\n";
+        return s.str();
+    }
+    if (unit == demcz_prog::UNIT_BRIDGE) {
+        s << "#define DEMCZ_D " << d << "\n#define DEMCZ_BRIDGE_UNIT\n"
+          << "#include <hip/hip_runtime.h>\n#include <stdint.h>\n" << k_math_macros
+          << "#line 1 \"program\"\n" << source << "\n"
+          << "#line 1 \"demcz_unit_bridge\"\n#include \"demcz_kernels_bridge.h\"\n";
         return s.str();
     }
     if (unit == demcz_prog::UNIT_WAVE) {
@@ -215,15 +229,18 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
     const char* headers[] = {k_device_h, k_kernels_h, k_rec_h, k_ml_h, k_mlb_inc, k_pc_h, k_ps_h, k_pw_h};
     const char* names[] = {"demcz_device.h", "demcz_kernels.h", "demcz_kernels_rec.h", "demcz_kernels_ml.h", "demcz_mlb_dpp_20_5.inc",
                            "demcz_kernels_pc.h", "demcz_kernels_ps.h", "demcz_kernels_pw.h"};
-    const bool pointwise = unit == demcz_prog::UNIT_POINTWISE;
-    const bool wave = unit == demcz_prog::UNIT_WAVE, derive = unit == demcz_prog::UNIT_DERIVE || pointwise;   // (derive: a streaming unit)
+    const bool pointwise = unit == demcz_prog::UNIT_POINTWISE, bridge = unit == demcz_prog::UNIT_BRIDGE;
+    const bool wave = unit == demcz_prog::UNIT_WAVE, derive = unit == demcz_prog::UNIT_DERIVE || pointwise || bridge;   // (derive: a streaming unit)
     const char* lane_headers[] = {k_device_h, k_kernels_h, k_snooker_h};
     const char* lane_names[] = {"demcz_device.h", "demcz_kernels.h", "demcz_kernels_snooker.h"};
     const char* derive_headers[] = {k_derive_h};
     const char* derive_names[] = {"demcz_kernels_derive.h"};
     const char* pointwise_headers[] = {k_derive_h, k_pointwise_h};
     const char* pointwise_names[] = {"demcz_kernels_derive.h", "demcz_kernels_pointwise.h"};
-    if (pointwise) RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_unit_pointwise.hip", 2, pointwise_headers, pointwise_names));
+    const char* bridge_headers[] = {k_device_h, k_derive_h, k_bridge_h};
+    const char* bridge_names[] = {"demcz_device.h", "demcz_kernels_derive.h", "demcz_kernels_bridge.h"};
+    if (bridge) RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_unit_bridge.hip", 3, bridge_headers, bridge_names));
+    else if (pointwise) RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_unit_pointwise.hip", 2, pointwise_headers, pointwise_names));
     else if (derive) RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_unit_derive.hip", 1, derive_headers, derive_names));
     else if (wave) RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_program_wave_unit.hip", 8, headers, names));
     else RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_program_unit.hip", 3, lane_headers, lane_names));
@@ -231,7 +248,7 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
     const std::string ds = std::to_string(d);
     std::vector<std::string> exprs;
     if (derive) {
-        exprs = {pointwise ? "&demcz::pointwise_kernel" : "&demcz::derive_kernel"};
+        exprs = {bridge ? "&demcz::bridge_proposal_program_kernel" : pointwise ? "&demcz::pointwise_kernel" : "&demcz::derive_kernel"};
     } else if (wave) {
         const std::string kn = (d <= 5) ? "&demcz::window_kernel_ps<4, " : "&demcz::window_kernel_pw<4, ";
         for (int live = 0; live < 2; ++live)
@@ -254,13 +271,13 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
             while (!log.empty() && log.back() == '\0') log.pop_back();
         }
         err = who + "compilation failed (" + std::string(hiprtcGetErrorString(rc)) + ")";
-        if (!derive && text.find("demcz_logobj") == std::string::npos)   // (the library's own call is in demcz_kernels.h, not in `text`)
+        if ((!derive || bridge) && text.find("demcz_logobj") == std::string::npos)   // (the library's own call is in demcz_kernels.h, not in `text`)
             err += "; the program does not define demcz_logobj -- it must define "
                    "__device__ double demcz_logobj(const double* x, const double* data, int64_t ndata)";
         if (pointwise && text.find("demcz_loglik") == std::string::npos)
             err += "; the program does not define demcz_loglik -- it must define "
                    "__device__ double demcz_loglik(const double* x, const double* data, int64_t ndata, int64_t i)";
-        if (derive && !pointwise && text.find("demcz_derive") == std::string::npos)    // (... and derive_kernel's in demcz_kernels_derive.h)
+        if (derive && !pointwise && !bridge && text.find("demcz_derive") == std::string::npos)    // (... and derive_kernel's in demcz_kernels_derive.h)
             err += "; the program does not define demcz_derive -- it must define "
                    "__device__ void demcz_derive(const double* x, double logp, const double* data, int64_t ndata, double* out)";
         err += ":\n" + trim_log(log);
@@ -272,7 +289,7 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
     RTCCHK(hiprtcGetCode(prog, code.object.data()));
     if (const char* dump = getenv("DEMCZ_PROGRAM_DUMP"); dump && *dump) {
         // diagnosis (scripts/kernel_regs.py, llvm-objdump): the code object as a file in that directory
-        const std::string path = std::string(dump) + "/demcz_program_" + (pointwise ? "pointwise" : derive ? "derive" : wave ? "wave" : "lane") + "_d" + ds + "_" +
+        const std::string path = std::string(dump) + "/demcz_program_" + (bridge ? "bridge" : pointwise ? "pointwise" : derive ? "derive" : wave ? "wave" : "lane") + "_d" + ds + "_" +
                                  std::to_string(std::hash<std::string>{}(text) % 1000000007ull) + ".co";
         if (FILE* f = fopen(path.c_str(), "wb")) { (void)fwrite(code.object.data(), 1, code.object.size(), f); fclose(f); }
     }
@@ -298,7 +315,7 @@ namespace demcz_prog {
 
 int32_t get_code(int d, const char* source, const char* options, int unit, std::shared_ptr<const Code>& out, std::string& err, int m)
 {
-    if (unit != UNIT_ONE_LANE && unit != UNIT_WAVE && unit != UNIT_DERIVE && unit != UNIT_POINTWISE) {
+    if (unit != UNIT_ONE_LANE && unit != UNIT_WAVE && unit != UNIT_DERIVE && unit != UNIT_POINTWISE && unit != UNIT_BRIDGE) {
         err = "program target: lanes_per_chain must be 0, 1 or DEMCZ_LAYOUT_PROGRAM_WAVE";
         return 1;
     }
@@ -323,7 +340,7 @@ int32_t get_code(int d, const char* source, const char* options, int unit, std::
     std::string inc;
     if (!rocm_include(inc, err)) return 1;
     std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-I" + inc};
-    if (unit != UNIT_DERIVE && unit != UNIT_POINTWISE)
+    if (unit != UNIT_DERIVE && unit != UNIT_POINTWISE && unit != UNIT_BRIDGE)
         for (const char* const* s = k_layout_switches; *s; ++s) opts.push_back(*s);
     for (auto& o : split_options(options)) opts.push_back(o);
     // (the text is the key: it names the unit's kernel header and, for a derive unit, DEMCZ_M)
@@ -352,7 +369,7 @@ int32_t get_module(const std::shared_ptr<const Code>& code, int device, Module& 
     Module m;
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipModuleLoadData(&m.module, code->object.data());
-    const bool streaming = code->unit == UNIT_DERIVE || code->unit == UNIT_POINTWISE;
+    const bool streaming = code->unit == UNIT_DERIVE || code->unit == UNIT_POINTWISE || code->unit == UNIT_BRIDGE;
     if (streaming) {
         if (e == hipSuccess) e = hipModuleGetFunction(&m.derive, m.module, code->derive.c_str());
     } else if (code->unit == UNIT_WAVE) {

@@ -112,6 +112,95 @@ def _r_eff_arg(r_eff, n):
     return r
 
 
+# The marginal likelihood by bridge sampling (demcz_bridge).  logml and its standard error se_logml; iterations and converged of the
+# fixed-point iteration; n_post and n_prop, the draws on either side; neff as used; n_nan, the proposal draws whose log-density was
+# NaN (taken as -inf); ess_f2; mean and L of the proposal N(mean, L L^T)
+Bridge = namedtuple("Bridge", "logml se_logml iterations converged n_post n_prop neff n_nan ess_f2 mean L")
+# demcz_bridge_iterate: moments = (mean f1, var f1, mean f2, var f2) at the final rho; f2: a DerivedHistory, or None
+BridgeIteration = namedtuple("BridgeIteration", "logml iterations converged moments n_nan f2")
+
+BRIDGE_SEED_XOR = 0x9E3779B97F4A7C15     # the default seed of the proposal's streams is the run's seed XOR this constant
+
+
+def bridge_seed(run_seed):
+    """The documented default seed of ``HipEngine.bridge``: the run's seed XOR ``BRIDGE_SEED_XOR`` (the 64-bit golden ratio), so
+    that the proposal does not replay the sampler's Philox streams."""
+    return (int(run_seed) ^ BRIDGE_SEED_XOR) & (2**64 - 1)
+
+
+def bridge_se(moments, n_prop, ess_f2):
+    """se_logml = sqrt(var f1 / (N2 mean f1^2) + var f2 / (ESS(f2) mean f2^2)) as demcz_bridge forms it (host code)."""
+    m1, v1, m2, v2 = (float(v) for v in moments)
+    with np.errstate(all="ignore"):
+        return float(np.sqrt(np.float64(v1) / (np.float64(n_prop) * (np.float64(m1) * m1))
+                             + np.float64(v2) / (np.float64(ess_f2) * (np.float64(m2) * m2))))
+
+
+def _bridge_outputs(d):
+    return dict(logml=C.c_double(), se=C.c_double(), it=C.c_int64(), conv=C.c_int32(), n1=C.c_int64(), n2=C.c_int64(),
+                neff=C.c_double(), nnan=C.c_int64(), ess=C.c_double(), mean=np.empty(d), L=np.empty((d, d), order="F"))
+
+
+def _bridge_out_args(o):
+    return [C.byref(o["logml"]), C.byref(o["se"]), C.byref(o["it"]), C.byref(o["conv"]), C.byref(o["n1"]), C.byref(o["n2"]),
+            C.byref(o["neff"]), C.byref(o["nnan"]), C.byref(o["ess"]), _lib.ptr(o["mean"]), _lib.ptr(o["L"])]
+
+
+def _bridge_record(o):
+    return Bridge(o["logml"].value, o["se"].value, o["it"].value, bool(o["conv"].value), o["n1"].value, o["n2"].value,
+                  o["neff"].value, o["nnan"].value, o["ess"].value, o["mean"], o["L"])
+
+
+def _bridge_ml(mean, L, d):
+    mean = _lib.f64(mean)
+    L = _lib.f64(L, "F")
+    if mean.shape != (d,) or L.shape != (d, d):
+        raise ValueError("mean must have d entries and L must be d x d")
+    return mean, L
+
+
+def bridge_iterate(post, prop, g_from=None, g_to=None, gp_from=None, gp_to=None, neff=None, tol=1e-10, max_iter=1000, want_f2=False):
+    """The fixed-point iteration of bridge sampling on two one-column ``DerivedHistory`` objects on one device
+    (demcz_bridge_iterate): ``post`` holds a1 = log_obj - log g at the posterior draws, ``prop`` a2 = logobj - log g at the
+    proposal's; the windows default to all of either.  ``neff``: the effective number of posterior draws (None: all of them).
+    Returns a ``BridgeIteration``; with ``want_f2`` its ``f2`` is a ``DerivedHistory`` (a context manager) whose ``ess`` gives
+    the error estimate's ESS(f2), see ``bridge_se``."""
+    g_from = post.g_from if g_from is None else int(g_from)
+    g_to = post.g_to if g_to is None else int(g_to)
+    gp_from = prop.g_from if gp_from is None else int(gp_from)
+    gp_to = prop.g_to if gp_to is None else int(gp_to)
+    logml, it, conv, nnan = C.c_double(), C.c_int64(), C.c_int32(), C.c_int64()
+    mom = np.empty(4)
+    f2 = C.c_void_p()
+    post._chk(post._L.demcz_bridge_iterate(post._h, g_from, g_to, prop._h, gp_from, gp_to, 0.0 if neff is None else float(neff),
+                                           float(tol), int(max_iter), C.byref(logml), C.byref(it), C.byref(conv), _lib.ptr(mom),
+                                           C.byref(nnan), C.byref(f2) if want_f2 else None))
+    hist = DerivedHistory(post._L, f2, post.N, 1, g_from, g_to, ["f2"]) if want_f2 else None
+    return BridgeIteration(logml.value, it.value, bool(conv.value), mom, nnan.value, hist)
+
+
+def bayes_factor(a, b):
+    """(log_bf, se) of two ``Bridge`` records, a over b: logml_a - logml_b and sqrt(se_a^2 + se_b^2).  Host code."""
+    with np.errstate(all="ignore"):
+        return float(a.logml - b.logml), float(np.sqrt(np.float64(a.se_logml) ** 2 + np.float64(b.se_logml) ** 2))
+
+
+def post_prob(*bridges, prior=None):
+    """Posterior model probabilities of ``Bridge`` records (or plain logml values): the softmax of logml + log prior on the host.
+    ``prior``: one positive weight per model (default: equal); it need not sum to one."""
+    lm = np.array([getattr(b, "logml", b) for b in bridges], dtype=np.float64)
+    if lm.size == 0:
+        raise ValueError("at least one model")
+    pr = np.ones(lm.size) if prior is None else np.asarray(prior, dtype=np.float64)
+    if pr.shape != lm.shape or not np.all(pr > 0):
+        raise ValueError("prior must hold one positive weight per model")
+    v = lm + np.log(pr)
+    if np.any(np.isnan(v)):
+        return np.full(lm.size, np.nan)
+    e = np.exp(v - v.max())
+    return e / e.sum()
+
+
 def rank_to_z(r, S):
     """demcz_rank_to_z (host code, no device): the normal scores of average ranks r (1 <= r <= S) among S draws, by the operation
     sequence the device runs (Blom's offsets, Wichura's AS 241)."""
@@ -426,6 +515,7 @@ class HipEngine(_HistoryStatistics):
         self._L = _lib.load()
         self.N, self.d, self.K, self.Mcap, self.Gcap = int(N), int(d), int(K), int(Mcap), int(Gcap)
         self.chain_id0 = int(chain_id0)
+        self.seed = int(seed) & (2**64 - 1)
         self._keep = []
         offs, idx = blocks_to_csr(blockindex, d)
         eps = _lib.f64(eps_scale)
@@ -475,6 +565,49 @@ class HipEngine(_HistoryStatistics):
             self.close()
         except Exception:
             pass
+
+    # -- the marginal likelihood (demcz_bridge) ------------------------------------------------
+    def bridge_posterior(self, g_from, g_to, mean, L):
+        """a1 = log_obj - log g(x) of every draw of generations g_from..g_to, g = N(mean, L L^T) (demcz_bridge_posterior): a
+        one-column ``DerivedHistory`` (a context manager) whose generations keep their numbers."""
+        mean, L = _bridge_ml(mean, L, self.d)
+        out = C.c_void_p()
+        self._chk(self._L.demcz_bridge_posterior(self._h, int(g_from), int(g_to), _lib.ptr(mean), _lib.ptr(L), C.byref(out)))
+        return DerivedHistory(self._L, out, self.N, 1, int(g_from), int(g_to), ["a1"], self.chain_id0)
+
+    def bridge_proposal(self, Np, wp, mean, L, seed=None, want_draws=False):
+        """Np x wp fresh draws of g = N(mean, L L^T) and a2 = logobj(x) - log g(x) with this engine's own target
+        (demcz_bridge_proposal): a one-column ``DerivedHistory`` of generations 1..wp, or with ``want_draws`` the pair (a2, draws),
+        draws an Np x d x wp ``DerivedHistory``.  ``seed``: default ``bridge_seed(self.seed)``."""
+        mean, L = _bridge_ml(mean, L, self.d)
+        seed = bridge_seed(self.seed) if seed is None else int(seed) & (2**64 - 1)
+        a2, xs = C.c_void_p(), C.c_void_p()
+        self._chk(self._L.demcz_bridge_proposal(self._h, int(Np), int(wp), seed, _lib.ptr(mean), _lib.ptr(L), C.byref(a2),
+                                                C.byref(xs) if want_draws else None))
+        ha = DerivedHistory(self._L, a2, int(Np), 1, 1, int(wp), ["a2"])
+        return (ha, DerivedHistory(self._L, xs, int(Np), self.d, 1, int(wp), getattr(self, "names", None))) if want_draws else ha
+
+    def bridge(self, g_from, g_to, seed=None, neff="auto", tol=1e-10, max_iter=1000):
+        """The marginal likelihood log Z = log integral exp(logobj) by bridge sampling over generations g_from..g_to (demcz_bridge):
+        a ``Bridge`` record.  The first half of the window fits a normal proposal, the second half is iterated against as many
+        fresh draws of it.  ``neff``: the effective number of posterior draws; "auto" is the median over the parameters of
+        ``ess`` of the iteration window, None all N1 of them.  ``seed``: the proposal's streams; the default is
+        ``bridge_seed(self.seed)``, the run's seed XOR ``BRIDGE_SEED_XOR`` -- with the run's own seed the proposal would replay
+        the sampler's streams.  Assumes that log_obj is the untempered log-posterior and that the window is converged; a
+        posterior far from normal shows as a large ``se_logml`` and a slow iteration."""
+        g_from, g_to = int(g_from), int(g_to)
+        if isinstance(neff, str):
+            if neff != "auto":
+                raise ValueError('neff must be a number, None or "auto"')
+            w = g_to - g_from + 1
+            ne = float(np.median(self.ess(g_from + w // 2, g_to).ess)) if w >= 8 else 0.0
+            ne = ne if np.isfinite(ne) and ne > 0 else 0.0
+        else:
+            ne = 0.0 if neff is None else float(neff)
+        seed = bridge_seed(self.seed) if seed is None else int(seed) & (2**64 - 1)
+        o = _bridge_outputs(self.d)
+        self._chk(self._L.demcz_bridge(self._h, g_from, g_to, seed, ne, float(tol), int(max_iter), *_bridge_out_args(o)))
+        return _bridge_record(o)
 
     # -- state --------------------------------------------------------------------------------
     def set_state(self, X, logp, Z):

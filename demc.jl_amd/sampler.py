@@ -329,6 +329,14 @@ class _Runner:
             raise
         return _DerivedRunner(self, hists, program, g_from, g_to)
 
+    def bridge(self, g_from, g_to, **kw):
+        """The marginal likelihood by bridge sampling over generations g_from..g_to (``HipEngine.bridge``; a ``Bridge`` record).
+        One engine only: the proposal is fitted to, and the iteration runs over, the draws of every chain."""
+        if self.lib_exchange or self.host_exchange or len(self.engines) != 1:
+            raise NotImplementedError("bridge over several shards: gather the window's chain and log_obj (history()) and use "
+                                      "demc.bridge_chain on the whole")
+        return self.engines[0].bridge(g_from, g_to, **kw)
+
     def changed(self, g_from, g_to):
         c = sum(e.get_changed(g_from, g_to) for e in self.engines)
         if self.sh is not None and self.sh.world_size > 1:

@@ -132,6 +132,15 @@ class ProgramTarget:
         if rc != 0:
             raise _lib.DemczError(rc, (L.demcz_last_error(None) or b"").decode())
 
+    def check_bridge(self):
+        """Compile the program's bridge-sampling unit (``demcz_bridge_check``; no device needed): what ``HipEngine.bridge`` and
+        ``demc.bridge_chain`` compile on first use.  Raises ``DemczError`` with the compiler log if it does not compile."""
+        L = _lib.load()
+        src, opts = self._args()
+        rc = L.demcz_bridge_check(self.d, src, opts)
+        if rc != 0:
+            raise _lib.DemczError(rc, (L.demcz_last_error(None) or b"").decode())
+
     def fill(self, cfg, keep):
         pass                # (the program and its data go to the handle after demcz_create: attach)
 

@@ -248,6 +248,63 @@ def loo_chain(chain, program, r_eff=None, device_id=0):
     return loo_record(e, k, n, l, w, N * G, program.names)
 
 
+def _program_args(program):
+    src, opts = program._args()
+    n = 0 if program.data is None else program.data.size
+    return src, opts, (_lib.ptr(program.data) if n else None), n
+
+
+def bridge_chain(chain, log_obj, program, seed=0x9E3779B97F4A7C15, neff=None, tol=1e-10, max_iter=1000, device_id=0):
+    """The marginal likelihood by bridge sampling of an Npop x Npar x Ngeneration history and its Npop x Ngeneration log_obj, the
+    target given as a ``ProgramTarget`` (demcz_bridge_array): a ``Bridge`` record.  The whole history is the window: its first
+    half fits the proposal.  ``neff``: the effective number of posterior draws of the second half (None: all of them);
+    ``seed``: the proposal's streams, not the run's own seed.  Not in the reference."""
+    from .engine import _bridge_outputs, _bridge_out_args, _bridge_record
+    chain = _lib.f64(chain, "F")
+    log_obj = _lib.f64(log_obj, "F")
+    N, d, G = chain.shape
+    if log_obj.shape != (N, G):
+        raise ValueError("log_obj must be Npop x Ngeneration")
+    if program.d != d:
+        raise ValueError("the program's d is not the chain's Npar")
+    src, opts, data, ndata = _program_args(program)
+    o = _bridge_outputs(d)
+    _chk(_lib.load().demcz_bridge_array(device_id, _lib.ptr(chain), _lib.ptr(log_obj), N, d, G, src, opts, data, ndata,
+                                        int(seed) & (2**64 - 1), 0.0 if neff is None else float(neff), float(tol), int(max_iter),
+                                        *_bridge_out_args(o)))
+    return _bridge_record(o)
+
+
+def bridge_posterior_chain(chain, log_obj, mean, L, device_id=0):
+    """a1 = log_obj - log g(x), g = N(mean, L L^T), of every draw of an Npop x Npar x Ngeneration history
+    (demcz_bridge_posterior_array): a one-column ``DerivedHistory`` on the device, generations 1..Ngeneration."""
+    from .engine import DerivedHistory, _bridge_ml
+    chain = _lib.f64(chain, "F")
+    log_obj = _lib.f64(log_obj, "F")
+    N, d, G = chain.shape
+    if log_obj.shape != (N, G):
+        raise ValueError("log_obj must be Npop x Ngeneration")
+    mean, L = _bridge_ml(mean, L, d)
+    lib = _lib.load()
+    out = C.c_void_p()
+    _chk(lib.demcz_bridge_posterior_array(device_id, _lib.ptr(chain), _lib.ptr(log_obj), N, d, G, _lib.ptr(mean), _lib.ptr(L), C.byref(out)))
+    return DerivedHistory(lib, out, N, 1, 1, G, ["a1"])
+
+
+def bridge_proposal_program(program, Np, wp, mean, L, seed, want_draws=False, device_id=0):
+    """Np x wp fresh draws of g = N(mean, L L^T) and a2 = logobj(x) - log g(x) of a ``ProgramTarget`` without an engine
+    (demcz_bridge_proposal_program): a one-column ``DerivedHistory``, or with ``want_draws`` the pair (a2, draws)."""
+    from .engine import DerivedHistory, _bridge_ml
+    mean, L = _bridge_ml(mean, L, program.d)
+    src, opts, data, ndata = _program_args(program)
+    lib = _lib.load()
+    a2, xs = C.c_void_p(), C.c_void_p()
+    _chk(lib.demcz_bridge_proposal_program(device_id, program.d, int(Np), int(wp), int(seed) & (2**64 - 1), _lib.ptr(mean), _lib.ptr(L),
+                                           src, opts, data, ndata, C.byref(a2), C.byref(xs) if want_draws else None))
+    ha = DerivedHistory(lib, a2, int(Np), 1, 1, int(wp), ["a2"])
+    return (ha, DerivedHistory(lib, xs, int(Np), program.d, 1, int(wp))) if want_draws else ha
+
+
 def convergence_check(chain, log_obj, figure_path=None, verbose=True, parnames=None, device_id=0):
     """(accept_ratio, Rhat) as src/utils.jl:34-94 returns them (the plotting part is commented out
     in the reference and is not reproduced)."""

@@ -493,7 +493,8 @@ int32_t demcz_best_array(int32_t device_id, const double* log_obj, int64_t N, in
  * freed by demcz_destroy.  It takes demcz_rhat, demcz_rhat_partial, demcz_autocov_sums, demcz_ess, demcz_select_counts,
  * demcz_quantiles, demcz_mean_cov, demcz_get_history with log_obj = NULL, demcz_synchronize, demcz_last_error, demcz_destroy,
  * demcz_derive (a derived history of a derived history; its logp is NaN) and demcz_rank_normalize, demcz_indicator_le,
- * demcz_rank_diagnostics, demcz_pointwise, demcz_loo_columns and demcz_loo (below).  Every other call that takes a handle returns
+ * demcz_rank_diagnostics, demcz_pointwise, demcz_loo_columns, demcz_loo and (a one-column one, as either argument)
+ * demcz_bridge_iterate (below).  Every other call that takes a handle returns
  * DEMCZ_ERR_STATE on it, with a message that says so. */
 int32_t demcz_derive_check(int32_t d, int32_t m, const char* source, const char* options);
 int32_t demcz_derive(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t m, const char* source, const char* options,
@@ -598,6 +599,71 @@ int32_t demcz_loo(demcz_handle* h, int64_t g_from, int64_t g_to, int64_t nobs, c
 int32_t demcz_loo_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, int64_t nobs,
                         const char* source, const char* options, const double* data, int64_t ndata, const double* r_eff,
                         double* elpd_loo, double* pareto_k, int64_t* n_tail, double* lppd, double* p_waic);
+
+/* The marginal likelihood log Z = log integral exp(logobj(x)) dx by bridge sampling (the optimal bridge of Meng & Wong 1996; the
+ * iterative scheme of Gronau et al. 2017; the error estimate of Fruehwirth-Schnatter 2004; not in the reference), from the history
+ * on the device (DESIGN.md sections 3 and 4.17).  It gives Bayes factors and posterior model probabilities.  It assumes that
+ * log_obj is the untempered log-posterior of the draws (not an annealing run) and that the window is converged; a posterior far
+ * from normal shows as a large se_logml and a slow iteration.  Four layers, each with an entry point of its own; 1 <= d <= 32.
+ *
+ * The window g_from..g_to of w >= 4 generations is cut at h = floor(w / 2): generations g_from .. g_from + h - 1 fit the proposal
+ * g = N(m, L L^T) -- (m, V) is demcz_mean_cov of them, L the lower Cholesky factor of V computed on the host; a pivot that is not
+ * positive and finite is DEMCZ_ERR_INVALID_ARGUMENT with the parameter's index in the message -- and generations g_from + h .. g_to
+ * are the N1 = N (w - h) posterior draws of the iteration.  mean: d values; L: d x d column-major, its lower triangle is read.
+ *
+ * 1. demcz_bridge_posterior: a1 = log_obj - log g(x) of every draw of generations g_from..g_to of h, by the solve L z = x - m: a
+ * one-column DERIVED HISTORY (see demcz_derive) whose generations keep their numbers.  A derived history as h has no log_obj:
+ * DEMCZ_ERR_STATE.  demcz_bridge_posterior_array: the same from host arrays N x d x G and N x G; generations 1..G.
+ *
+ * 2. demcz_bridge_proposal: Np x wp fresh draws of g -- draw j = c + Np t takes its normals from Philox blocks t B .. t B + B - 1,
+ * B = ceil(d / 2), of stream (seed, chain c), the pairs demcz_selftest_draws returns -- and a2 = logobj(x) - log g(x) with the
+ * handle's own target, built-in or program (a program's bridge unit is compiled on first use): *logratio is a one-column derived
+ * history of generations 1..wp; with draws != NULL, *draws is the Np x d x wp derived history of the draws themselves.  A NaN from
+ * the target stays NaN.  A host-closure handle has no target on the device and is refused (DEMCZ_ERR_STATE).
+ * demcz_bridge_proposal_program: the same for a program (demcz_set_program's source, options and data) without a handle.
+ * demcz_bridge_check compiles a program's bridge unit and needs no device; errors as demcz_program_check's.
+ *
+ * 3. demcz_bridge_iterate works on any two one-column histories on one device: a1 over generations g_from..g_to of post (N1
+ * values), a2 over gp_from..gp_to of prop (N2 values).  With s1 = neff / (neff + N2), s2 = 1 - s1 (neff <= 0 means N1),
+ *     f1_j = 1 / (s1 + s2 exp(rho - a2_j))   f2_i = 1 / (s1 exp(a1_i - rho) + s2)   rho' = rho + log mean f1 - log mean f2
+ * from rho_0 = max a1, until |rho' - rho| <= tol (*converged = 1) or max_iter updates (>= 1) have been made.  *logml is the last
+ * rho', *iterations the number of updates.  A NaN in a2 counts as -inf and is counted in *n_nan.  A non-finite a1, a +inf in a2
+ * or a mean that is 0 gives *logml = NaN with *converged = 0 (and NaN moments).  moments[4] = mean f1, var f1, mean f2, var f2 at
+ * the final rho, variances with divisor n.  With f2 != NULL, *f2 is f2 at the final rho as a derived history numbered as post's
+ * window.  Sums are made in tiles of 1024 added in index order, without floating-point atomics: the same call gives the same
+ * bits, and neither they nor *iterations depend on how many updates are queued between two synchronisations (4; the environment
+ * variable DEMCZ_BRIDGE_BATCH, 1..64, sets another number).
+ *
+ * 4. demcz_bridge: the whole pipeline on h's history with Np = N, wp = w - h.  Outputs, any may be NULL: logml; se_logml =
+ * sqrt(var f1 / (N2 mean f1^2) + var f2 / (ess_f2 mean f2^2)); iterations; converged; n_post = N1; n_prop = N2; neff_used; n_nan;
+ * ess_f2 = demcz_ess of f2 over the iteration window (NaN, and se_logml with it, where that window has fewer than 4 generations);
+ * mean_out (d) and L_out (d x d column-major) of the proposal.  Use a seed
+ * other than the run's: with the run's own the proposal would replay the sampler's streams.  demcz_bridge_array: the same from
+ * host arrays and a program.  Range and state errors are demcz_rhat's; a handle whose communicator has more than one rank is
+ * refused as demcz_rank_normalize refuses it (gather the window and use demcz_bridge_array).  Every failure leaves the derived
+ * histories NULL. */
+int32_t demcz_bridge_check(int32_t d, const char* source, const char* options);
+int32_t demcz_bridge_posterior(demcz_handle* h, int64_t g_from, int64_t g_to, const double* mean, const double* L,
+                               demcz_handle** derived);
+int32_t demcz_bridge_posterior_array(int32_t device_id, const double* chain, const double* log_obj, int64_t N, int32_t d,
+                                     int64_t G, const double* mean, const double* L, demcz_handle** derived);
+int32_t demcz_bridge_proposal(demcz_handle* h, int64_t Np, int64_t wp, uint64_t seed, const double* mean, const double* L,
+                              demcz_handle** logratio, demcz_handle** draws /* may be NULL */);
+int32_t demcz_bridge_proposal_program(int32_t device_id, int32_t d, int64_t Np, int64_t wp, uint64_t seed, const double* mean,
+                                      const double* L, const char* source, const char* options, const double* data,
+                                      int64_t ndata, demcz_handle** logratio, demcz_handle** draws /* may be NULL */);
+int32_t demcz_bridge_iterate(demcz_handle* post, int64_t g_from, int64_t g_to, demcz_handle* prop, int64_t gp_from,
+                             int64_t gp_to, double neff, double tol, int64_t max_iter, double* logml, int64_t* iterations,
+                             int32_t* converged, double* moments /* 4 values */, int64_t* n_nan,
+                             demcz_handle** f2 /* may be NULL */);
+int32_t demcz_bridge(demcz_handle* h, int64_t g_from, int64_t g_to, uint64_t seed, double neff, double tol, int64_t max_iter,
+                     double* logml, double* se_logml, int64_t* iterations, int32_t* converged, int64_t* n_post,
+                     int64_t* n_prop, double* neff_used, int64_t* n_nan, double* ess_f2, double* mean_out, double* L_out);
+int32_t demcz_bridge_array(int32_t device_id, const double* chain, const double* log_obj, int64_t N, int32_t d, int64_t G,
+                           const char* source, const char* options, const double* data, int64_t ndata, uint64_t seed,
+                           double neff, double tol, int64_t max_iter, double* logml, double* se_logml, int64_t* iterations,
+                           int32_t* converged, int64_t* n_post, int64_t* n_prop, double* neff_used, int64_t* n_nan,
+                           double* ess_f2, double* mean_out, double* L_out);
 
 /* Introspection for benchmarks and tests. */
 int32_t demcz_get_info(const demcz_handle* h, int64_t* M, int64_t* launches_window, int32_t* lanes_per_chain);

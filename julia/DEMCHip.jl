@@ -501,6 +501,87 @@ function rank_diagnostics_chain(chain::Array{Float64,3}; device_id=0)
     (rhat_rank=r, ess_bulk=eb, ess_tail=et)
 end
 
+# ---- the marginal likelihood by bridge sampling (include/demcz.h: demcz_bridge; not in the reference) ------------------------
+# log Z = log ∫ exp(logobj(x)) dx from the history on the device: the first half of the window g_from:g_to fits a normal proposal,
+# the second half is iterated against as many fresh draws of it.  Assumes log_obj is the untempered log-posterior (not an
+# annealing run) and a converged window; a posterior far from normal shows as a large se_logml and a slow iteration.
+const BRIDGE_SEED_XOR = 0x9e3779b97f4a7c15
+bridge_seed(seed) = UInt64(seed) ⊻ BRIDGE_SEED_XOR     # not the run's own seed: the proposal would replay the sampler's streams
+bridge_check(t::ProgramTarget) =
+    chk(ccall((:demcz_bridge_check, libdemcz), Int32, (Int32, Cstring, Cstring), Int32(t.d), t.source, join(t.options, " ")))
+function bridge_result(d, call)
+    logml = Ref(0.0); se = Ref(0.0); it = Ref{Int64}(0); conv = Ref{Int32}(0); n1 = Ref{Int64}(0); n2 = Ref{Int64}(0)
+    ne = Ref(0.0); nnan = Ref{Int64}(0); ess = Ref(0.0); m = zeros(d); L = zeros(d, d)
+    call(logml, se, it, conv, n1, n2, ne, nnan, ess, m, L)
+    (logml=logml[], se_logml=se[], iterations=it[], converged=conv[] == 1, n_post=n1[], n_prop=n2[], neff=ne[], n_nan=nnan[],
+     ess_f2=ess[], mean=m, L=L)
+end
+# neff <= 0: every posterior draw counts (the usual choice is the median over the parameters of ess of g_from + w ÷ 2 : g_to)
+function bridge(h, g_from, g_to, d; seed, neff=0.0, tol=1e-10, max_iter=1000)
+    bridge_result(d, (logml, se, it, conv, n1, n2, ne, nnan, ess, m, L) ->
+        chk(ccall((:demcz_bridge, libdemcz), Int32,
+                  (Ptr{Cvoid}, Int64, Int64, UInt64, Float64, Float64, Int64, Ref{Float64}, Ref{Float64}, Ref{Int64}, Ref{Int32},
+                   Ref{Int64}, Ref{Int64}, Ref{Float64}, Ref{Int64}, Ref{Float64}, Ptr{Float64}, Ptr{Float64}),
+                  h, g_from, g_to, UInt64(seed), neff, tol, max_iter, logml, se, it, conv, n1, n2, ne, nnan, ess, m, L), h))
+end
+function bridge_chain(chain::Array{Float64,3}, log_obj::Matrix{Float64}, t::ProgramTarget; seed=BRIDGE_SEED_XOR, neff=0.0, tol=1e-10,
+                      max_iter=1000, device_id=0)
+    Npop, Npar, Ngeneration = size(chain)
+    bridge_result(Npar, (logml, se, it, conv, n1, n2, ne, nnan, ess, m, L) ->
+        chk(ccall((:demcz_bridge_array, libdemcz), Int32,
+                  (Int32, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Int64, Cstring, Cstring, Ptr{Float64}, Int64, UInt64, Float64,
+                   Float64, Int64, Ref{Float64}, Ref{Float64}, Ref{Int64}, Ref{Int32}, Ref{Int64}, Ref{Int64}, Ref{Float64},
+                   Ref{Int64}, Ref{Float64}, Ptr{Float64}, Ptr{Float64}),
+                  device_id, chain, log_obj, Npop, Npar, Ngeneration, t.source, join(t.options, " "), t.data, length(t.data),
+                  UInt64(seed), neff, tol, max_iter, logml, se, it, conv, n1, n2, ne, nnan, ess, m, L)))
+end
+# the layers: derived histories (destroy them when done).  a1 of the posterior draws; (a2, draws) of fresh proposal draws;
+# the iteration on any two one-column histories -> (logml, iterations, converged, moments, n_nan, f2)
+function bridge_posterior(h, g_from, g_to, m::Vector{Float64}, L::Matrix{Float64})
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    chk(ccall((:demcz_bridge_posterior, libdemcz), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+              h, g_from, g_to, m, L, out), h)
+    out[]
+end
+function bridge_posterior_chain(chain::Array{Float64,3}, log_obj::Matrix{Float64}, m::Vector{Float64}, L::Matrix{Float64}; device_id=0)
+    Npop, Npar, Ngeneration = size(chain)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    chk(ccall((:demcz_bridge_posterior_array, libdemcz), Int32,
+              (Int32, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+              device_id, chain, log_obj, Npop, Npar, Ngeneration, m, L, out))
+    out[]
+end
+function bridge_proposal(h, Np, wp, seed, m::Vector{Float64}, L::Matrix{Float64})
+    a2 = Ref{Ptr{Cvoid}}(C_NULL); xs = Ref{Ptr{Cvoid}}(C_NULL)
+    chk(ccall((:demcz_bridge_proposal, libdemcz), Int32,
+              (Ptr{Cvoid}, Int64, Int64, UInt64, Ptr{Float64}, Ptr{Float64}, Ref{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}),
+              h, Np, wp, UInt64(seed), m, L, a2, xs), h)
+    a2[], xs[]
+end
+function bridge_proposal(t::ProgramTarget, Np, wp, seed, m::Vector{Float64}, L::Matrix{Float64}; device_id=0)
+    a2 = Ref{Ptr{Cvoid}}(C_NULL); xs = Ref{Ptr{Cvoid}}(C_NULL)
+    chk(ccall((:demcz_bridge_proposal_program, libdemcz), Int32,
+              (Int32, Int32, Int64, Int64, UInt64, Ptr{Float64}, Ptr{Float64}, Cstring, Cstring, Ptr{Float64}, Int64, Ref{Ptr{Cvoid}},
+               Ref{Ptr{Cvoid}}),
+              device_id, Int32(t.d), Np, wp, UInt64(seed), m, L, t.source, join(t.options, " "), t.data, length(t.data), a2, xs))
+    a2[], xs[]
+end
+function bridge_iterate(post, g_from, g_to, prop, gp_from, gp_to; neff=0.0, tol=1e-10, max_iter=1000)
+    logml = Ref(0.0); it = Ref{Int64}(0); conv = Ref{Int32}(0); mom = zeros(4); nnan = Ref{Int64}(0); f2 = Ref{Ptr{Cvoid}}(C_NULL)
+    chk(ccall((:demcz_bridge_iterate, libdemcz), Int32,
+              (Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Int64, Int64, Float64, Float64, Int64, Ref{Float64}, Ref{Int64}, Ref{Int32},
+               Ptr{Float64}, Ref{Int64}, Ref{Ptr{Cvoid}}),
+              post, g_from, g_to, prop, gp_from, gp_to, neff, tol, max_iter, logml, it, conv, mom, nnan, f2), post)
+    (logml=logml[], iterations=it[], converged=conv[] == 1, moments=mom, n_nan=nnan[], f2=f2[])
+end
+# (log_bf, se) of two results, a over b; the posterior model probabilities of several (softmax of logml + log prior)
+bayes_factor(a, b) = (a.logml - b.logml, sqrt(a.se_logml^2 + b.se_logml^2))
+function post_prob(rs...; prior=ones(length(rs)))
+    v = [r.logml for r in rs] .+ log.(prior)
+    e = exp.(v .- maximum(v))
+    e ./ sum(e)
+end
+
 # ---- checkpoint: what a resumed run needs (the reference resumes in memory only, demcz.jl:18-22) ----------------------------
 struct Checkpoint
     prevrun::MC                 # last generation only: chain[:, :, end:end], log_obj[:, end:end], Xcurrent, log_objcurrent
