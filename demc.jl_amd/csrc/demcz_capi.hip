@@ -4468,6 +4468,10 @@ extern "C" int32_t demcz_get_snooker(const demcz_handle* h, int32_t* every, doub
 
 // ---- stateless diagnostics on caller arrays (src/utils.jl) ------------------------------------------
 namespace {
+// A demcz_handle that only holds a history: the caller's host arrays, uploaded for the length of one _array call into hipMalloc
+// blocks of their own, behind a stream created for the call.  derived_create (below) is the other builder of such a handle: a
+// history that outlives the call that made it, from the pools.  They stay two because merging them would move one's memory to
+// where the other's comes from.
 struct ScratchHandle {
     demcz_handle h;
     int32_t open(int32_t device_id, int64_t N, int d, int64_t G, const double* chain, const double* log_obj)
@@ -4502,76 +4506,68 @@ int32_t diag_fail(const ScratchHandle& s, int32_t rc)
     if (rc) g_create_error = s.h.err;
     return rc;
 }
+
+// The body of every _array entry point: the arrays go up into a ScratchHandle, fn works on it as on any handle holding generations
+// 1..G, the uploads are freed when the call returns, and a failure's message moves to where demcz_last_error(NULL) finds it.
+template <class F>
+int32_t with_arrays(int32_t device_id, int64_t N, int d, int64_t G, const double* chain, const double* log_obj, F fn)
+{
+    ScratchHandle s;
+    int32_t rc = s.open(device_id, N, d, G, chain, log_obj);
+    return diag_fail(s, rc ? rc : fn(&s.h));
+}
 }  // namespace
 
 extern "C" int32_t demcz_rhat_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, double* rhat)
 {
     if (!chain || !rhat) return DEMCZ_ERR_INVALID_ARGUMENT;
-    ScratchHandle s;
-    int32_t rc = s.open(device_id, N, d, G, chain, nullptr);
-    if (rc) return diag_fail(s, rc);
-    return diag_fail(s, demcz_rhat(&s.h, 1, G, rhat));
+    return with_arrays(device_id, N, d, G, chain, nullptr, [&](demcz_handle* h) { return demcz_rhat(h, 1, G, rhat); });
 }
 
 extern "C" int32_t demcz_autocov_sums_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G,
                                             int64_t lag_from, int64_t lag_to, double* sums)
 {
     if (!chain || !sums) return DEMCZ_ERR_INVALID_ARGUMENT;
-    ScratchHandle s;
-    int32_t rc = s.open(device_id, N, d, G, chain, nullptr);
-    if (rc) return diag_fail(s, rc);
-    return diag_fail(s, demcz_autocov_sums(&s.h, 1, G, lag_from, lag_to, sums));
+    return with_arrays(device_id, N, d, G, chain, nullptr, [&](demcz_handle* h) { return demcz_autocov_sums(h, 1, G, lag_from, lag_to, sums); });
 }
 
 extern "C" int32_t demcz_ess_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, int64_t max_lag,
                                    double* ess, double* tau, double* varplus, int64_t* pairs, int32_t* converged)
 {
     if (!chain || !ess) return DEMCZ_ERR_INVALID_ARGUMENT;
-    ScratchHandle s;
-    int32_t rc = s.open(device_id, N, d, G, chain, nullptr);
-    if (rc) return diag_fail(s, rc);
-    return diag_fail(s, demcz_ess(&s.h, 1, G, max_lag, ess, tau, varplus, pairs, converged));
+    return with_arrays(device_id, N, d, G, chain, nullptr,
+                       [&](demcz_handle* h) { return demcz_ess(h, 1, G, max_lag, ess, tau, varplus, pairs, converged); });
 }
 
 extern "C" int32_t demcz_quantiles_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, int32_t nq,
                                          const double* probs, double* q, double* lower, double* upper)
 {
     if (!chain || !probs || !q) return DEMCZ_ERR_INVALID_ARGUMENT;
-    ScratchHandle s;
-    int32_t rc = s.open(device_id, N, d, G, chain, nullptr);
-    if (rc) return diag_fail(s, rc);
-    return diag_fail(s, demcz_quantiles(&s.h, 1, G, nq, probs, q, lower, upper));
+    return with_arrays(device_id, N, d, G, chain, nullptr, [&](demcz_handle* h) { return demcz_quantiles(h, 1, G, nq, probs, q, lower, upper); });
 }
 
 extern "C" int32_t demcz_best_array(int32_t device_id, const double* log_obj, int64_t N, int64_t G, double* bestval, int64_t* chain,
                                     int64_t* column)
 {
     if (!log_obj || !bestval || !chain || !column) return DEMCZ_ERR_INVALID_ARGUMENT;
-    ScratchHandle s;
-    int32_t rc = s.open(device_id, N, 1, G, nullptr, log_obj);
-    if (rc) return diag_fail(s, rc);
-    int64_t g = -1;
-    rc = demcz_best(&s.h, 1, G, bestval, chain, &g, nullptr);
-    if (!rc) *column = (g < 0) ? -1 : g - 1;
-    return diag_fail(s, rc);
+    return with_arrays(device_id, N, 1, G, nullptr, log_obj, [&](demcz_handle* h) {
+        int64_t g = -1;
+        int32_t rc = demcz_best(h, 1, G, bestval, chain, &g, nullptr);
+        if (!rc) *column = (g < 0) ? -1 : g - 1;
+        return rc;
+    });
 }
 
 extern "C" int32_t demcz_accept_ratio_array(int32_t device_id, const double* log_obj, int64_t N, int64_t G, double* ratio)
 {
     if (!log_obj || !ratio) return DEMCZ_ERR_INVALID_ARGUMENT;
-    ScratchHandle s;
-    int32_t rc = s.open(device_id, N, 1, G, nullptr, log_obj);
-    if (rc) return diag_fail(s, rc);
-    return diag_fail(s, demcz_accept_ratio(&s.h, 1, G, ratio));
+    return with_arrays(device_id, N, 1, G, nullptr, log_obj, [&](demcz_handle* h) { return demcz_accept_ratio(h, 1, G, ratio); });
 }
 
 extern "C" int32_t demcz_mean_cov_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, double* mean, double* cov)
 {
     if (!chain || !mean || !cov) return DEMCZ_ERR_INVALID_ARGUMENT;
-    ScratchHandle s;
-    int32_t rc = s.open(device_id, N, d, G, chain, nullptr);
-    if (rc) return diag_fail(s, rc);
-    return diag_fail(s, demcz_mean_cov(&s.h, 1, G, mean, cov));
+    return with_arrays(device_id, N, d, G, chain, nullptr, [&](demcz_handle* h) { return demcz_mean_cov(h, 1, G, mean, cov); });
 }
 
 // ---- derived quantities: user functions of the draws (demcz_kernels_derive.h) -----------------------------------------------
@@ -4584,12 +4580,102 @@ extern "C" int32_t demcz_derive_check(int32_t d, int32_t m, const char* source, 
 }
 
 namespace {
-// The derived history of N x m x w values on `device`, generations g0 + 1 .. g0 + w, with `data` copied into memory it owns:
-// the ScratchHandle shape on the heap.  On failure everything made so far is freed, nullptr is returned and `why` says what failed.
-demcz_handle* derived_create(int device, int64_t N, int m, int64_t w, int64_t g0, const double* data, int64_t ndata, std::string& why,
-                             const char* who = "demcz_derive")
+// ---- what the workers on a window of a history share (derive, rank, pointwise, loo, bridge) --------------------------------------
+// A launch or a synchronisation that failed with DEMCZ_ERR_HIP says nothing about the kernels queued before it: the device is
+// synchronised before anything they may still be writing is released.  The one home of that rule: a worker passes the status of
+// its device work through here while the owners of what its kernels write (NewDerived, DevBlock) are still in scope.
+int32_t settle(int32_t rc)
 {
-    demcz_handle* dh = new demcz_handle;
+    if (rc == DEMCZ_ERR_HIP) (void)hipDeviceSynchronize();
+    return rc;
+}
+
+// A derived history between derived_create and its hand-over to the caller (release()).  A producer that fails on the way frees
+// it with free_all: only the producer knows it, and nothing has been queued on its stream since derived_create waited for it.
+struct FreeDerived {
+    void operator()(demcz_handle* dh) const { free_all(dh); delete dh; }
+};
+using NewDerived = std::unique_ptr<demcz_handle, FreeDerived>;
+
+// A complete derived history that a worker had a producer make, to take statistics of it and drop it: dropped as its user would,
+// with demcz_destroy, which waits for the history's own stream (the statistics ran there) before the buffers go back to the pools.
+// (Not a unique_ptr: the producers fill a demcz_handle**, as the entry points need it.)
+struct Part {
+    demcz_handle* h = nullptr;
+    Part() = default;
+    Part(const Part&) = delete;
+    Part& operator=(const Part&) = delete;
+    ~Part() { (void)demcz_destroy(h); }
+};
+
+// the status of a call on another handle than the caller's (a Part, the second history of a pair): its error message moves to
+// the handle the caller holds
+int32_t part_rc(demcz_handle* caller, const demcz_handle* part, int32_t rc)
+{
+    if (rc) caller->err = part->err;
+    return rc;
+}
+
+// A dev_malloc block that goes back to the pool when its scope ends (after settle(), if kernels were given it)
+struct DevBlock {
+    int device = 0;
+    void* p = nullptr;
+    DevBlock() = default;
+    DevBlock(const DevBlock&) = delete;
+    DevBlock& operator=(const DevBlock&) = delete;
+    ~DevBlock() { (void)dev_free(device, p); }
+    hipError_t alloc(int dev, size_t bytes)
+    {
+        device = dev;
+        const hipError_t e = dev_malloc(dev, &p, bytes);
+        if (e != hipSuccess) { (void)hipGetLastError(); p = nullptr; }
+        return e;
+    }
+};
+
+// The window g_from..g_to of h's history as the kernels index it: N chains, d columns, w generations from slot s0, total = N w
+struct Window {
+    int64_t N, w, s0, total;
+    int d;
+};
+
+// A worker's first stage: the range check, whose refusal names `who`, and the window.  Its own argument checks come next.
+int32_t open_window(demcz_handle* h, int64_t g_from, int64_t g_to, const char* who, Window& win)
+{
+    int32_t rc = check_hist_range(h, g_from, g_to, who);
+    if (rc) return rc;
+    win.N = h->cfg.N; win.d = h->cfg.d; win.w = g_to - g_from + 1; win.s0 = g_from - h->g0 - 1; win.total = win.N * win.w;
+    return DEMCZ_OK;
+}
+
+// ... and its second, behind those checks: h's device is current and what h's launches wrote is verified.  (quiesce_all stays the
+// worker's own line, right before its first allocation: some compile a program or check a size in between.)
+int32_t enter_device(demcz_handle* h)
+{
+    HIPCHK(h, hipSetDevice(h->cfg.device_id));
+    return live_verify(h);
+}
+
+// A producer's last stage, `launched` being what its one launch returned: a failed launch goes to h->err, otherwise h's stream is
+// waited for.  Then the history is the caller's; on a failure it stays with its owner, which frees it behind the settling here.
+int32_t finish(demcz_handle* h, const char* who, const char* kernel, hipError_t launched, NewDerived& dh, demcz_handle** out)
+{
+    int32_t rc = DEMCZ_ERR_HIP;
+    if (launched != hipSuccess) h->err = std::string(who) + ": launching " + kernel + ": " + hipGetErrorString(launched);
+    else rc = sync_stream(h, h->stream, who);
+    if (!rc) *out = dh.release();
+    return settle(rc);
+}
+
+// The derived history of N x m x w values on `device`, generations g0 + 1 .. g0 + w, with `data` copied into memory it owns:
+// a handle on the heap that outlives the call that makes it, its buffers and its stream from the pools.  ScratchHandle (above) is
+// the other builder of a handle that only holds a history: an _array call's uploads in hipMalloc blocks of their own, gone when
+// the call returns; they stay two so that neither's memory moves to where the other's comes from.  On failure everything made so
+// far is freed, null is returned and `why` says what failed.
+NewDerived derived_create(int device, int64_t N, int m, int64_t w, int64_t g0, const double* data, int64_t ndata, std::string& why,
+                          const char* who = "demcz_derive")
+{
+    NewDerived dh(new demcz_handle);
     dh->cfg.N = N; dh->cfg.d = m; dh->cfg.Gcap = w; dh->cfg.device_id = device; dh->cfg.nobs = ndata;
     dh->g0 = g0; dh->nranks = 1; dh->derived = true;
     dh->stage_cap = 4096 + (int64_t)m * (m + 1);
@@ -4603,51 +4689,41 @@ demcz_handle* derived_create(int device, int64_t N, int m, int64_t w, int64_t g0
     if (e != hipSuccess) {
         (void)hipGetLastError();
         why = std::string(who) + ": " + what + ": " + hipGetErrorString(e);
-        free_all(dh);
-        delete dh;
         return nullptr;
     }
     return dh;
 }
 
+unsigned derive_blocks(int64_t total) { return (unsigned)std::min<int64_t>((total + DERIVE_THREADS - 1) / DERIVE_THREADS, DERIVE_MAX_WG); }
+
 // demcz_derive on a source that holds an N x d x Gcap history (a sampling handle, a derived history, a ScratchHandle)
 int32_t derive_from(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t m, const char* source, const char* options,
                     const double* data, int64_t ndata, demcz_handle** derived)
 {
-    int32_t rc = check_hist_range(h, g_from, g_to, "demcz_derive");
+    const char* who = "demcz_derive";
+    Window win;
+    int32_t rc = open_window(h, g_from, g_to, who, win);
     if (rc) return rc;
     if (ndata < 0 || (ndata > 0 && !data)) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_derive: need ndata >= 0 and data for ndata > 0");
-    HIPCHK(h, hipSetDevice(h->cfg.device_id));
-    rc = live_verify(h);
+    rc = enter_device(h);
     if (rc) return rc;
     std::shared_ptr<const demcz_prog::Code> code;
     std::string err;
-    if (demcz_prog::get_code(h->cfg.d, source, options, demcz_prog::UNIT_DERIVE, code, err, m) != 0) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, err);
+    if (demcz_prog::get_code(win.d, source, options, demcz_prog::UNIT_DERIVE, code, err, m) != 0) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, err);
     demcz_prog::Module mod;
     if (demcz_prog::get_module(code, h->cfg.device_id, mod, err) != 0) return fail(h, DEMCZ_ERR_HIP, err);
     rc = quiesce_all(h);                        // (a sharded handle: the allocations below synchronise the device)
     if (rc) return rc;
-    int64_t N = h->cfg.N, w = g_to - g_from + 1, s0 = g_from - h->g0 - 1, total = N * w;
-    demcz_handle* dh = derived_create(h->cfg.device_id, N, m, w, g_from - 1, data, ndata, err);
+    NewDerived dh = derived_create(h->cfg.device_id, win.N, m, win.w, g_from - 1, data, ndata, err);
     if (!dh) return fail(h, DEMCZ_ERR_HIP, err);
     const double* chain = h->dchain;
     const double* logobj = h->dlogobj;          // (nullptr on a derived history and on arrays given without log_obj: logp is NaN)
     const double* ddata = ndata > 0 ? dh->d_design : nullptr;
     double* out = dh->dchain;
-    void* args[] = {&chain, &logobj, &N, &s0, &total, &ddata, &ndata, &out};
-    const unsigned blocks = (unsigned)std::min<int64_t>((total + DERIVE_THREADS - 1) / DERIVE_THREADS, DERIVE_MAX_WG);
+    void* args[] = {&chain, &logobj, &win.N, &win.s0, &win.total, &ddata, &ndata, &out};
     // on the source's stream: behind the window launches that write the history, and behind whatever else is queued there
-    hipError_t e = hipModuleLaunchKernel(mod.derive, blocks, 1, 1, DERIVE_THREADS, 1, 1, 0, h->stream, args, nullptr);
-    if (e != hipSuccess) h->err = std::string("demcz_derive: launching derive_kernel: ") + hipGetErrorString(e);
-    rc = (e != hipSuccess) ? DEMCZ_ERR_HIP : sync_stream(h, h->stream, "demcz_derive");
-    if (rc) {
-        if (rc == DEMCZ_ERR_HIP) (void)hipDeviceSynchronize();      // (the kernel may still be writing what is about to be freed)
-        free_all(dh);
-        delete dh;
-        return rc;
-    }
-    *derived = dh;
-    return DEMCZ_OK;
+    const hipError_t e = hipModuleLaunchKernel(mod.derive, derive_blocks(win.total), 1, 1, DERIVE_THREADS, 1, 1, 0, h->stream, args, nullptr);
+    return finish(h, who, "derive_kernel", e, dh, derived);
 }
 }  // namespace
 
@@ -4669,17 +4745,16 @@ extern "C" int32_t demcz_derive_array(int32_t device_id, const double* chain, co
     // (compiled before anything is uploaded: a program that does not compile costs no copy)
     int32_t rc = demcz_derive_check(d, m, source, options);
     if (rc) return rc;
-    ScratchHandle s;                            // (the uploads: freed when this call returns, only the derived history stays)
-    rc = s.open(device_id, N, d, G, chain, log_obj);
-    if (rc) return diag_fail(s, rc);
-    return diag_fail(s, derive_from(&s.h, 1, G, m, source, options, data, ndata, derived));
+    // (the uploads are freed when this call returns: only the derived history stays)
+    return with_arrays(device_id, N, d, G, chain, log_obj,
+                       [&](demcz_handle* h) { return derive_from(h, 1, G, m, source, options, data, ndata, derived); });
 }
 
 // ---- rank-normalised diagnostics (K10, demcz_kernels_rank.h): average ranks, normal scores, indicator columns -----------------
 namespace {
 // Everything a ranking needs besides the two key buffers, carved from ONE pool allocation so that there is one thing to free.
 struct RankScratch {
-    void* base = nullptr;
+    DevBlock base;
     uint64_t *buf0, *buf1;
     unsigned long long *hist, *nan;
     unsigned int* tcount;
@@ -4709,7 +4784,7 @@ struct RankSort {
     std::vector<unsigned int> hbase;
 };
 
-// the scratch layout of a sort of d columns of S keys; the caller frees rs.sc.base with dev_free
+// the scratch layout of a sort of d columns of S keys; freed with rs
 int32_t rank_sort_alloc(demcz_handle* h, int d, int64_t S, const char* who, RankSort& rs)
 {
     RankScratch& sc = rs.sc;
@@ -4718,13 +4793,10 @@ int32_t rank_sort_alloc(demcz_handle* h, int d, int64_t S, const char* who, Rank
     const size_t nkeys = (size_t)d * S, nhist = (size_t)d * RANK_DIGITS * 256, ntc = (size_t)d * ntiles * 256,
                  ninfo = (size_t)(RANK_DIGITS + 1) * d;
     const size_t bytes = 2 * nkeys * 8 + nhist * 8 + (size_t)d * 8 + (size_t)d * 8 + (ntc * 4 + 7) / 8 * 8 + nhist * 4 + (ninfo * 4 + 7) / 8 * 8;
-    hipError_t e = dev_malloc(h->cfg.device_id, &sc.base, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        sc.base = nullptr;
+    const hipError_t e = sc.base.alloc(h->cfg.device_id, bytes);
+    if (e != hipSuccess)
         return fail(h, DEMCZ_ERR_HIP, std::string(who) + ": the sort's scratch (two key buffers of N w d words): " + hipGetErrorString(e));
-    }
-    sc.buf0 = static_cast<uint64_t*>(sc.base);
+    sc.buf0 = static_cast<uint64_t*>(sc.base.p);
     sc.buf1 = sc.buf0 + nkeys;
     sc.hist = reinterpret_cast<unsigned long long*>(sc.buf1 + nkeys);
     sc.nan = sc.hist + nhist;
@@ -4808,28 +4880,24 @@ int32_t rank_from(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t mode, c
         return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_rank_normalize: mode is DEMCZ_RANK_Z or DEMCZ_RANK_AVERAGE");
     int32_t rc = rank_refuse_sharded(h, who);
     if (rc) return rc;
-    rc = check_hist_range(h, g_from, g_to, who);
+    Window win;
+    rc = open_window(h, g_from, g_to, who, win);
     if (rc) return rc;
-    HIPCHK(h, hipSetDevice(h->cfg.device_id));
-    rc = live_verify(h);
+    rc = enter_device(h);
     if (rc) return rc;
-    const int64_t N = h->cfg.N, w = g_to - g_from + 1, s0 = g_from - h->g0 - 1, S = N * w;
-    const int d = h->cfg.d;
+    const int64_t N = win.N, s0 = win.s0, S = win.total;
+    const int d = win.d;
     if (S >= ((int64_t)1 << 31) || d > 65535)
         return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_rank_normalize: at most 2^31 - 1 draws per parameter and 65535 parameters");
     rc = quiesce_all(h);                        // (the allocations below may synchronise the device)
     if (rc) return rc;
     std::string err;
-    demcz_handle* dh = derived_create(h->cfg.device_id, N, d, w, g_from - 1, nullptr, 0, err, who);
+    NewDerived dh = derived_create(h->cfg.device_id, N, d, win.w, g_from - 1, nullptr, 0, err, who);
     if (!dh) return fail(h, DEMCZ_ERR_HIP, err);
-    RankSort rs;
+    RankSort rs;                                // (behind dh: the scratch goes first)
     rc = rank_sort_alloc(h, d, S, who, rs);
-    if (rc) {
-        free_all(dh);
-        delete dh;
-        return rc;
-    }
-    auto body = [&]() -> int32_t {
+    if (rc) return rc;
+    auto body = [&]() -> int32_t {              // (HIPCHK returns from inside: one place where every such return is settled)
         int32_t r2 = rank_sort_run(h, N, d, s0, S, center, who, rs);
         if (r2) return r2;
         const RankScratch& sc = rs.sc;
@@ -4839,15 +4907,9 @@ int32_t rank_from(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t mode, c
         HIPCHK(h, hipGetLastError());
         return sync_stream(h, h->stream, who);
     };
-    rc = body();
-    if (rc == DEMCZ_ERR_HIP) (void)hipDeviceSynchronize();          // (a kernel may still be writing what is about to be freed)
-    (void)dev_free(h->cfg.device_id, rs.sc.base);
-    if (rc) {
-        free_all(dh);
-        delete dh;
-        return rc;
-    }
-    *ranked = dh;
+    rc = settle(body());
+    if (rc) return rc;
+    *ranked = dh.release();
     return DEMCZ_OK;
 }
 
@@ -4855,48 +4917,24 @@ int32_t rank_from(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t mode, c
 int32_t indicator_from(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t nthr, const double* thr, demcz_handle** derived)
 {
     const char* who = "demcz_indicator_le";
-    int32_t rc = check_hist_range(h, g_from, g_to, who);
+    Window win;
+    int32_t rc = open_window(h, g_from, g_to, who, win);
     if (rc) return rc;
-    if (nthr < 1 || nthr > 64 || (int64_t)h->cfg.d * nthr > 65535)
+    if (nthr < 1 || nthr > 64 || (int64_t)win.d * nthr > 65535)
         return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_indicator_le: 1 <= nthr <= 64 and d nthr <= 65535");
-    HIPCHK(h, hipSetDevice(h->cfg.device_id));
-    rc = live_verify(h);
+    rc = enter_device(h);
     if (rc) return rc;
     rc = quiesce_all(h);
     if (rc) return rc;
-    const int64_t N = h->cfg.N, w = g_to - g_from + 1, s0 = g_from - h->g0 - 1;
-    const int d = h->cfg.d, m = d * nthr;
-    const int64_t total = N * m * w;
+    const int m = win.d * nthr;
+    const int64_t total = win.total * m;
     std::string err;
-    demcz_handle* dh = derived_create(h->cfg.device_id, N, m, w, g_from - 1, thr, (int64_t)m, err, who);   // (the thresholds: its data)
+    NewDerived dh = derived_create(h->cfg.device_id, win.N, m, win.w, g_from - 1, thr, (int64_t)m, err, who);   // (the thresholds: its data)
     if (!dh) return fail(h, DEMCZ_ERR_HIP, err);
     const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 8192);
-    hipLaunchKernelGGL(indicator_le_kernel, dim3(blocks), dim3(256), 0, h->stream, (const double*)h->dchain, N, d, s0, total, (int)nthr,
-                       (const double*)dh->d_design, dh->dchain);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) h->err = std::string("demcz_indicator_le: launching indicator_le_kernel: ") + hipGetErrorString(e);
-    rc = (e != hipSuccess) ? DEMCZ_ERR_HIP : sync_stream(h, h->stream, who);
-    if (rc) {
-        if (rc == DEMCZ_ERR_HIP) (void)hipDeviceSynchronize();
-        free_all(dh);
-        delete dh;
-        return rc;
-    }
-    *derived = dh;
-    return DEMCZ_OK;
-}
-
-// a statistic of a derived history made on the way; its error message moves to the handle the caller holds
-int32_t rank_part(demcz_handle* h, demcz_handle* part, int32_t rc)
-{
-    if (rc) h->err = part->err;
-    return rc;
-}
-
-void rank_drop(demcz_handle* dh)
-{
-    if (!dh) return;
-    (void)demcz_destroy(dh);
+    hipLaunchKernelGGL(indicator_le_kernel, dim3(blocks), dim3(256), 0, h->stream, (const double*)h->dchain, win.N, win.d, win.s0, total,
+                       (int)nthr, (const double*)dh->d_design, dh->dchain);
+    return finish(h, who, "indicator_le_kernel", hipGetLastError(), dh, derived);
 }
 
 int32_t rank_diagnostics_from(demcz_handle* h, int64_t g_from, int64_t g_to, double* rhat_rank, double* ess_bulk, double* ess_tail)
@@ -4912,18 +4950,17 @@ int32_t rank_diagnostics_from(demcz_handle* h, int64_t g_from, int64_t g_to, dou
     std::vector<double> q((size_t)3 * d), a((size_t)2 * d), b((size_t)d);
     rc = demcz_quantiles(h, g_from, g_to, 3, probs, q.data(), nullptr, nullptr);
     if (rc) return rc;
-    demcz_handle *zb = nullptr, *zf = nullptr, *ind = nullptr;
-    if (rhat_rank || ess_bulk) {
-        rc = rank_from(h, g_from, g_to, DEMCZ_RANK_Z, nullptr, &zb);
-        if (!rc && ess_bulk) rc = rank_part(h, zb, demcz_ess(zb, g_from, g_to, 0, ess_bulk, nullptr, nullptr, nullptr, nullptr));
-        if (!rc && rhat_rank) rc = rank_part(h, zb, demcz_rhat(zb, g_from, g_to, a.data()));
-        rank_drop(zb);
+    if (rhat_rank || ess_bulk) {                // (each part is dropped before the next is made: it takes the same memory)
+        Part zb;
+        rc = rank_from(h, g_from, g_to, DEMCZ_RANK_Z, nullptr, &zb.h);
+        if (!rc && ess_bulk) rc = part_rc(h, zb.h, demcz_ess(zb.h, g_from, g_to, 0, ess_bulk, nullptr, nullptr, nullptr, nullptr));
+        if (!rc && rhat_rank) rc = part_rc(h, zb.h, demcz_rhat(zb.h, g_from, g_to, a.data()));
         if (rc) return rc;
     }
     if (rhat_rank) {
-        rc = rank_from(h, g_from, g_to, DEMCZ_RANK_Z, q.data() + d, &zf);               // folded at the median
-        if (!rc) rc = rank_part(h, zf, demcz_rhat(zf, g_from, g_to, b.data()));
-        rank_drop(zf);
+        Part zf;
+        rc = rank_from(h, g_from, g_to, DEMCZ_RANK_Z, q.data() + d, &zf.h);             // folded at the median
+        if (!rc) rc = part_rc(h, zf.h, demcz_rhat(zf.h, g_from, g_to, b.data()));
         if (rc) return rc;
         for (int p = 0; p < d; ++p)
             rhat_rank[p] = (a[p] != a[p] || b[p] != b[p]) ? std::nan("") : std::max(a[p], b[p]);
@@ -4931,9 +4968,9 @@ int32_t rank_diagnostics_from(demcz_handle* h, int64_t g_from, int64_t g_to, dou
     if (ess_tail) {
         std::vector<double> thr((size_t)2 * d);
         for (int p = 0; p < d; ++p) { thr[p] = q[p]; thr[(size_t)d + p] = q[(size_t)2 * d + p]; }
-        rc = indicator_from(h, g_from, g_to, 2, thr.data(), &ind);
-        if (!rc) rc = rank_part(h, ind, demcz_ess(ind, g_from, g_to, 0, a.data(), nullptr, nullptr, nullptr, nullptr));
-        rank_drop(ind);
+        Part ind;
+        rc = indicator_from(h, g_from, g_to, 2, thr.data(), &ind.h);
+        if (!rc) rc = part_rc(h, ind.h, demcz_ess(ind.h, g_from, g_to, 0, a.data(), nullptr, nullptr, nullptr, nullptr));
         if (rc) return rc;
         for (int p = 0; p < d; ++p) {
             const double lo = a[p], hi = a[(size_t)d + p];
@@ -4958,10 +4995,8 @@ extern "C" int32_t demcz_rank_normalize_array(int32_t device_id, const double* c
 {
     if (!chain || !ranked) return DEMCZ_ERR_INVALID_ARGUMENT;
     *ranked = nullptr;
-    ScratchHandle s;                            // (the upload: freed when this call returns, only the ranked history stays)
-    int32_t rc = s.open(device_id, N, d, G, chain, nullptr);
-    if (rc) return diag_fail(s, rc);
-    return diag_fail(s, rank_from(&s.h, 1, G, mode, center, ranked));
+    // (the upload is freed when this call returns: only the ranked history stays)
+    return with_arrays(device_id, N, d, G, chain, nullptr, [&](demcz_handle* h) { return rank_from(h, 1, G, mode, center, ranked); });
 }
 
 extern "C" int32_t demcz_indicator_le(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t nthr, const double* thr,
@@ -4987,10 +5022,8 @@ extern "C" int32_t demcz_rank_diagnostics_array(int32_t device_id, const double*
                                                 double* rhat_rank, double* ess_bulk, double* ess_tail)
 {
     if (!chain || (!rhat_rank && !ess_bulk && !ess_tail)) return DEMCZ_ERR_INVALID_ARGUMENT;
-    ScratchHandle s;
-    int32_t rc = s.open(device_id, N, d, G, chain, nullptr);
-    if (rc) return diag_fail(s, rc);
-    return diag_fail(s, rank_diagnostics_from(&s.h, 1, G, rhat_rank, ess_bulk, ess_tail));
+    return with_arrays(device_id, N, d, G, chain, nullptr,
+                       [&](demcz_handle* h) { return rank_diagnostics_from(h, 1, G, rhat_rank, ess_bulk, ess_tail); });
 }
 
 // ---- PSIS-LOO and WAIC (demcz_kernels_pointwise.h, K11 demcz_kernels_loo.h, demcz_loo_host.h) -----------------------------------
@@ -5007,41 +5040,31 @@ namespace {
 int32_t pointwise_from(demcz_handle* h, int64_t g_from, int64_t g_to, int64_t obs_from, int32_t mc, const char* source, const char* options,
                        const double* data, int64_t ndata, demcz_handle** derived)
 {
-    int32_t rc = check_hist_range(h, g_from, g_to, "demcz_pointwise");
+    const char* who = "demcz_pointwise";
+    Window win;
+    int32_t rc = open_window(h, g_from, g_to, who, win);
     if (rc) return rc;
     if (ndata < 0 || (ndata > 0 && !data)) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_pointwise: need ndata >= 0 and data for ndata > 0");
     if (mc < 1 || mc > LOO_MAX_CHUNK || obs_from < 0)
         return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "pointwise program: mc must be in 1.." + std::to_string(LOO_MAX_CHUNK) + " and obs_from >= 0");
-    HIPCHK(h, hipSetDevice(h->cfg.device_id));
-    rc = live_verify(h);
+    rc = enter_device(h);
     if (rc) return rc;
     std::shared_ptr<const demcz_prog::Code> code;
     std::string err;
-    if (demcz_prog::get_code(h->cfg.d, source, options, demcz_prog::UNIT_POINTWISE, code, err) != 0) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, err);
+    if (demcz_prog::get_code(win.d, source, options, demcz_prog::UNIT_POINTWISE, code, err) != 0) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, err);
     demcz_prog::Module mod;
     if (demcz_prog::get_module(code, h->cfg.device_id, mod, err) != 0) return fail(h, DEMCZ_ERR_HIP, err);
     rc = quiesce_all(h);                        // (a sharded handle: the allocations below synchronise the device)
     if (rc) return rc;
-    int64_t N = h->cfg.N, w = g_to - g_from + 1, s0 = g_from - h->g0 - 1, total = N * w;
-    demcz_handle* dh = derived_create(h->cfg.device_id, N, mc, w, g_from - 1, data, ndata, err, "demcz_pointwise");
+    NewDerived dh = derived_create(h->cfg.device_id, win.N, mc, win.w, g_from - 1, data, ndata, err, who);
     if (!dh) return fail(h, DEMCZ_ERR_HIP, err);
     const double* chain = h->dchain;
     const double* ddata = ndata > 0 ? dh->d_design : nullptr;
     double* out = dh->dchain;
     int mcount = mc;
-    void* args[] = {&chain, &N, &s0, &total, &ddata, &ndata, &obs_from, &mcount, &out};
-    const unsigned blocks = (unsigned)std::min<int64_t>((total + DERIVE_THREADS - 1) / DERIVE_THREADS, DERIVE_MAX_WG);
-    hipError_t e = hipModuleLaunchKernel(mod.derive, blocks, 1, 1, DERIVE_THREADS, 1, 1, 0, h->stream, args, nullptr);
-    if (e != hipSuccess) h->err = std::string("demcz_pointwise: launching pointwise_kernel: ") + hipGetErrorString(e);
-    rc = (e != hipSuccess) ? DEMCZ_ERR_HIP : sync_stream(h, h->stream, "demcz_pointwise");
-    if (rc) {
-        if (rc == DEMCZ_ERR_HIP) (void)hipDeviceSynchronize();      // (the kernel may still be writing what is about to be freed)
-        free_all(dh);
-        delete dh;
-        return rc;
-    }
-    *derived = dh;
-    return DEMCZ_OK;
+    void* args[] = {&chain, &win.N, &win.s0, &win.total, &ddata, &ndata, &obs_from, &mcount, &out};
+    const hipError_t e = hipModuleLaunchKernel(mod.derive, derive_blocks(win.total), 1, 1, DERIVE_THREADS, 1, 1, 0, h->stream, args, nullptr);
+    return finish(h, who, "pointwise_kernel", e, dh, derived);
 }
 
 // demcz_loo_columns on such a source: the d columns of the window are the log-likelihoods of d observations
@@ -5051,16 +5074,16 @@ int32_t loo_columns_from(demcz_handle* h, int64_t g_from, int64_t g_to, const do
     const char* who = "demcz_loo_columns";
     int32_t rc = rank_refuse_sharded(h, who);
     if (rc) return rc;
-    rc = check_hist_range(h, g_from, g_to, who);
+    Window win;
+    rc = open_window(h, g_from, g_to, who, win);
     if (rc) return rc;
-    const int64_t N = h->cfg.N, w = g_to - g_from + 1, s0 = g_from - h->g0 - 1, S = N * w;
-    const int d = h->cfg.d;
+    const int64_t N = win.N, s0 = win.s0, S = win.total;
+    const int d = win.d;
     if (r_eff)
         for (int p = 0; p < d; ++p)
             if (!(r_eff[p] > 0.0) || !(r_eff[p] < INFINITY))
                 return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_loo_columns: every r_eff must be in (0, inf)");
-    HIPCHK(h, hipSetDevice(h->cfg.device_id));
-    rc = live_verify(h);
+    rc = enter_device(h);
     if (rc) return rc;
     if (S >= ((int64_t)1 << 31) || d > 65535)
         return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_loo_columns: at most 2^31 - 1 draws per column and 65535 columns");
@@ -5072,21 +5095,17 @@ int32_t loo_columns_from(demcz_handle* h, int64_t g_from, int64_t g_to, const do
     // [fit | part | out (4 d doubles) | n_tail (d) | r_eff (d)], every piece a multiple of 8 bytes
     const int64_t ntiles = (S + LOO_TILE - 1) / LOO_TILE;
     const size_t fit_bytes = ((size_t)d * sizeof(LooFit) + 7) / 8 * 8, npart = (size_t)d * ntiles * LOO_NPART;
-    void* base = nullptr;
-    hipError_t e = dev_malloc(h->cfg.device_id, &base, fit_bytes + npart * 8 + (size_t)6 * d * 8);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        (void)dev_free(h->cfg.device_id, rs.sc.base);
-        return fail(h, DEMCZ_ERR_HIP, std::string(who) + ": the fit table and the tile sums: " + hipGetErrorString(e));
-    }
-    LooFit* fit = static_cast<LooFit*>(base);
-    double* part = reinterpret_cast<double*>(static_cast<char*>(base) + fit_bytes);
+    DevBlock base;                              // (behind rs: freed first)
+    const hipError_t e = base.alloc(h->cfg.device_id, fit_bytes + npart * 8 + (size_t)6 * d * 8);
+    if (e != hipSuccess) return fail(h, DEMCZ_ERR_HIP, std::string(who) + ": the fit table and the tile sums: " + hipGetErrorString(e));
+    LooFit* fit = static_cast<LooFit*>(base.p);
+    double* part = reinterpret_cast<double*>(static_cast<char*>(base.p) + fit_bytes);
     double* dout = part + npart;
     long long* dtail = reinterpret_cast<long long*>(dout + (size_t)4 * d);
     double* dreff = reinterpret_cast<double*>(dtail + d);
     std::vector<double> hout((size_t)4 * d), hreff;
     std::vector<long long> htail((size_t)d);
-    auto body = [&]() -> int32_t {
+    auto body = [&]() -> int32_t {              // (HIPCHK returns from inside: one place where every such return is settled)
         int32_t r2 = rank_sort_run(h, N, d, s0, S, nullptr, who, rs);
         if (r2) return r2;
         const RankScratch& sc = rs.sc;
@@ -5108,10 +5127,7 @@ int32_t loo_columns_from(demcz_handle* h, int64_t g_from, int64_t g_to, const do
         HIPCHK(h, hipMemcpyAsync(htail.data(), dtail, htail.size() * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
         return sync_stream(h, h->stream, who);
     };
-    rc = body();
-    if (rc == DEMCZ_ERR_HIP) (void)hipDeviceSynchronize();          // (a kernel may still be writing what is about to be freed)
-    (void)dev_free(h->cfg.device_id, base);
-    (void)dev_free(h->cfg.device_id, rs.sc.base);
+    rc = settle(body());
     if (rc) return rc;
     for (int p = 0; p < d; ++p) {
         if (elpd_loo) elpd_loo[p] = hout[p];
@@ -5143,13 +5159,12 @@ int32_t loo_from(demcz_handle* h, int64_t g_from, int64_t g_to, int64_t nobs, co
         int64_t from = 0;
         int count = 0;
         loo_chunk(nobs, mc, i, &from, &count);
-        demcz_handle* dh = nullptr;
-        rc = pointwise_from(h, g_from, g_to, from, count, source, options, data, ndata, &dh);
+        Part dh;
+        rc = pointwise_from(h, g_from, g_to, from, count, source, options, data, ndata, &dh.h);
         if (rc) return rc;
-        rc = rank_part(h, dh, loo_columns_from(dh, g_from, g_to, r_eff ? r_eff + from : nullptr, elpd_loo ? elpd_loo + from : nullptr,
-                                               pareto_k ? pareto_k + from : nullptr, n_tail ? n_tail + from : nullptr,
-                                               lppd ? lppd + from : nullptr, p_waic ? p_waic + from : nullptr));
-        rank_drop(dh);
+        rc = part_rc(h, dh.h, loo_columns_from(dh.h, g_from, g_to, r_eff ? r_eff + from : nullptr, elpd_loo ? elpd_loo + from : nullptr,
+                                                pareto_k ? pareto_k + from : nullptr, n_tail ? n_tail + from : nullptr,
+                                                lppd ? lppd + from : nullptr, p_waic ? p_waic + from : nullptr));
         if (rc) return rc;
     }
     return DEMCZ_OK;
@@ -5173,10 +5188,8 @@ extern "C" int32_t demcz_pointwise_array(int32_t device_id, const double* chain,
     *derived = nullptr;
     int32_t rc = demcz_pointwise_check(d, source, options);     // (compiled before anything is uploaded)
     if (rc) return rc;
-    ScratchHandle s;
-    rc = s.open(device_id, N, d, G, chain, nullptr);
-    if (rc) return diag_fail(s, rc);
-    return diag_fail(s, pointwise_from(&s.h, 1, G, obs_from, mc, source, options, data, ndata, derived));
+    return with_arrays(device_id, N, d, G, chain, nullptr,
+                       [&](demcz_handle* h) { return pointwise_from(h, 1, G, obs_from, mc, source, options, data, ndata, derived); });
 }
 
 extern "C" int32_t demcz_loo_columns(demcz_handle* h, int64_t g_from, int64_t g_to, const double* r_eff, double* elpd_loo,
@@ -5191,10 +5204,8 @@ extern "C" int32_t demcz_loo_columns_array(int32_t device_id, const double* chai
                                            double* elpd_loo, double* pareto_k, int64_t* n_tail, double* lppd, double* p_waic)
 {
     if (!chain) return DEMCZ_ERR_INVALID_ARGUMENT;
-    ScratchHandle s;
-    int32_t rc = s.open(device_id, N, d, G, chain, nullptr);
-    if (rc) return diag_fail(s, rc);
-    return diag_fail(s, loo_columns_from(&s.h, 1, G, r_eff, elpd_loo, pareto_k, n_tail, lppd, p_waic));
+    return with_arrays(device_id, N, d, G, chain, nullptr,
+                       [&](demcz_handle* h) { return loo_columns_from(h, 1, G, r_eff, elpd_loo, pareto_k, n_tail, lppd, p_waic); });
 }
 
 extern "C" int32_t demcz_loo(demcz_handle* h, int64_t g_from, int64_t g_to, int64_t nobs, const char* source, const char* options,
@@ -5213,10 +5224,9 @@ extern "C" int32_t demcz_loo_array(int32_t device_id, const double* chain, int64
     if (!chain) return DEMCZ_ERR_INVALID_ARGUMENT;
     int32_t rc = demcz_pointwise_check(d, source, options);     // (compiled before anything is uploaded)
     if (rc) return rc;
-    ScratchHandle s;
-    rc = s.open(device_id, N, d, G, chain, nullptr);
-    if (rc) return diag_fail(s, rc);
-    return diag_fail(s, loo_from(&s.h, 1, G, nobs, source, options, data, ndata, r_eff, elpd_loo, pareto_k, n_tail, lppd, p_waic));
+    return with_arrays(device_id, N, d, G, chain, nullptr, [&](demcz_handle* h) {
+        return loo_from(h, 1, G, nobs, source, options, data, ndata, r_eff, elpd_loo, pareto_k, n_tail, lppd, p_waic);
+    });
 }
 
 // ---- the marginal likelihood by bridge sampling (K12, demcz_kernels_bridge.h; DESIGN.md sections 3 and 4.17) ---------------------
@@ -5294,55 +5304,35 @@ int32_t bridge_cholesky(demcz_handle* h, int d, const double* V, double* L, cons
     return DEMCZ_OK;
 }
 
-void bridge_free(demcz_handle*& dh)
-{
-    if (!dh) return;
-    free_all(dh);
-    delete dh;
-    dh = nullptr;
-}
-
-unsigned bridge_blocks(int64_t total) { return (unsigned)std::min<int64_t>((total + DERIVE_THREADS - 1) / DERIVE_THREADS, DERIVE_MAX_WG); }
-
 // demcz_bridge_posterior on a source with a chain and a log_obj history (a sampling handle, a ScratchHandle)
 int32_t bridge_posterior_from(demcz_handle* h, int64_t g_from, int64_t g_to, const double* mean, const double* L, demcz_handle** derived)
 {
     const char* who = "demcz_bridge_posterior";
-    int32_t rc = check_hist_range(h, g_from, g_to, who);
+    Window win;
+    int32_t rc = open_window(h, g_from, g_to, who, win);
     if (rc) return rc;
     if (!h->dlogobj || !h->dchain) return fail(h, DEMCZ_ERR_STATE, std::string(who) + ": the source keeps no log_obj history");
-    const int d = h->cfg.d;
     std::vector<double> mL;
     double cg = 0.0;
-    rc = bridge_pack(h, d, mean, L, who, mL, cg);
+    rc = bridge_pack(h, win.d, mean, L, who, mL, cg);
     if (rc) return rc;
-    const void* fn = bridge_posterior_fn(d);
+    const void* fn = bridge_posterior_fn(win.d);
     if (!fn) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": no kernel for this d");
-    HIPCHK(h, hipSetDevice(h->cfg.device_id));
-    rc = live_verify(h);
+    rc = enter_device(h);
     if (rc) return rc;
     rc = quiesce_all(h);                        // (the allocations below may synchronise the device)
     if (rc) return rc;
-    int64_t N = h->cfg.N, w = g_to - g_from + 1, s0 = g_from - h->g0 - 1, total = N * w;
     std::string err;
     // (the proposal rides in the derived history's data slot: freed with it)
-    demcz_handle* dh = derived_create(h->cfg.device_id, N, 1, w, g_from - 1, mL.data(), (int64_t)mL.size(), err, who);
+    NewDerived dh = derived_create(h->cfg.device_id, win.N, 1, win.w, g_from - 1, mL.data(), (int64_t)mL.size(), err, who);
     if (!dh) return fail(h, DEMCZ_ERR_HIP, err);
     const double* chain = h->dchain;
     const double* logobj = h->dlogobj;
     const double* dmL = dh->d_design;
     double* out = dh->dchain;
-    void* args[] = {&chain, &logobj, &N, &s0, &total, &dmL, &cg, &out};
-    hipError_t e = hipLaunchKernel(fn, dim3(bridge_blocks(total)), dim3(DERIVE_THREADS), args, 0, h->stream);
-    if (e != hipSuccess) h->err = std::string(who) + ": launching bridge_posterior_kernel: " + hipGetErrorString(e);
-    rc = (e != hipSuccess) ? DEMCZ_ERR_HIP : sync_stream(h, h->stream, who);
-    if (rc) {
-        if (rc == DEMCZ_ERR_HIP) (void)hipDeviceSynchronize();      // (the kernel may still be writing what is about to be freed)
-        bridge_free(dh);
-        return rc;
-    }
-    *derived = dh;
-    return DEMCZ_OK;
+    void* args[] = {&chain, &logobj, &win.N, &win.s0, &win.total, &dmL, &cg, &out};
+    const hipError_t e = hipLaunchKernel(fn, dim3(derive_blocks(win.total)), dim3(DERIVE_THREADS), args, 0, h->stream);
+    return finish(h, who, "bridge_posterior_kernel", e, dh, derived);
 }
 
 // What evaluates the target at the proposal's draws: a built-in target's kernel with its parameters, or a program's bridge unit
@@ -5417,12 +5407,12 @@ int32_t bridge_proposal_from(demcz_handle* h, int d, const BridgeTarget& t, int6
     // the proposal and, behind it, a program's data ride in the a2 history's data slot
     std::vector<double> slot(mL);
     if (t.hdata && t.ndata > 0) slot.insert(slot.end(), t.hdata, t.hdata + t.ndata);
-    demcz_handle* da = derived_create(h->cfg.device_id, Np, 1, wp, 0, slot.data(), (int64_t)slot.size(), err, who);
+    NewDerived dx;                              // (the draws; declared first: on a failure a2 is freed before them)
+    NewDerived da = derived_create(h->cfg.device_id, Np, 1, wp, 0, slot.data(), (int64_t)slot.size(), err, who);
     if (!da) return fail(h, DEMCZ_ERR_HIP, err);
-    demcz_handle* dx = nullptr;
     if (draws) {
         dx = derived_create(h->cfg.device_id, Np, d, wp, 0, nullptr, 0, err, who);
-        if (!dx) { bridge_free(da); return fail(h, DEMCZ_ERR_HIP, err); }
+        if (!dx) return fail(h, DEMCZ_ERR_HIP, err);
     }
     int64_t N = Np, total = Np * wp, ndata = t.ndata;
     const double* dmL = da->d_design;
@@ -5432,23 +5422,15 @@ int32_t bridge_proposal_from(demcz_handle* h, int d, const BridgeTarget& t, int6
     hipError_t e;
     if (t.prog) {
         void* args[] = {&N, &total, &seed, &dmL, &cg, &ddata, &ndata, &a2, &xs};
-        e = hipModuleLaunchKernel(t.prog, bridge_blocks(total), 1, 1, DERIVE_THREADS, 1, 1, 0, h->stream, args, nullptr);
+        e = hipModuleLaunchKernel(t.prog, derive_blocks(total), 1, 1, DERIVE_THREADS, 1, 1, 0, h->stream, args, nullptr);
     } else {
         TargetParams tp = t.tp;
         void* args[] = {&tp, &N, &total, &seed, &dmL, &cg, &a2, &xs};
-        e = hipLaunchKernel(t.fn, dim3(bridge_blocks(total)), dim3(DERIVE_THREADS), args, 0, h->stream);
+        e = hipLaunchKernel(t.fn, dim3(derive_blocks(total)), dim3(DERIVE_THREADS), args, 0, h->stream);
     }
-    if (e != hipSuccess) h->err = std::string(who) + ": launching bridge_proposal_kernel: " + hipGetErrorString(e);
-    rc = (e != hipSuccess) ? DEMCZ_ERR_HIP : sync_stream(h, h->stream, who);
-    if (rc) {
-        if (rc == DEMCZ_ERR_HIP) (void)hipDeviceSynchronize();      // (the kernel may still be writing what is about to be freed)
-        bridge_free(da);
-        bridge_free(dx);
-        return rc;
-    }
-    *logratio = da;
-    if (draws) *draws = dx;
-    return DEMCZ_OK;
+    rc = finish(h, who, "bridge_proposal_kernel", e, da, logratio);
+    if (!rc && draws) *draws = dx.release();
+    return rc;
 }
 
 // updates queued between two synchronisations (DEMCZ_BRIDGE_BATCH: 1..64; the result does not depend on it)
@@ -5473,8 +5455,8 @@ int32_t bridge_iterate_from(demcz_handle* post, int64_t g_from, int64_t g_to, de
     const char* who = "demcz_bridge_iterate";
     int32_t rc = check_hist_range(post, g_from, g_to, who);
     if (rc) return rc;
-    rc = check_hist_range(prop, gp_from, gp_to, who);
-    if (rc) { post->err = prop->err; return rc; }
+    rc = part_rc(post, prop, check_hist_range(prop, gp_from, gp_to, who));       // (post is the handle the caller asks about)
+    if (rc) return rc;
     if (post->cfg.d != 1 || prop->cfg.d != 1 || !post->dchain || !prop->dchain)
         return fail(post, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": both histories must have one column");
     if (post->cfg.device_id != prop->cfg.device_id)
@@ -5486,39 +5468,35 @@ int32_t bridge_iterate_from(demcz_handle* post, int64_t g_from, int64_t g_to, de
     HIPCHK(post, hipSetDevice(post->cfg.device_id));
     rc = live_verify(post);
     if (rc) return rc;
-    rc = live_verify(prop);
-    if (rc) { post->err = prop->err; return rc; }
+    rc = part_rc(post, prop, live_verify(prop));
+    if (rc) return rc;
     rc = quiesce_all(post);
     if (rc) return rc;
-    rc = sync_stream(prop, prop->stream, who);  // (what wrote a2 ran on its own stream)
-    if (rc) { post->err = prop->err; return rc; }
+    rc = part_rc(post, prop, sync_stream(prop, prop->stream, who));      // (what wrote a2 ran on its own stream)
+    if (rc) return rc;
     const double ne = (neff > 0.0) ? neff : (double)n1;
     double s1 = ne / (ne + (double)n2), s2 = 1.0 - s1;
     const double* a1 = post->dchain + post->cfg.N * (g_from - post->g0 - 1);
     const double* a2 = prop->dchain + prop->cfg.N * (gp_from - prop->g0 - 1);
     int64_t ntiles = (std::max(n1, n2) + BRIDGE_TILE - 1) / BRIDGE_TILE;
     std::string err;
-    demcz_handle* df = nullptr;
+    NewDerived df;
     if (f2) {
         df = derived_create(post->cfg.device_id, post->cfg.N, 1, g_to - g_from + 1, g_from - 1, nullptr, 0, err, who);
         if (!df) return fail(post, DEMCZ_ERR_HIP, err);
     }
     // [state | part (2 ntiles BRIDGE_NPART doubles)]
     const size_t st_bytes = (sizeof(BridgeState) + 7) / 8 * 8;
-    void* base = nullptr;
-    hipError_t e = dev_malloc(post->cfg.device_id, &base, st_bytes + (size_t)2 * ntiles * BRIDGE_NPART * 8);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        bridge_free(df);
-        return fail(post, DEMCZ_ERR_HIP, std::string(who) + ": the tile sums: " + hipGetErrorString(e));
-    }
-    BridgeState* st = static_cast<BridgeState*>(base);
-    double* part = reinterpret_cast<double*>(static_cast<char*>(base) + st_bytes);
+    DevBlock base;                              // (behind df: freed first)
+    const hipError_t e = base.alloc(post->cfg.device_id, st_bytes + (size_t)2 * ntiles * BRIDGE_NPART * 8);
+    if (e != hipSuccess) return fail(post, DEMCZ_ERR_HIP, std::string(who) + ": the tile sums: " + hipGetErrorString(e));
+    BridgeState* st = static_cast<BridgeState*>(base.p);
+    double* part = reinterpret_cast<double*>(static_cast<char*>(base.p) + st_bytes);
     double* f2out = df ? df->dchain : nullptr;
     BridgeState hs;
     const int batch = bridge_batch();
     hipStream_t s = post->stream;
-    auto body = [&]() -> int32_t {
+    auto body = [&]() -> int32_t {              // (HIPCHK returns from inside: one place where every such return is settled)
         HIPCHK(post, hipMemsetAsync(st, 0, st_bytes, s));
         int64_t tiles1 = (n1 + BRIDGE_TILE - 1) / BRIDGE_TILE;               // (<= ntiles: the maxima fit in part)
         for (int stage = 0; stage < 2; ++stage) {
@@ -5545,13 +5523,8 @@ int32_t bridge_iterate_from(demcz_handle* post, int64_t g_from, int64_t g_to, de
         HIPCHK(post, hipMemcpyAsync(&hs, st, sizeof(BridgeState), hipMemcpyDeviceToHost, s));
         return sync_stream(post, s, who);
     };
-    rc = body();
-    if (rc == DEMCZ_ERR_HIP) (void)hipDeviceSynchronize();          // (a kernel may still be writing what is about to be freed)
-    (void)dev_free(post->cfg.device_id, base);
-    if (rc) {
-        bridge_free(df);
-        return rc;
-    }
+    rc = settle(body());
+    if (rc) return rc;
     res.logml = hs.rho;
     res.iterations = (int64_t)hs.iterations;
     res.converged = hs.converged;
@@ -5561,7 +5534,7 @@ int32_t bridge_iterate_from(demcz_handle* post, int64_t g_from, int64_t g_to, de
     res.moments[1] = ok ? hs.var[0] : NAN;
     res.moments[2] = ok ? hs.mean[1] : NAN;
     res.moments[3] = ok ? hs.var[1] : NAN;
-    if (f2) *f2 = df;
+    if (f2) *f2 = df.release();
     return DEMCZ_OK;
 }
 
@@ -5593,20 +5566,18 @@ int32_t bridge_from(demcz_handle* h, const BridgeTarget& t, int64_t g_from, int6
     if (rc) return rc;
     rc = bridge_cholesky(h, d, V.data(), L.data(), who);
     if (rc) return rc;
-    demcz_handle *post = nullptr, *prop = nullptr, *f2 = nullptr;
+    Part post, prop, f2;                        // (dropped when this call returns: f2, prop, post)
     BridgeResult res;
     double ess = NAN;
-    rc = bridge_posterior_from(h, g_from + hw, g_to, m.data(), L.data(), &post);
-    if (!rc) rc = bridge_proposal_from(h, d, t, N, w - hw, seed, m.data(), L.data(), &prop, nullptr);
-    if (!rc) rc = bridge_iterate_from(post, g_from + hw, g_to, prop, 1, w - hw, neff, tol, max_iter, res, &f2);
-    if (rc && post && !post->err.empty() && h->err.empty()) h->err = post->err;
+    rc = bridge_posterior_from(h, g_from + hw, g_to, m.data(), L.data(), &post.h);
+    if (!rc) rc = bridge_proposal_from(h, d, t, N, w - hw, seed, m.data(), L.data(), &prop.h, nullptr);
+    if (!rc) rc = bridge_iterate_from(post.h, g_from + hw, g_to, prop.h, 1, w - hw, neff, tol, max_iter, res, &f2.h);
+    // (not part_rc: the two producers report on h, only bridge_iterate_from on post, and its message moves up where h has none)
+    if (rc && post.h && !post.h->err.empty() && h->err.empty()) h->err = post.h->err;
     if (!rc && res.logml == res.logml && w - hw >= 4) {
         int32_t conv = 0;
-        rc = rank_part(h, f2, demcz_ess(f2, g_from + hw, g_to, 0, &ess, nullptr, nullptr, nullptr, &conv));
+        rc = part_rc(h, f2.h, demcz_ess(f2.h, g_from + hw, g_to, 0, &ess, nullptr, nullptr, nullptr, &conv));
     }
-    rank_drop(f2);
-    rank_drop(prop);
-    rank_drop(post);
     if (rc) return rc;
     const int64_t n1 = N * (w - hw), n2 = n1;
     double se = NAN;
@@ -5645,10 +5616,7 @@ extern "C" int32_t demcz_bridge_posterior_array(int32_t device_id, const double*
 {
     if (derived) *derived = nullptr;
     if (!chain || !log_obj || !derived || !mean || !L) return DEMCZ_ERR_INVALID_ARGUMENT;
-    ScratchHandle s;
-    int32_t rc = s.open(device_id, N, d, G, chain, log_obj);
-    if (rc) return diag_fail(s, rc);
-    return diag_fail(s, bridge_posterior_from(&s.h, 1, G, mean, L, derived));
+    return with_arrays(device_id, N, d, G, chain, log_obj, [&](demcz_handle* h) { return bridge_posterior_from(h, 1, G, mean, L, derived); });
 }
 
 extern "C" int32_t demcz_bridge_proposal(demcz_handle* h, int64_t Np, int64_t wp, uint64_t seed, const double* mean, const double* L,
@@ -5674,13 +5642,12 @@ extern "C" int32_t demcz_bridge_proposal_program(int32_t device_id, int32_t d, i
     if (!logratio || !mean || !L) return DEMCZ_ERR_INVALID_ARGUMENT;
     int32_t rc = demcz_bridge_check(d, source, options);        // (compiled before a device is touched)
     if (rc) return rc;
-    ScratchHandle s;
-    rc = s.open(device_id, 1, d, 1, nullptr, nullptr);
-    if (rc) return diag_fail(s, rc);
-    BridgeTarget t;
-    rc = bridge_target_program(&s.h, d, source, options, data, ndata, "demcz_bridge_proposal_program", t);
-    if (rc) return diag_fail(s, rc);
-    return diag_fail(s, bridge_proposal_from(&s.h, d, t, Np, wp, seed, mean, L, logratio, draws));
+    // (no arrays: a 1 x d x 1 handle that only names the device and brings a stream)
+    return with_arrays(device_id, 1, d, 1, nullptr, nullptr, [&](demcz_handle* h) {
+        BridgeTarget t;
+        int32_t r2 = bridge_target_program(h, d, source, options, data, ndata, "demcz_bridge_proposal_program", t);
+        return r2 ? r2 : bridge_proposal_from(h, d, t, Np, wp, seed, mean, L, logratio, draws);
+    });
 }
 
 extern "C" int32_t demcz_bridge_iterate(demcz_handle* post, int64_t g_from, int64_t g_to, demcz_handle* prop, int64_t gp_from,
@@ -5727,14 +5694,12 @@ extern "C" int32_t demcz_bridge_array(int32_t device_id, const double* chain, co
     if (!chain || !log_obj) return DEMCZ_ERR_INVALID_ARGUMENT;
     int32_t rc = demcz_bridge_check(d, source, options);        // (compiled before anything is uploaded)
     if (rc) return rc;
-    ScratchHandle s;
-    rc = s.open(device_id, N, d, G, chain, log_obj);
-    if (rc) return diag_fail(s, rc);
-    BridgeTarget t;
-    rc = bridge_target_program(&s.h, d, source, options, data, ndata, "demcz_bridge_array", t);
-    if (rc) return diag_fail(s, rc);
     const BridgeOut o{logml, se_logml, iterations, converged, n_post, n_prop, neff_used, n_nan, ess_f2, mean_out, L_out};
-    return diag_fail(s, bridge_from(&s.h, t, 1, G, seed, neff, tol, max_iter, o));
+    return with_arrays(device_id, N, d, G, chain, log_obj, [&](demcz_handle* h) {
+        BridgeTarget t;
+        int32_t r2 = bridge_target_program(h, d, source, options, data, ndata, "demcz_bridge_array", t);
+        return r2 ? r2 : bridge_from(h, t, 1, G, seed, neff, tol, max_iter, o);
+    });
 }
 
 extern "C" int32_t demcz_get_info(const demcz_handle* h, int64_t* M, int64_t* launches_window, int32_t* lanes_per_chain)
