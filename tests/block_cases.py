@@ -158,10 +158,11 @@ def _seed(name):
     return 20261019 + sum((i + 1) * ord(c) for i, c in enumerate(name)) % 100000
 
 
-def _case(name, kind, d, blocks, N, gamma, pieces, env=(), temperature=None, k=K):
+def _case(name, kind, d, blocks, N, gamma, pieces, env=(), temperature=None, k=K, problem=None):
+    """(problem: a world of another shape than _problem's -- tests/full_update_cases.py: other observation counts)"""
     G = pieces[-1][1]
     return dict(name=name, kind=kind, d=d, blocks=[list(b) for b in blocks], N=N, K=k, seed=_seed(name), gamma=gamma, env=tuple(env),
-                problem=_problem(kind, d, N), pieces=pieces, G=G, temperature=temperatures(G, *HOT_COLD.get((kind, d), (10.0, 0.25))) if temperature is None else temperature)
+                problem=_problem(kind, d, N) if problem is None else problem, pieces=pieces, G=G, temperature=temperatures(G, *HOT_COLD.get((kind, d), (10.0, 0.25))) if temperature is None else temperature)
 
 
 def mlb_case(name):

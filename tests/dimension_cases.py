@@ -136,12 +136,14 @@ def lr_case(d, coop):
                 temperature=temperatures(G))
 
 
-def lr_kernel_name(d, coop):
+def lr_kernel_name(d, coop, lr16_fits=True):
     """What the library launches for the regression target on sixteen lanes per chain.  d = 10 has a kernel of its own while design
-    and observations fit LDS (window_kernel_lr16, the matrix instruction; about 1536 observations): the COOP case's 1381
-    observations run that one, and window_kernel_ml's helper-wave form is never chosen at d = 10; 1601 observations do not fit
-    and run window_kernel_ml<LINREG_SSE, 10, 16> like any other dimension."""
-    if d == 10 and coop:
+    and observations fit LDS (window_kernel_lr16, the matrix instruction; up to 1472 observations): the COOP case's 1381
+    observations run that one, and window_kernel_ml's helper-wave form is not chosen at d = 10 by any case here; 1601 observations
+    do not fit and run window_kernel_ml<LINREG_SSE, 10, 16> like any other dimension.  lr16_fits = False: a count that does not
+    fit window_kernel_lr16 -- from 1473 to ML_COOP_MAX_OBS observations that is the helper-wave form at d = 10 too
+    (tests/full_update_cases.py)."""
+    if d == 10 and coop and lr16_fits:
         return "demcz::window_kernel_lr16<10, false, false>"
     return "demcz::window_kernel_ml<LINREG_SSE, %d, 16%s>" % (d, ", false, false, true" if coop else "")
 

@@ -26,10 +26,11 @@ ROOT = Path(__file__).resolve().parent.parent
 L32 = "DEMCZ_MLB_L32"
 
 
-def engine_run(demc, case, lanes, history=True, resume_at=None, changed_from=1):
+def engine_run(demc, case, lanes, history=True, resume_at=None, changed_from=1, tail_from=None):
     """The library over the case's pieces on one handle: block_cases.oracle_run's dict (changed: the total), `names`, `launches`
     and `live` after every piece, `layout`.  resume_at: behind the piece that ends there the handle is given its own state back.
-    changed_from: the first generation of the changed_total asked for."""
+    changed_from: the first generation of the changed_total asked for.  tail_from: a function of the handle's LIVE status that
+    gives the first generation of a second total (`changed_tail`: tests/test_gpu_full_update_forms.py, the last launch's)."""
     w, N, d, G = case["problem"], case["N"], case["d"], case["G"]
     M0 = w["Zinit"].shape[0]
     e = demc.HipEngine(N=N, d=d, K=case["K"], Mcap=M0 + N * (G // case["K"] + 1), Gcap=G if history else 0, blockindex=case["blocks"],
@@ -49,8 +50,10 @@ def engine_run(demc, case, lanes, history=True, resume_at=None, changed_from=1):
         chain, lobj = e.get_history(1, G) if history else (None, None)
         X, lp, Z, M = e.get_state()
         total, from_ballots = e.changed_total(changed_from, G, with_source=True)
+        tail = e.changed_total(tail_from(live[-1][0]), G, with_source=True) if tail_from else (None, None)
         return dict(chain=chain, log_obj=lobj, X=np.array(X), logp=np.array(lp), Z=np.array(Z[:M]), M=M, changed=total,
-                    from_ballots=from_ballots, names=names, launches=launches, live=live, layout=layout)
+                    from_ballots=from_ballots, changed_tail=tail[0], tail_from_ballots=tail[1], names=names, launches=launches, live=live,
+                    layout=layout)
     finally:
         e.close()
 
