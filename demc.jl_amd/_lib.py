@@ -60,6 +60,8 @@ SYMBOLS = [
     "demcz_loo_columns", "demcz_loo_columns_array", "demcz_loo", "demcz_loo_array",
     "demcz_bridge_check", "demcz_bridge_posterior", "demcz_bridge_posterior_array", "demcz_bridge_proposal",
     "demcz_bridge_proposal_program", "demcz_bridge_iterate", "demcz_bridge", "demcz_bridge_array",
+    "demcz_histogram_edges", "demcz_histogram", "demcz_histogram_array", "demcz_histogram2d", "demcz_histogram2d_array",
+    "demcz_hdi_steps", "demcz_hdi", "demcz_hdi_array",
 ]
 
 
@@ -229,6 +231,15 @@ def load():
     L.demcz_indicator_le.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, _dp, C.POINTER(C.c_void_p)]
     L.demcz_rank_diagnostics.argtypes = [C.c_void_p, C.c_int64, C.c_int64, _dp, _dp, _dp]
     L.demcz_rank_diagnostics_array.argtypes = [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int64, _dp, _dp, _dp]
+    L.demcz_histogram_edges.argtypes = [C.c_int32, C.c_double, C.c_double, _dp]
+    L.demcz_histogram.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, _dp, _dp, _dp, _lp, _lp, _lp, _lp]
+    L.demcz_histogram_array.argtypes = [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int64, C.c_int32, _dp, _dp, _dp, _lp, _lp, _lp, _lp]
+    L.demcz_histogram2d.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, _ip, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _lp, _lp]
+    L.demcz_histogram2d_array.argtypes = [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int64, C.c_int32, _ip, C.c_int32, C.c_int32, _dp, _dp,
+                                          _dp, _dp, _lp, _lp]
+    L.demcz_hdi_steps.argtypes = [C.c_int64, C.c_int32, _dp, _lp]
+    L.demcz_hdi.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, _dp, _dp]
+    L.demcz_hdi_array.argtypes = [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int64, C.c_int32, _dp, _dp]
     _vpp = C.POINTER(C.c_void_p)
     L.demcz_pointwise_check.argtypes = [C.c_int32, C.c_char_p, C.c_char_p]
     L.demcz_pointwise.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_char_p, C.c_char_p, _dp, C.c_int64, _vpp]

@@ -8,6 +8,7 @@
 #include "demcz_kernels_sel.h"
 #include "demcz_select_host.h"
 #include "demcz_kernels_rank.h"
+#include "demcz_kernels_density.h"
 #include "demcz_kernels_loo.h"
 #include "demcz_kernels_bridge.h"
 #include "demcz_slab_plan.h"
@@ -30,6 +31,7 @@
 #include <thread>
 #include <cstdlib>
 #include <deque>
+#include <map>
 #include <mutex>
 #include <cfloat>
 #include <cmath>
@@ -4761,6 +4763,7 @@ struct RankScratch {
     int* info;                      // [RANK_DIGITS + 1][d]: per pass the source buffer of each parameter or -1; last row: where it ends
     unsigned int* dbase;            // [RANK_DIGITS][d][256]: keys of the parameter with a smaller digit in that pass
     double* center;
+    void* extra;                    // what the caller asked for besides (demcz_hdi: its partials and its result), 8-byte aligned
 };
 
 int32_t rank_refuse_sharded(demcz_handle* h, const char* who)
@@ -4771,7 +4774,7 @@ int32_t rank_refuse_sharded(demcz_handle* h, const char* who)
     return DEMCZ_OK;
 }
 
-// The keys-only sort of the d columns of a window, shared by demcz_rank_normalize and demcz_loo_columns: the scratch and the host
+// The keys-only sort of the d columns of a window, shared by demcz_rank_normalize, demcz_loo_columns and demcz_hdi: the scratch and the host
 // copies that have to live until the stream is synchronised.
 struct RankSort {
     RankScratch sc;
@@ -4784,16 +4787,16 @@ struct RankSort {
     std::vector<unsigned int> hbase;
 };
 
-// the scratch layout of a sort of d columns of S keys; freed with rs
-int32_t rank_sort_alloc(demcz_handle* h, int d, int64_t S, const char* who, RankSort& rs)
+// the scratch layout of a sort of d columns of S keys, and `extra` bytes behind it; freed with rs
+int32_t rank_sort_alloc(demcz_handle* h, int d, int64_t S, const char* who, RankSort& rs, size_t extra = 0)
 {
     RankScratch& sc = rs.sc;
     const int64_t ntiles = rs.ntiles = (S + RANK_TILE - 1) / RANK_TILE;
-    // [buf0 | buf1 | hist | nan | center | tcount | dbase | info], every piece a multiple of 8 bytes
+    // [buf0 | buf1 | hist | nan | center | tcount | dbase | info | extra], every piece a multiple of 8 bytes
     const size_t nkeys = (size_t)d * S, nhist = (size_t)d * RANK_DIGITS * 256, ntc = (size_t)d * ntiles * 256,
                  ninfo = (size_t)(RANK_DIGITS + 1) * d;
     const size_t bytes = 2 * nkeys * 8 + nhist * 8 + (size_t)d * 8 + (size_t)d * 8 + (ntc * 4 + 7) / 8 * 8 + nhist * 4 + (ninfo * 4 + 7) / 8 * 8;
-    const hipError_t e = sc.base.alloc(h->cfg.device_id, bytes);
+    const hipError_t e = sc.base.alloc(h->cfg.device_id, bytes + extra);
     if (e != hipSuccess)
         return fail(h, DEMCZ_ERR_HIP, std::string(who) + ": the sort's scratch (two key buffers of N w d words): " + hipGetErrorString(e));
     sc.buf0 = static_cast<uint64_t*>(sc.base.p);
@@ -4804,6 +4807,7 @@ int32_t rank_sort_alloc(demcz_handle* h, int d, int64_t S, const char* who, Rank
     sc.tcount = reinterpret_cast<unsigned int*>(sc.center + d);
     sc.dbase = reinterpret_cast<unsigned int*>(reinterpret_cast<char*>(sc.tcount) + (ntc * 4 + 7) / 8 * 8);
     sc.info = reinterpret_cast<int*>(sc.dbase + nhist);              // (nhist = d * 8 * 256 is even)
+    sc.extra = static_cast<char*>(sc.base.p) + bytes;
     rs.nhist = nhist;
     rs.ninfo = ninfo;
     rs.hhist.assign(nhist, 0ull);
@@ -5024,6 +5028,297 @@ extern "C" int32_t demcz_rank_diagnostics_array(int32_t device_id, const double*
     if (!chain || (!rhat_rank && !ess_bulk && !ess_tail)) return DEMCZ_ERR_INVALID_ARGUMENT;
     return with_arrays(device_id, N, d, G, chain, nullptr,
                        [&](demcz_handle* h) { return rank_diagnostics_from(h, 1, G, rhat_rank, ess_bulk, ess_tail); });
+}
+
+// ---- posterior densities (K13, demcz_kernels_density.h, demcz_density_host.h): histograms, pair grids, the HDI -------------------
+namespace {
+// The range of every parameter of a histogram: the caller's (finite, lo < hi, hi - lo finite), or with neither given the window's
+// smallest and largest draw, exact, by the select at probabilities 0 and 1; where the two are equal, (x - 0.5, x + 0.5).
+int32_t density_range(demcz_handle* h, int64_t g_from, int64_t g_to, const double* lo, const double* hi, const char* who,
+                      std::vector<double>& rlo, std::vector<double>& rhi)
+{
+    const int d = h->cfg.d;
+    rlo.resize((size_t)d);
+    rhi.resize((size_t)d);
+    if ((lo == nullptr) != (hi == nullptr)) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": give both lo and hi, or neither");
+    if (lo) {
+        for (int p = 0; p < d; ++p) {
+            if (!(lo[p] < hi[p]) || !std::isfinite(lo[p]) || !std::isfinite(hi[p]) || !std::isfinite(hi[p] - lo[p]))
+                return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": parameter " + std::to_string(p) +
+                                                           ": the range must be finite with lo < hi (and hi - lo finite)");
+            rlo[p] = lo[p];
+            rhi[p] = hi[p];
+        }
+        return DEMCZ_OK;
+    }
+    if (h->comm && h->nranks > 1)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": on a sharded handle give the range (the extremes over all ranks: "
+                                                   "demcz_select_counts added on the host), then add the counts over the ranks");
+    const double probs[2] = {0.0, 1.0};
+    std::vector<double> q((size_t)2 * d);
+    int32_t rc = demcz_quantiles(h, g_from, g_to, 2, probs, q.data(), nullptr, nullptr);
+    if (rc) return rc;
+    for (int p = 0; p < d; ++p) {
+        double a = q[p], b = q[(size_t)d + p];
+        if (!std::isfinite(a) || !std::isfinite(b) || !std::isfinite(b - a))
+            return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": parameter " + std::to_string(p) +
+                                                       " has a NaN or infinite draw in the window (or extremes further apart than a "
+                                                       "double holds): give a range");
+        if (a == b) { a = a - 0.5; b = b + 0.5; }
+        if (!(a < b))
+            return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": parameter " + std::to_string(p) +
+                                                       " is a constant too large for the range (x - 0.5, x + 0.5): give a range");
+        rlo[p] = a;
+        rhi[p] = b;
+    }
+    return DEMCZ_OK;
+}
+
+// the d edge tables of nb + 1 entries each, [p][k]
+int32_t density_tables(demcz_handle* h, int nb, const std::vector<double>& lo, const std::vector<double>& hi, const char* who,
+                       std::vector<double>& edges)
+{
+    const int d = h->cfg.d;
+    edges.resize((size_t)d * (nb + 1));
+    for (int p = 0; p < d; ++p)
+        if (demcz_histogram_edges(nb, lo[p], hi[p], edges.data() + (size_t)p * (nb + 1)))
+            return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": parameter " + std::to_string(p) + ": no edge table for its range");
+    return DEMCZ_OK;
+}
+
+// demcz_histogram on a source that holds an N x d x Gcap history (a sampling handle, a derived history, a ScratchHandle)
+int32_t histogram_from(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t nbins, const double* lo, const double* hi, double* edges,
+                       int64_t* counts, int64_t* below, int64_t* above, int64_t* nan_count)
+{
+    const char* who = "demcz_histogram";
+    if (nbins < 1 || nbins > DENSITY_MAX_BINS)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_histogram: 1 <= nbins <= 4096 (32-bit counters in 16 KB of LDS)");
+    int32_t rc = check_hist_range(h, g_from, g_to, who);
+    if (rc) return rc;
+    std::vector<double> rlo, rhi, he;
+    rc = density_range(h, g_from, g_to, lo, hi, who, rlo, rhi);
+    if (rc) return rc;
+    rc = density_tables(h, nbins, rlo, rhi, who, he);
+    if (rc) return rc;
+    const int d = h->cfg.d;
+    const int64_t ne = (int64_t)d * (nbins + 1), nc = (int64_t)d * (nbins + 3);
+    SelPlan s;
+    rc = sel_prepare(h, g_from, g_to, s, ne + nc, who);
+    if (rc) return rc;
+    static_assert(sizeof(unsigned long long) == sizeof(double), "scratch reuse");
+    double* de = h->d_scratch + s.off;
+    unsigned long long* dc = reinterpret_cast<unsigned long long*>(de + ne);
+    std::vector<uint64_t> hc((size_t)nc);
+    auto body = [&]() -> int32_t {
+        HIPCHK(h, hipMemcpyAsync(de, he.data(), (size_t)ne * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemsetAsync(dc, 0, (size_t)nc * sizeof(unsigned long long), h->stream));
+        hipLaunchKernelGGL(histogram_kernel, dim3((unsigned)(s.cb * s.d), (unsigned)s.nchunk), dim3(DEN_BS), 0, h->stream,
+                           (const double*)h->dchain, s.N, s.d, s.s0, s.w, s.cb, s.per, (int)nbins, (const double*)de, dc);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(hc.data(), dc, (size_t)nc * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+        return sync_stream(h, h->stream, who);
+    };
+    rc = body();
+    if (rc) { (void)hipStreamSynchronize(h->stream); return rc; }          // (copies into this call's vectors may be under way)
+    for (int p = 0; p < d; ++p) {
+        const uint64_t* c = hc.data() + (size_t)p * (nbins + 3);
+        for (int k = 0; k < nbins; ++k) counts[(size_t)p * nbins + k] = (int64_t)c[k];
+        if (below) below[p] = (int64_t)c[nbins];
+        if (above) above[p] = (int64_t)c[nbins + 1];
+        if (nan_count) nan_count[p] = (int64_t)c[nbins + 2];
+    }
+    if (edges) std::copy(he.begin(), he.end(), edges);
+    return DEMCZ_OK;
+}
+
+// demcz_histogram2d on such a source
+int32_t histogram2d_from(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t npairs, const int32_t* pairs, int32_t nbx, int32_t nby,
+                         const double* lo, const double* hi, double* edges_x, double* edges_y, int64_t* counts, int64_t* outside)
+{
+    const char* who = "demcz_histogram2d";
+    if (nbx < 1 || nby < 1 || nbx > DENSITY_MAX_SIDE || nby > DENSITY_MAX_SIDE)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_histogram2d: 1 <= nbx, nby <= 128 (the 32-bit counters of one pair in 64 KB of LDS)");
+    if (npairs < 1) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_histogram2d: npairs >= 1");
+    int32_t rc = check_hist_range(h, g_from, g_to, who);
+    if (rc) return rc;
+    const int d = h->cfg.d;
+    const int64_t ncell = (int64_t)nbx * nby;
+    // the distinct pairs, in order of first appearance; a repeated one is counted once and copied
+    std::map<std::pair<int32_t, int32_t>, int32_t> seen;
+    std::vector<int32_t> uniq, src((size_t)npairs);
+    for (int i = 0; i < npairs; ++i) {
+        const int32_t p = pairs[2 * i], q = pairs[2 * i + 1];
+        if (p < 0 || q < 0 || p >= d || q >= d || p == q)
+            return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_histogram2d: pair " + std::to_string(i) + ": need 0 <= p, q < d and p != q");
+        const auto at = seen.emplace(std::make_pair(p, q), (int32_t)(uniq.size() / 2));
+        if (at.second) { uniq.push_back(p); uniq.push_back(q); }
+        src[i] = at.first->second;
+    }
+    const int64_t nu = (int64_t)uniq.size() / 2;
+    if (nu * ncell > ((int64_t)1 << 27))
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_histogram2d: more than 2^27 cells in one call: ask for the pairs in several");
+    std::vector<double> rlo, rhi, hex, hey;
+    rc = density_range(h, g_from, g_to, lo, hi, who, rlo, rhi);
+    if (rc) return rc;
+    rc = density_tables(h, nbx, rlo, rhi, who, hex);
+    if (rc) return rc;
+    rc = density_tables(h, nby, rlo, rhi, who, hey);
+    if (rc) return rc;
+    DensityPlan plan;
+    if (density_plan(d, (int32_t)nu, uniq.data(), nbx, nby, plan)) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_histogram2d: no plan");
+    const int64_t ntiles = (int64_t)plan.tiles.size();
+    static_assert(sizeof(DensityTile) % 8 == 0, "tiles lie in 8-byte words of the scratch");
+    const int64_t nex = (int64_t)d * (nbx + 1), ney = (int64_t)d * (nby + 1), nc = nu * ncell,
+                  nt = ntiles * (int64_t)(sizeof(DensityTile) / 8);
+    SelPlan s;
+    rc = sel_prepare(h, g_from, g_to, s, nex + ney + nc + nt, who);
+    if (rc) return rc;
+    // chunks as sel_prepare's, for ntiles x cb groups of workgroups instead of d x cb
+    const int64_t groups = ntiles * s.cb;
+    if (groups > 0x7fffffffll) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_histogram2d: too many tiles for one launch");
+    int64_t nchunk = std::max<int64_t>(1, std::min<int64_t>((s.w + 15) / 16, (4096 + groups - 1) / groups));
+    nchunk = std::max<int64_t>(nchunk, (s.w + ((int64_t)1 << 20) - 1) >> 20);
+    const int64_t per = (s.w + nchunk - 1) / nchunk;
+    nchunk = (s.w + per - 1) / per;
+    int most = 1;
+    for (const DensityTile& T : plan.tiles) most = std::max(most, (int)T.npair);
+    const size_t lds = (size_t)most * ncell * sizeof(unsigned int);       // <= cap nbx nby counters = 64 KB
+    double* dex = h->d_scratch + s.off;
+    double* dey = dex + nex;
+    unsigned long long* dc = reinterpret_cast<unsigned long long*>(dey + ney);
+    DensityTile* dt = reinterpret_cast<DensityTile*>(dc + nc);
+    std::vector<uint64_t> hc((size_t)nc);
+    auto body = [&]() -> int32_t {
+        HIPCHK(h, hipMemcpyAsync(dex, hex.data(), (size_t)nex * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(dey, hey.data(), (size_t)ney * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(dt, plan.tiles.data(), (size_t)ntiles * sizeof(DensityTile), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemsetAsync(dc, 0, (size_t)nc * sizeof(unsigned long long), h->stream));
+        hipLaunchKernelGGL(histogram2d_kernel, dim3((unsigned)groups, (unsigned)nchunk), dim3(DEN_BS), lds, h->stream,
+                           (const double*)h->dchain, s.N, s.d, s.s0, s.w, s.cb, per, (int)nbx, (int)nby, (const double*)dex,
+                           (const double*)dey, (const DensityTile*)dt, dc);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(hc.data(), dc, (size_t)nc * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+        return sync_stream(h, h->stream, who);
+    };
+    rc = body();
+    if (rc) { (void)hipStreamSynchronize(h->stream); return rc; }          // (copies into this call's vectors may be under way)
+    // every draw of the window is in one cell of a pair or outside it: outside = S - the cells' total
+    const int64_t S = s.N * s.w;
+    for (int i = 0; i < npairs; ++i) {
+        const uint64_t* c = hc.data() + (size_t)src[i] * ncell;
+        int64_t in = 0;
+        for (int64_t k = 0; k < ncell; ++k) { counts[(size_t)i * ncell + k] = (int64_t)c[k]; in += (int64_t)c[k]; }
+        if (outside) outside[i] = S - in;
+    }
+    if (edges_x) std::copy(hex.begin(), hex.end(), edges_x);
+    if (edges_y) std::copy(hey.begin(), hey.end(), edges_y);
+    return DEMCZ_OK;
+}
+
+// demcz_hdi on such a source: the ranks' sort, then the arg-min over the sorted keys
+int32_t hdi_from(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t nprob, const double* probs, double* hdi)
+{
+    const char* who = "demcz_hdi";
+    if (h->comm && h->nranks > 1)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_hdi: the sort is of one handle's draws, and the interval needs those of every "
+                                                   "shard: gather the window with demcz_get_history on every rank and use demcz_hdi_array "
+                                                   "on the whole");
+    Window win;
+    int32_t rc = open_window(h, g_from, g_to, who, win);
+    if (rc) return rc;
+    HdiSteps steps = {};
+    int64_t m[DENSITY_MAX_PROBS] = {};
+    if (nprob < 1 || nprob > DENSITY_MAX_PROBS || demcz_hdi_steps(win.total, nprob, probs, m))
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_hdi: 1 to 16 probabilities, each inside (0, 1)");
+    for (int j = 0; j < nprob; ++j) steps.m[j] = (long long)m[j];
+    rc = enter_device(h);
+    if (rc) return rc;
+    const int64_t N = win.N, s0 = win.s0, S = win.total;
+    const int d = win.d;
+    if (S >= ((int64_t)1 << 31) || d > 65535)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_hdi: at most 2^31 - 1 draws per parameter and 65535 parameters");
+    rc = quiesce_all(h);                        // (the allocation below may synchronise the device)
+    if (rc) return rc;
+    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((S + 2047) / 2048, 1024));
+    const size_t npart = (size_t)d * nprob * nb, nout = (size_t)d * nprob * 2;
+    std::vector<double> hout(nout);
+    RankSort rs;                                // (behind hout: the scratch goes first)
+    rc = rank_sort_alloc(h, d, S, who, rs, npart * 16 + nout * 8);
+    if (rc) return rc;
+    auto body = [&]() -> int32_t {              // (HIPCHK returns from inside: one place where every such return is settled)
+        int32_t r2 = rank_sort_run(h, N, d, s0, S, nullptr, who, rs);
+        if (r2) return r2;
+        const RankScratch& sc = rs.sc;
+        static_assert(sizeof(long long) == sizeof(double), "partials");
+        double* pv = static_cast<double*>(sc.extra);
+        long long* pi = reinterpret_cast<long long*>(pv + npart);
+        double* dout = reinterpret_cast<double*>(pi + npart);
+        const int* where = sc.info + (size_t)RANK_DIGITS * d;
+        hipLaunchKernelGGL(hdi_partial_kernel, dim3((unsigned)nb, (unsigned)nprob, (unsigned)d), dim3(256), 0, h->stream,
+                           (const uint64_t*)sc.buf0, (const uint64_t*)sc.buf1, where, S, steps, pv, pi);
+        hipLaunchKernelGGL(hdi_final_kernel, dim3((unsigned)nprob, (unsigned)d), dim3(256), 0, h->stream, (const uint64_t*)sc.buf0,
+                           (const uint64_t*)sc.buf1, where, (const unsigned long long*)sc.nan, S, steps, (const double*)pv,
+                           (const long long*)pi, nb, dout);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(hout.data(), dout, nout * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        return sync_stream(h, h->stream, who);
+    };
+    rc = settle(body());
+    if (rc) return rc;
+    std::copy(hout.begin(), hout.end(), hdi);
+    return DEMCZ_OK;
+}
+}  // namespace
+
+extern "C" int32_t demcz_histogram(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t nbins, const double* lo, const double* hi,
+                                   double* edges, int64_t* counts, int64_t* below, int64_t* above, int64_t* nan_count)
+{
+    if (!h || !counts) return DEMCZ_ERR_INVALID_ARGUMENT;
+    DEADCHK(h);
+    return histogram_from(h, g_from, g_to, nbins, lo, hi, edges, counts, below, above, nan_count);
+}
+
+extern "C" int32_t demcz_histogram_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, int32_t nbins,
+                                         const double* lo, const double* hi, double* edges, int64_t* counts, int64_t* below,
+                                         int64_t* above, int64_t* nan_count)
+{
+    if (!chain || !counts) return DEMCZ_ERR_INVALID_ARGUMENT;
+    return with_arrays(device_id, N, d, G, chain, nullptr, [&](demcz_handle* h) {
+        return histogram_from(h, 1, G, nbins, lo, hi, edges, counts, below, above, nan_count);
+    });
+}
+
+extern "C" int32_t demcz_histogram2d(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t npairs, const int32_t* pairs, int32_t nbx,
+                                     int32_t nby, const double* lo, const double* hi, double* edges_x, double* edges_y,
+                                     int64_t* counts, int64_t* outside)
+{
+    if (!h || !pairs || !counts) return DEMCZ_ERR_INVALID_ARGUMENT;
+    DEADCHK(h);
+    return histogram2d_from(h, g_from, g_to, npairs, pairs, nbx, nby, lo, hi, edges_x, edges_y, counts, outside);
+}
+
+extern "C" int32_t demcz_histogram2d_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, int32_t npairs,
+                                           const int32_t* pairs, int32_t nbx, int32_t nby, const double* lo, const double* hi,
+                                           double* edges_x, double* edges_y, int64_t* counts, int64_t* outside)
+{
+    if (!chain || !pairs || !counts) return DEMCZ_ERR_INVALID_ARGUMENT;
+    return with_arrays(device_id, N, d, G, chain, nullptr, [&](demcz_handle* h) {
+        return histogram2d_from(h, 1, G, npairs, pairs, nbx, nby, lo, hi, edges_x, edges_y, counts, outside);
+    });
+}
+
+extern "C" int32_t demcz_hdi(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t nprob, const double* probs, double* hdi)
+{
+    if (!h || !probs || !hdi) return DEMCZ_ERR_INVALID_ARGUMENT;
+    DEADCHK(h);
+    return hdi_from(h, g_from, g_to, nprob, probs, hdi);
+}
+
+extern "C" int32_t demcz_hdi_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, int32_t nprob,
+                                   const double* probs, double* hdi)
+{
+    if (!chain || !probs || !hdi) return DEMCZ_ERR_INVALID_ARGUMENT;
+    return with_arrays(device_id, N, d, G, chain, nullptr, [&](demcz_handle* h) { return hdi_from(h, 1, G, nprob, probs, hdi); });
 }
 
 // ---- PSIS-LOO and WAIC (demcz_kernels_pointwise.h, K11 demcz_kernels_loo.h, demcz_loo_host.h) -----------------------------------

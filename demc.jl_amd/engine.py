@@ -45,6 +45,97 @@ Best = namedtuple("Best", "bestval chain generation bestpar")
 RankDiagnostics = namedtuple("RankDiagnostics", "rhat_rank ess_bulk ess_tail")
 
 
+class Histogram(namedtuple("Histogram", "counts edges below above nan")):
+    """Marginal histograms (demcz_histogram): counts d x nbins int64, edges d x (nbins + 1), and per parameter the draws below the
+    range, above it, and NaN.  Bin k holds edges[k] <= x < edges[k+1]; the last bin also holds x == edges[nbins]."""
+    __slots__ = ()
+
+    @property
+    def density(self):
+        """counts / (in-range total * bin width): integrates to one over the range (NaN for a parameter with no draw in range)."""
+        with np.errstate(all="ignore"):
+            return self.counts / (self.counts.sum(axis=1, keepdims=True) * np.diff(self.edges, axis=1))
+
+    def mode(self):
+        """The centre of the fullest bin of every parameter, the lowest on ties."""
+        k = np.argmax(self.counts, axis=1)
+        p = np.arange(self.counts.shape[0])
+        return 0.5 * (self.edges[p, k] + self.edges[p, k + 1])
+
+    def hdi(self, prob):
+        """The multimodal highest-density region from the bins (host code): bins are taken in order of falling count, among
+        equals in order of rising index, until their share of the in-range draws reaches ``prob``; the result is the union of
+        adjacent taken bins: per parameter a list of (lo, hi) intervals (empty with no draw in range)."""
+        prob = float(prob)
+        if not 0.0 < prob < 1.0:
+            raise ValueError("prob must lie inside (0, 1)")
+        out = []
+        for c, e in zip(self.counts, self.edges):
+            total = int(c.sum())
+            if total == 0:
+                out.append([])
+                continue
+            order = np.argsort(-c, kind="stable")
+            ntake = int(np.searchsorted(np.cumsum(c[order]), prob * total, side="left")) + 1
+            taken = np.sort(order[:min(ntake, c.size)])
+            cuts = np.flatnonzero(np.diff(taken) > 1)
+            first = np.concatenate([[0], cuts + 1])
+            last = np.concatenate([cuts, [taken.size - 1]])
+            out.append([(float(e[taken[a]]), float(e[taken[b] + 1])) for a, b in zip(first, last)])
+        return out
+
+
+# pairwise histograms (demcz_histogram2d): counts npairs x nbx x nby int64, pairs npairs x 2, edges = (edges_x d x (nbx + 1),
+# edges_y d x (nby + 1)): pair (p, q) is binned by edges_x[p] and edges_y[q]; outside: draws with a coordinate out of range or NaN
+Histogram2D = namedtuple("Histogram2D", "counts pairs edges outside")
+
+
+def histogram_edges(nbins, lo, hi):
+    """demcz_histogram_edges (host code, no device): the table np.linspace(lo, hi, nbins + 1) of one parameter, as the library
+    forms it."""
+    out = np.empty(int(nbins) + 1 if nbins >= 1 else 1)
+    rc = _lib.load().demcz_histogram_edges(int(nbins), float(lo), float(hi), _lib.ptr(out))
+    if rc != 0:
+        raise DemczError(rc, "demcz_histogram_edges: 1 <= nbins <= 4096 and lo < hi, both finite, hi - lo finite")
+    return out
+
+
+def hdi_steps(S, probs):
+    """demcz_hdi_steps (host code, no device): min(floor(prob S), S - 1) per probability."""
+    probs = np.ascontiguousarray(np.atleast_1d(probs), dtype=np.float64)
+    out = np.zeros(probs.size, dtype=np.int64)
+    rc = _lib.load().demcz_hdi_steps(int(S), probs.size, _lib.ptr(probs), _lib.ptr(out, _lib._lp))
+    if rc != 0:
+        raise DemczError(rc, "demcz_hdi_steps: S >= 1 and 1 to 16 probabilities inside (0, 1)")
+    return out
+
+
+def _range_args(rng, d):
+    """(lo, hi) as two contiguous d-vectors, or (None, None): ``rng`` is None, one (lo, hi) for every parameter, or d x 2."""
+    if rng is None:
+        return None, None
+    r = np.asarray(rng, dtype=np.float64)
+    if r.shape == (2,):
+        r = np.broadcast_to(r, (d, 2))
+    if r.shape != (d, 2):
+        raise ValueError("range must be (lo, hi) or d x 2")
+    return np.ascontiguousarray(r[:, 0]), np.ascontiguousarray(r[:, 1])
+
+
+def _pairs_arg(pairs, d):
+    if pairs is None:
+        pairs = [(p, q) for p in range(d) for q in range(p + 1, d)]
+    pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    if pr.shape[0] < 1:
+        raise ValueError("at least one pair (d >= 2)")
+    return pr
+
+
+def _bins2(bins):
+    nbx, nby = (bins, bins) if np.ndim(bins) == 0 else bins
+    return int(nbx), int(nby)
+
+
 # PSIS-LOO and WAIC (demcz_loo, demcz_loo_columns).  Per observation: elpd_loo_i, pareto_k, n_tail, lppd_i, p_waic_i,
 # p_loo_i = lppd_i - elpd_loo_i and elpd_waic_i = lppd_i - p_waic_i; the totals elpd_loo, p_loo, elpd_waic, p_waic; se_elpd_loo and
 # se_elpd_waic = sqrt(nobs var(pointwise, divisor nobs - 1)); k_threshold = min(1 - 1 / log10(S), 0.7) of the S draws; bad_k: the
@@ -444,11 +535,50 @@ class _HistoryStatistics:
                                                  _lib.ptr(out.ess_tail)))
         return out
 
+    def histogram(self, g_from, g_to, bins=33, range=None):
+        """Marginal histograms of every parameter over generations g_from..g_to (demcz_histogram): a ``Histogram``.  ``bins``: 1 to
+        4096 uniform bins; ``range``: (lo, hi) for every parameter, d x 2, or None: the window's smallest and largest draw of each
+        parameter (a parameter with a NaN or infinite draw then needs a range).  The counts are np.histogram's."""
+        d, nb = self.d, int(bins)
+        lo, hi = _range_args(range, d)
+        out = Histogram(np.zeros((d, max(nb, 0)), dtype=np.int64), np.empty((d, max(nb, 0) + 1)), np.zeros(d, dtype=np.int64),
+                        np.zeros(d, dtype=np.int64), np.zeros(d, dtype=np.int64))
+        self._chk(self._L.demcz_histogram(self._h, int(g_from), int(g_to), nb, _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(out.edges),
+                                          _lib.ptr(out.counts, _lib._lp), _lib.ptr(out.below, _lib._lp), _lib.ptr(out.above, _lib._lp),
+                                          _lib.ptr(out.nan, _lib._lp)))
+        return out
+
+    def histogram2d(self, g_from, g_to, pairs=None, bins=32, range=None):
+        """Pairwise histograms over generations g_from..g_to (demcz_histogram2d): a ``Histogram2D``.  ``pairs``: (p, q) pairs with
+        p != q (default: all p < q); ``bins``: one number or (nbx, nby), each 1 to 128; ``range`` as for ``histogram``.  The counts
+        of pair (p, q) are np.histogram2d(x_p, x_q, bins=[edges_x[p], edges_y[q]])'s."""
+        d = self.d
+        nbx, nby = _bins2(bins)
+        pr = _pairs_arg(pairs, d)
+        lo, hi = _range_args(range, d)
+        npairs = pr.shape[0]
+        counts = np.zeros((npairs, max(nbx, 0), max(nby, 0)), dtype=np.int64)
+        ex, ey = np.empty((d, max(nbx, 0) + 1)), np.empty((d, max(nby, 0) + 1))
+        outside = np.zeros(npairs, dtype=np.int64)
+        self._chk(self._L.demcz_histogram2d(self._h, int(g_from), int(g_to), npairs, _lib.ptr(pr, _lib._ip), nbx, nby, _lib.ptr(lo),
+                                            _lib.ptr(hi), _lib.ptr(ex), _lib.ptr(ey), _lib.ptr(counts, _lib._lp),
+                                            _lib.ptr(outside, _lib._lp)))
+        return Histogram2D(counts, pr, (ex, ey), outside)
+
+    def hdi(self, g_from, g_to, prob=0.94):
+        """The highest-density interval of every parameter over generations g_from..g_to (demcz_hdi): the shortest interval between
+        two order statistics that spans floor(prob S) steps among the S sorted draws (ArviZ's unimodal hdi).  d x 2, or
+        d x nprob x 2 for several probabilities (up to 16).  ``Histogram.hdi`` has the multimodal one."""
+        probs = np.ascontiguousarray(np.atleast_1d(prob), dtype=np.float64)
+        out = np.empty((self.d, probs.size, 2))
+        self._chk(self._L.demcz_hdi(self._h, int(g_from), int(g_to), probs.size, _lib.ptr(probs), _lib.ptr(out)))
+        return out[:, 0, :] if np.ndim(prob) == 0 else out
+
 
 class DerivedHistory(_HistoryStatistics):
     """An N x m x w history of derived quantities on the device (``demcz_derive``): generations ``g_from..g_to``, numbered as in
     the history it came from.  ``rhat``, ``rhat_partial``, ``autocov_sums``, ``ess``, ``select_counts``, ``quantiles``, ``mean_cov``,
-    ``derive``, ``rank_normalize``, ``indicator_le``, ``rank_diagnostics``, ``pointwise``, ``loo_columns`` and ``loo`` are ``HipEngine``'s; nothing else of an engine applies (the library answers ERR_STATE)."""
+    ``derive``, ``rank_normalize``, ``indicator_le``, ``rank_diagnostics``, ``histogram``, ``histogram2d``, ``hdi``, ``pointwise``, ``loo_columns`` and ``loo`` are ``HipEngine``'s; nothing else of an engine applies (the library answers ERR_STATE)."""
 
     def __init__(self, L, handle, N, m, g_from, g_to, names=None, chain_id0=0):
         self._L, self._h = L, handle
@@ -490,10 +620,10 @@ class DerivedHistory(_HistoryStatistics):
         self._chk(self._L.demcz_get_history(self._h, g_from, g_to, _lib.ptr(out), None))
         return out
 
-    def summary(self, probs=None, rank_normalized=False):
+    def summary(self, probs=None, rank_normalized=False, hdi_prob=None):
         """What ``posterior_summary`` returns for a host array (mean, sd, mcse, ess, rhat, converged and, with ``probs``,
-        quantiles; with ``rank_normalized``, rhat_rank, ess_bulk and ess_tail), computed from the handle with no download, plus
-        ``names``."""
+        quantiles; with ``rank_normalized``, rhat_rank, ess_bulk and ess_tail; with ``hdi_prob``, hdi), computed from the handle
+        with no download, plus ``names``."""
         mean, _ = self.mean_cov(self.g_from, self.g_to)
         e = self.ess(self.g_from, self.g_to)
         with np.errstate(all="ignore"):
@@ -503,6 +633,8 @@ class DerivedHistory(_HistoryStatistics):
             out["quantiles"] = self.quantiles(self.g_from, self.g_to, probs)
         if rank_normalized:
             out.update(self.rank_diagnostics(self.g_from, self.g_to)._asdict())
+        if hdi_prob is not None:
+            out["hdi"] = self.hdi(self.g_from, self.g_to, hdi_prob)
         out["names"] = self.names
         return out
 

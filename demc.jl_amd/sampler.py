@@ -296,6 +296,71 @@ class _Runner:
         out = select_quantiles(count_pass, self.N_total * (g_to - g_from + 1), self.d, probs)
         return out if with_order_stats else out.q
 
+    def _window_range(self, g_from, g_to, range):
+        """d x 2: the given range, or the smallest and largest draw of every parameter over ALL shards (``quantiles`` at 0 and 1,
+        exact), widened to (x - 0.5, x + 0.5) where the two are equal, as demcz_histogram's automatic range."""
+        if range is not None:
+            return range
+        q = np.array(self.quantiles(g_from, g_to, [0.0, 1.0]))
+        bad = np.flatnonzero(~np.isfinite(q).all(axis=1))
+        if bad.size:
+            raise ValueError(f"parameter {int(bad[0])} has a NaN or infinite draw in the window: give a range")
+        same = q[:, 0] == q[:, 1]
+        q[same, 0] -= 0.5
+        q[same, 1] += 0.5
+        return q
+
+    def _sum_counts(self, arrays):
+        """int64 arrays added over this process's engines and, under a host-exchange sharding, over the processes (counts stay
+        below 2^53: exact as doubles)."""
+        out = [sum(parts) for parts in zip(*arrays)]
+        if self.sh is not None and self.sh.world_size > 1:
+            flat = np.concatenate([a.ravel() for a in out]).astype(np.float64)
+            flat = self.sh.all_reduce_sum(np.ascontiguousarray(flat)).astype(np.int64)
+            at, res = 0, []
+            for a in out:
+                res.append(flat[at:at + a.size].reshape(a.shape))
+                at += a.size
+            out = res
+        return out
+
+    def histogram(self, g_from, g_to, bins=33, range=None):
+        """Marginal histograms over all N_total chains (an engine.Histogram).  One engine: demcz_histogram.  Several shards: with
+        no range given the extremes are taken over the shards first (``quantiles``); every shard then counts under the same edge
+        tables, and the counts, integers, are added on the host."""
+        if self.lib_exchange:
+            raise NotImplementedError("histogram over a communicator of several ranks: give every rank the same range and add "
+                                      "the counts of engine.histogram over the ranks on the host")
+        if not self.host_exchange and len(self.engines) == 1:
+            return self.engines[0].histogram(g_from, g_to, bins, range)
+        from .engine import Histogram
+        rng = self._window_range(g_from, g_to, range)
+        parts = [e.histogram(g_from, g_to, bins, rng) for e in self.engines]
+        counts, below, above, nan = self._sum_counts([(h.counts, h.below, h.above, h.nan) for h in parts])
+        return Histogram(counts, parts[0].edges, below, above, nan)
+
+    def histogram2d(self, g_from, g_to, pairs=None, bins=32, range=None):
+        """Pairwise histograms over all N_total chains (an engine.Histogram2D); shards as in ``histogram``."""
+        if self.lib_exchange:
+            raise NotImplementedError("histogram2d over a communicator of several ranks: give every rank the same range and add "
+                                      "the counts of engine.histogram2d over the ranks on the host")
+        if not self.host_exchange and len(self.engines) == 1:
+            return self.engines[0].histogram2d(g_from, g_to, pairs, bins, range)
+        from .engine import Histogram2D
+        rng = self._window_range(g_from, g_to, range)
+        parts = [e.histogram2d(g_from, g_to, pairs, bins, rng) for e in self.engines]
+        counts, outside = self._sum_counts([(h.counts, h.outside) for h in parts])
+        return Histogram2D(counts, parts[0].pairs, parts[0].edges, outside)
+
+    def hdi(self, g_from, g_to, prob=0.94):
+        """The highest-density interval (``HipEngine.hdi``).  One engine only: the sort behind it is of one handle's draws, and an
+        interval over host shards is not provided -- gather the window (``history()``) and use ``demc.hdi_chain`` on the whole, or
+        take the multimodal ``histogram(...).hdi(prob)``, whose counts do add over shards."""
+        if self.lib_exchange or self.host_exchange or len(self.engines) != 1:
+            raise NotImplementedError("hdi over several shards: gather the window's chain (history()) and use demc.hdi_chain on "
+                                      "the whole, or use histogram(...).hdi(prob)")
+        return self.engines[0].hdi(g_from, g_to, prob)
+
     def best(self, g_from, g_to):
         """The best draw over all N_total chains (an engine.Best tuple with the GLOBAL 0-based chain): the maximum over the engines,
         ties to the earliest generation, then to the lowest chain."""

@@ -7,7 +7,9 @@ kernels the autostop uses.  ``flatten_chain`` is a pure re-indexing (utils.jl:22
 SURVEY.md Q16).
 Beyond the reference: ``ess_chain``, ``autocov_chain``, ``quantile_chain`` and ``posterior_summary`` (effective sample size and
 quantiles by exact selection), ``derive_chain`` (functions of the draws, evaluated on the device), and
-``rank_normalize_chain`` / ``rank_diagnostics_chain`` (exact ranks on the device: rank-normalised R-hat, bulk- and tail-ESS).
+``rank_normalize_chain`` / ``rank_diagnostics_chain`` (exact ranks on the device: rank-normalised R-hat, bulk- and tail-ESS),
+``histogram_chain`` / ``histogram2d_chain`` / ``hdi_chain`` (the counts behind a marginal density and a corner plot, and the
+highest-density interval; the drawing itself stays out of scope).
 Checkpoints: the reference only resumes in memory (``prevrun=``); ``save_checkpoint`` /
 ``load_checkpoint`` put the same information in one ``.npz`` file.
 """
@@ -159,11 +161,58 @@ def rank_diagnostics_chain(chain, device_id=0):
     return out
 
 
-def posterior_summary(chain, device_id=0, probs=None, rank_normalized=False):
+def histogram_chain(chain, bins=33, range=None, device_id=0):
+    """Marginal histograms of every parameter of an Npop x Npar x Ngeneration history over all its draws (demcz_histogram_array): a
+    ``Histogram`` with np.histogram's counts.  ``range``: (lo, hi), Npar x 2, or None (the smallest and largest draw of each
+    parameter).  Not in the reference beyond the 33-bin histogram its convergence_check once drew."""
+    from .engine import Histogram, _range_args
+    chain = _lib.f64(chain, "F")
+    N, d, G = chain.shape
+    nb = int(bins)
+    lo, hi = _range_args(range, d)
+    out = Histogram(np.zeros((d, max(nb, 0)), dtype=np.int64), np.empty((d, max(nb, 0) + 1)), np.zeros(d, dtype=np.int64),
+                    np.zeros(d, dtype=np.int64), np.zeros(d, dtype=np.int64))
+    _chk(_lib.load().demcz_histogram_array(device_id, _lib.ptr(chain), N, d, G, nb, _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(out.edges),
+                                           _lib.ptr(out.counts, _lib._lp), _lib.ptr(out.below, _lib._lp), _lib.ptr(out.above, _lib._lp),
+                                           _lib.ptr(out.nan, _lib._lp)))
+    return out
+
+
+def histogram2d_chain(chain, pairs=None, bins=32, range=None, device_id=0):
+    """Pairwise histograms of an Npop x Npar x Ngeneration history (demcz_histogram2d_array): a ``Histogram2D`` with
+    np.histogram2d's counts for every pair (default: all p < q).  ``bins``: one number or (nbx, nby), each 1 to 128."""
+    from .engine import Histogram2D, _bins2, _pairs_arg, _range_args
+    chain = _lib.f64(chain, "F")
+    N, d, G = chain.shape
+    nbx, nby = _bins2(bins)
+    pr = _pairs_arg(pairs, d)
+    lo, hi = _range_args(range, d)
+    npairs = pr.shape[0]
+    counts = np.zeros((npairs, max(nbx, 0), max(nby, 0)), dtype=np.int64)
+    ex, ey = np.empty((d, max(nbx, 0) + 1)), np.empty((d, max(nby, 0) + 1))
+    outside = np.zeros(npairs, dtype=np.int64)
+    _chk(_lib.load().demcz_histogram2d_array(device_id, _lib.ptr(chain), N, d, G, npairs, _lib.ptr(pr, _lib._ip), nbx, nby, _lib.ptr(lo),
+                                             _lib.ptr(hi), _lib.ptr(ex), _lib.ptr(ey), _lib.ptr(counts, _lib._lp),
+                                             _lib.ptr(outside, _lib._lp)))
+    return Histogram2D(counts, pr, (ex, ey), outside)
+
+
+def hdi_chain(chain, prob=0.94, device_id=0):
+    """The highest-density interval of every parameter of an Npop x Npar x Ngeneration history (demcz_hdi_array; ArviZ's unimodal
+    hdi): Npar x 2, or Npar x nprob x 2 for several probabilities.  A parameter that holds a NaN is NaN."""
+    chain = _lib.f64(chain, "F")
+    N, d, G = chain.shape
+    probs = np.ascontiguousarray(np.atleast_1d(prob), dtype=np.float64)
+    out = np.empty((d, probs.size, 2))
+    _chk(_lib.load().demcz_hdi_array(device_id, _lib.ptr(chain), N, d, G, probs.size, _lib.ptr(probs), _lib.ptr(out)))
+    return out[:, 0, :] if np.ndim(prob) == 0 else out
+
+
+def posterior_summary(chain, device_id=0, probs=None, rank_normalized=False, hdi_prob=None):
     """Per parameter: mean, sd = sqrt(var+), mcse = sqrt(var+ / ess), ess, rhat, converged (of the ESS: 0 where the lags ran out
     and ess is an upper bound) -- mean_cov_chain, Rhat_gelman and ess_chain, all reduced on the device.  With `probs`, also
     quantiles = quantile_chain(chain, probs): Npar x len(probs).  With `rank_normalized`, also rhat_rank, ess_bulk and ess_tail
-    (rank_diagnostics_chain)."""
+    (rank_diagnostics_chain).  With `hdi_prob`, also hdi = hdi_chain(chain, hdi_prob)."""
     mean, _ = mean_cov_chain(chain, device_id=device_id)
     e = ess_chain(chain, device_id=device_id)
     with np.errstate(all="ignore"):
@@ -173,6 +222,8 @@ def posterior_summary(chain, device_id=0, probs=None, rank_normalized=False):
         out["quantiles"] = quantile_chain(chain, probs, device_id=device_id)
     if rank_normalized:
         out.update(rank_diagnostics_chain(chain, device_id=device_id)._asdict())
+    if hdi_prob is not None:
+        out["hdi"] = hdi_chain(chain, hdi_prob, device_id=device_id)
     return out
 
 

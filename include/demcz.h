@@ -493,7 +493,7 @@ int32_t demcz_best_array(int32_t device_id, const double* log_obj, int64_t N, in
  * freed by demcz_destroy.  It takes demcz_rhat, demcz_rhat_partial, demcz_autocov_sums, demcz_ess, demcz_select_counts,
  * demcz_quantiles, demcz_mean_cov, demcz_get_history with log_obj = NULL, demcz_synchronize, demcz_last_error, demcz_destroy,
  * demcz_derive (a derived history of a derived history; its logp is NaN) and demcz_rank_normalize, demcz_indicator_le,
- * demcz_rank_diagnostics, demcz_pointwise, demcz_loo_columns, demcz_loo and (a one-column one, as either argument)
+ * demcz_rank_diagnostics, demcz_histogram, demcz_histogram2d, demcz_hdi, demcz_pointwise, demcz_loo_columns, demcz_loo and (a one-column one, as either argument)
  * demcz_bridge_iterate (below).  Every other call that takes a handle returns
  * DEMCZ_ERR_STATE on it, with a message that says so. */
 int32_t demcz_derive_check(int32_t d, int32_t m, const char* source, const char* options);
@@ -542,6 +542,61 @@ int32_t demcz_rank_diagnostics(demcz_handle* h, int64_t g_from, int64_t g_to,
                                double* rhat_rank, double* ess_bulk, double* ess_tail);
 int32_t demcz_rank_diagnostics_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G,
                                      double* rhat_rank, double* ess_bulk, double* ess_tail);
+
+/* Posterior densities (not in the reference beyond the 33-bin histogram its convergence_check once drew): marginal histograms,
+ * pairwise histograms and highest-density intervals over generations g_from..g_to of the history on the device (DESIGN.md
+ * sections 3 and 4.18).  Counts are integers: exact, bit-reproducible, additive over shards in any order.
+ *
+ * THE BIN RULE.  Parameter p has nbins uniform bins over [lo[p], hi[p]] with the edge table
+ *     edges[p][k] = numpy.linspace(lo[p], hi[p], nbins + 1)[k]:   k * ((hi - lo) / nbins) + lo, two rounded operations after the
+ *     division (should (hi - lo) / nbins underflow to 0: (k / nbins) * (hi - lo) + lo), and edges[p][nbins] = hi exactly.
+ * A draw x lies in bin k iff edges[k] <= x < edges[k+1]; the last bin also takes x == edges[nbins].  x < edges[0] (-inf too)
+ * counts in below[p], x > edges[nbins] (+inf too) in above[p], a NaN in nan_count[p].  -0.0 compares as 0.0.  The table decides,
+ * not the rounding of any estimate: the counts are numpy.histogram(x, bins = nbins, range = (lo, hi))'s.
+ *   demcz_histogram_edges  host code, no device: the table of one parameter, nbins + 1 values.  INVALID_ARGUMENT unless
+ *                          1 <= nbins <= 4096 and lo < hi, both finite, hi - lo finite -- and unless the table comes out
+ *                          non-decreasing, which it does between normal doubles (a span of a few thousand subnormals can fail).
+ *   demcz_histogram        counts: d x nbins, [p][k] (row-major); edges: d x (nbins + 1), [p][k], the tables used (may be NULL);
+ *                          below, above, nan_count: d values each (any may be NULL).  lo, hi: d values each, or both NULL: the
+ *                          AUTOMATIC RANGE, the window's smallest and largest draw of the parameter (exact: demcz_quantiles at
+ *                          probabilities 0 and 1); where the two are equal, (x - 0.5, x + 0.5).  A parameter whose extreme is NaN
+ *                          or infinite: INVALID_ARGUMENT, the message names the parameter -- give a range.  A given range must be
+ *                          finite with lo < hi for every parameter.  On a handle whose communicator has more than one rank the
+ *                          counts are those of the handle's own chains: give the range, and add the counts over the ranks.
+ *   demcz_histogram2d      npairs pairs (p, q) = (pairs[2 i], pairs[2 i + 1]), p != q, both in 0..d-1; p's draws go by its table
+ *                          of nbx bins, q's by its table of nby bins, both over the parameter's range [lo, hi] (d values each, or
+ *                          both NULL as above).  counts: npairs x nbx x nby, [i][kx][ky]; a draw with either coordinate outside
+ *                          its range, or NaN, counts in outside[i] (may be NULL) and in no cell:
+ *                          numpy.histogram2d(x_p, x_q, bins = [edges_x[p], edges_y[q]]).  1 <= nbx, nby <= 128: the 32-bit counters
+ *                          of one pair are then at most the 64 KB of LDS a workgroup may have.  edges_x: d x (nbx + 1), edges_y:
+ *                          d x (nby + 1) (may be NULL).  At most 2^27 cells in one call.
+ *   demcz_hdi_steps        host code, no device: steps[j] = min(floor(probs[j] S), S - 1) for 1 to 16 probabilities inside (0, 1).
+ *   demcz_hdi              the shortest interval between two order statistics that spans m = demcz_hdi_steps steps: with s the
+ *                          window's S = N w draws of the parameter in ascending order (-0.0 taken as 0.0),
+ *                          i* = argmin over 0 <= i < S - m of s[i + m] - s[i], one rounded subtraction each; ties go to the
+ *                          smallest i; a NaN width (inf - inf) is never a candidate.  hdi: d x nprob x 2, [p][j][0] = s[i*],
+ *                          [p][j][1] = s[i* + m]; NaN, NaN without a candidate, and for a parameter with a NaN draw in the window.
+ *                          The sort is demcz_rank_normalize's, in 2 S d words of device memory returned before the call ends; at
+ *                          most 2^31 - 1 draws per parameter.  On a handle whose communicator has more than one rank:
+ *                          INVALID_ARGUMENT -- the sort is of one handle's draws; gather the window and use demcz_hdi_array.
+ *   ..._array              the same from a host array N x d x G column-major, generations 1..G.
+ * Range and state errors are demcz_rhat's; h may be a derived history. */
+int32_t demcz_histogram_edges(int32_t nbins, double lo, double hi, double* edges);
+int32_t demcz_histogram(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t nbins, const double* lo, const double* hi,
+                        double* edges, int64_t* counts, int64_t* below, int64_t* above, int64_t* nan_count);
+int32_t demcz_histogram_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, int32_t nbins,
+                              const double* lo, const double* hi, double* edges, int64_t* counts, int64_t* below,
+                              int64_t* above, int64_t* nan_count);
+int32_t demcz_histogram2d(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t npairs, const int32_t* pairs, int32_t nbx,
+                          int32_t nby, const double* lo, const double* hi, double* edges_x, double* edges_y,
+                          int64_t* counts, int64_t* outside);
+int32_t demcz_histogram2d_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, int32_t npairs,
+                                const int32_t* pairs, int32_t nbx, int32_t nby, const double* lo, const double* hi,
+                                double* edges_x, double* edges_y, int64_t* counts, int64_t* outside);
+int32_t demcz_hdi_steps(int64_t S, int32_t nprob, const double* probs, int64_t* steps);
+int32_t demcz_hdi(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t nprob, const double* probs, double* hdi);
+int32_t demcz_hdi_array(int32_t device_id, const double* chain, int64_t N, int32_t d, int64_t G, int32_t nprob,
+                        const double* probs, double* hdi);
 
 /* PSIS-LOO and WAIC (Vehtari, Gelman & Gabry 2017; Vehtari, Simpson, Gelman, Yao & Gabry 2024; the generalised-Pareto fit of
  * Zhang & Stephens 2009; not in the reference): how well the model predicts each observation it was fitted to, from the history

@@ -501,6 +501,40 @@ function rank_diagnostics_chain(chain::Array{Float64,3}; device_id=0)
     (rhat_rank=r, ess_bulk=eb, ess_tail=et)
 end
 
+# ---- posterior densities (include/demcz.h: demcz_histogram, demcz_histogram2d, demcz_hdi; not in the reference) ---------------
+# The library's arrays are row-major per parameter; as Julia arrays the parameter is the LAST index: counts[k, p], edges[k, p].
+# Bin k of parameter p holds edges[k, p] <= x < edges[k + 1, p], the last bin also x == edges[end, p]: the counts are those of
+# fit(Histogram, x, range-like linspace edges; closed=:left) with the last bin closed.  lo / hi: d values each, or `nothing`: the
+# smallest and largest draw of every parameter.
+function histogram(h, g_from, g_to, d; bins=33, lo::Union{Vector{Float64},Nothing}=nothing, hi::Union{Vector{Float64},Nothing}=nothing)
+    counts = zeros(Int64, bins, d); edges = zeros(bins + 1, d); below = zeros(Int64, d); above = zeros(Int64, d); nan = zeros(Int64, d)
+    chk(ccall((:demcz_histogram, libdemcz), Int32,
+              (Ptr{Cvoid}, Int64, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+              h, g_from, g_to, Int32(bins), lo === nothing ? C_NULL : lo, hi === nothing ? C_NULL : hi, edges, counts, below, above, nan), h)
+    (counts=counts, edges=edges, below=below, above=above, nan=nan)
+end
+# pairs: 2 x npairs, 1-based parameters (p, q), p != q; counts[ky, kx, i] of pair i under edges_x[:, p] and edges_y[:, q]
+function histogram2d(h, g_from, g_to, d, pairs::Matrix{Int}; bins=(32, 32), lo::Union{Vector{Float64},Nothing}=nothing,
+                     hi::Union{Vector{Float64},Nothing}=nothing)
+    nbx, nby = bins
+    np = size(pairs, 2)
+    pr = Matrix{Int32}(pairs .- 1)
+    counts = zeros(Int64, nby, nbx, np); ex = zeros(nbx + 1, d); ey = zeros(nby + 1, d); outside = zeros(Int64, np)
+    chk(ccall((:demcz_histogram2d, libdemcz), Int32,
+              (Ptr{Cvoid}, Int64, Int64, Int32, Ptr{Int32}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}),
+              h, g_from, g_to, Int32(np), pr, Int32(nbx), Int32(nby), lo === nothing ? C_NULL : lo, hi === nothing ? C_NULL : hi,
+              ex, ey, counts, outside), h)
+    (counts=counts, pairs=pairs, edges_x=ex, edges_y=ey, outside=outside)
+end
+# the highest-density interval: the shortest interval between two order statistics that spans floor(prob S) steps of the S sorted
+# draws; out[1, j, p], out[2, j, p] = its ends for probability j and parameter p (NaN for a parameter with a NaN draw)
+function hdi(h, g_from, g_to, d, probs::Vector{Float64}=[0.94])
+    out = zeros(2, length(probs), d)
+    chk(ccall((:demcz_hdi, libdemcz), Int32, (Ptr{Cvoid}, Int64, Int64, Int32, Ptr{Float64}, Ptr{Float64}),
+              h, g_from, g_to, Int32(length(probs)), probs, out), h)
+    out
+end
+
 # ---- the marginal likelihood by bridge sampling (include/demcz.h: demcz_bridge; not in the reference) ------------------------
 # log Z = log ∫ exp(logobj(x)) dx from the history on the device: the first half of the window g_from:g_to fits a normal proposal,
 # the second half is iterated against as many fresh draws of it.  Assumes log_obj is the untempered log-posterior (not an
