@@ -68,7 +68,7 @@ def snooker_step(O, seed, chain, B, Z, M, x, lp, logobj, gamma, T=None):
     for p in range(1, d):
         e2 = e2 + e[p] * e[p]
         t = t + (z1[p] - z2[p]) * e[p]
-    facts = dict(i1=i1, i2=i2, ia=ia, gamma_s=gs, logu=logu, e2=e2, valid=False, accepted=False)
+    facts = dict(i1=i1, i2=i2, ia=ia, gamma_s=gs, logu=logu, e2=e2, valid=False, accepted=False, lp=lp, T=T)
     if not norm_ok(e2):                      # (what follows would divide by it; the step rejects whatever it gives)
         return list(x), lp, facts
     c = gs * (t / e2)
@@ -77,7 +77,7 @@ def snooker_step(O, seed, chain, B, Z, M, x, lp, logobj, gamma, T=None):
     f2 = f[0] * f[0]
     for p in range(1, d):
         f2 = f2 + f[p] * f[p]
-    facts["f2"] = f2
+    facts.update(f2=f2, xp=list(xp))
     if not norm_ok(f2):
         return list(x), lp, facts
     facts["valid"] = True
@@ -88,7 +88,7 @@ def snooker_step(O, seed, chain, B, Z, M, x, lp, logobj, gamma, T=None):
         if T is not None:
             dlt = dlt / np.float64(T)        # (NumPy: T = 0 gives +-inf or NaN as IEEE says, where Python raises)
         accept = bool(np.float64(logu) < dlt + np.float64(jac))
-    facts.update(lp_prop=lpp, jac=jac, accepted=accept)
+    facts.update(lp_prop=lpp, jac=jac, accepted=accept, dlt=float(dlt))      # dlt: as it entered the comparison, after the division by T
     return (xp, lpp, facts) if accept else (list(x), lp, facts)
 
 

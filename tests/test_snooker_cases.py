@@ -4,6 +4,10 @@
   * every world shows accepted and rejected snooker steps; the marked worlds show steps whose norms are no positive normal
     doubles (e2 == 0 from a chain that meets its own row; infinite and NaN norms from +-inf in the archive); the tempered world
     has T = 0 at snooker and at ordinary generations;
+  * every main world has steps that a wrong kernel would decide otherwise -- the Jacobian's exponent one off in either direction,
+    the temperature ignored or applied to the Jacobian too, a blocked handle's quadratic form summed in one piece -- at K
+    boundaries and away from them, and the edge worlds show both outcomes in their last wave (three invalid steps on three rows);
+    the planned kernel names are exactly the built-in instantiations and the program units of d = 2, 3, 4, 7, 32;
   * the anchor is never one of the two projected rows and is uniform over the others (exhaustive at M = 3, 4, 5);
   * gamma_s stays within its bounds, ends included;
   * a run cut into pieces is the run in one piece (the reference's own cut rule);
@@ -19,7 +23,7 @@ import snooker_reference as sr
 from helpers import same_bits
 
 
-@pytest.mark.parametrize("name", list(sc.WORLDS))
+@pytest.mark.parametrize("name", list(sc.MAIN))
 def test_every_world_shows_both_outcomes(oracle, name):
     w, ref, run = sc.reference(oracle, name)
     facts = [f for _, _, f in run.steps]
@@ -33,6 +37,122 @@ def test_every_world_shows_both_outcomes(oracle, name):
     if w["needs_invalid"]:
         assert sum(not f["valid"] for f in facts) >= 3, name
     assert ref["M"] == w["Z0"].shape[0] + w["N"] * (w["G"] // w["K"])
+
+
+@pytest.mark.parametrize("name", list(sc.MAIN))
+def test_every_world_has_the_steps_a_wrong_kernel_decides_otherwise(oracle, name):
+    """Each count is of steps on which the bit comparison would catch the named wrong kernel; three of each, this project's usual count."""
+    w, _, run = sc.reference(oracle, name)
+    c = sc.step_counts(oracle, w, run)
+    print(name, {k: v for k, v in c.items() if not isinstance(v, set)})
+    assert c["flip_lo"] >= 3 and c["flip_hi"] >= 3, f"{name}: decisions that differ with the exponent d - 2: {c['flip_lo']}, with d: {c['flip_hi']}"
+    sn = sc.snooker_generations(w)
+    assert any(g % w["K"] == 0 for g in sn), name
+    assert c["b_acc"] >= 3 and c["b_rej"] >= 3, f"{name}: at multiples of K {c['b_acc']} accepted, {c['b_rej']} rejected"
+    if any(g % w["K"] != 0 for g in sn):
+        assert c["nb_acc"] >= 3 and c["nb_rej"] >= 3, f"{name}: away from multiples of K {c['nb_acc']} accepted, {c['nb_rej']} rejected"
+    else:
+        assert c["nb_acc"] == c["nb_rej"] == 0
+    if w["temperature"] is not None:
+        assert c["t_ignored"] >= 3, f"{name}: decisions that differ with T ignored: {c['t_ignored']}"
+        assert c["t_jacobian"] >= 3, f"{name}: decisions that differ with the Jacobian divided by T too: {c['t_jacobian']}"
+        assert {0.0, 1e-300, 1e300} <= c["T_at_snooker"], name
+        if name != "mvn5_tempered":              # a plain piece with snooker and ordinary generations in it
+            plain = [(a, b) for a, b, t in w["pieces"] if not t]
+            assert len(plain) == 1 and any(a <= g <= b for a, b in plain for g in sn) and any(a <= g <= b and g not in sn for a, b in plain for g in range(a, b + 1))
+    else:
+        assert c["T_at_snooker"] == set() and all(not t for _, _, t in w["pieces"])
+    if len(w["blocks"]) > 1:
+        differ, accepted = sc.grouping_counts(oracle, w, run)
+        if name == "mvn8_inter":
+            assert differ == 0, "an interleaved structure groups nothing"
+        else:
+            assert accepted >= 3, f"{name}: {differ} proposals with other bits in the ungrouped order, {accepted} of them accepted"
+
+
+def test_the_worlds_with_tempered_or_grouped_steps_are_the_ones_meant():
+    assert {n for n, df in sc.MAIN.items() if df[4].get("tempered")} == {n for n in sc.MAIN if n.endswith("_tempered")} and \
+        len([n for n in sc.MAIN if n.endswith("_tempered")]) == 11
+    assert {n for n, df in sc.MAIN.items() if "blocks" in df[4]} == {"mvn6_blocks", "mvn10_halves", "mvn20_4x5", "mvn8_inter", "mvn10_halves_tempered"}
+    assert list(sc.MAIN)[:16] == list(sc.WORLDS) and len(sc.MAIN) == 41 and not set(sc.MAIN) & set(sc.EDGE_WORLDS)
+
+
+@pytest.mark.parametrize("name", list(sc.EDGE_WORLDS))
+def test_every_edge_world_is_at_its_edge(oracle, name):
+    w, ref, run = sc.reference(oracle, name)
+    facts = [f for _, _, f in run.steps]
+    sn = sc.snooker_generations(w)
+    assert run.snooker_generations == sn and len(facts) == w["N"] * len(sn)
+    assert all(f["ia"] not in (f["i1"], f["i2"]) and f["i1"] != f["i2"] for f in facts)
+    assert all(w["gamma_s"][0] <= f["gamma_s"] <= w["gamma_s"][1] for f in facts)
+    assert ref["M"] == w["Z0"].shape[0] + w["N"] * (w["G"] // w["K"])
+    c = sc.step_counts(oracle, w, run)
+    print(name, {k: v for k, v in c.items() if not isinstance(v, set)})
+    if name == "mvn5_never":                     # by its definition: no snooker generation in the run
+        assert sn == [] and w["every"] > w["G"]
+        return
+    assert sn, name
+    if w["N"] >= 63:
+        assert c["last_wave"] == {True, False}, f"{name}: the last wave's outcomes"
+    if w["three_rows"]:
+        assert w["Z0"].shape[0] == 3 and w["N"] in (1, 2)
+        assert c["accepted"] >= 1 and c["rejected"] >= 1 and c["invalid"] >= 3, name
+    if w["needs_invalid"]:
+        assert c["invalid"] >= 3, name
+    if w["gamma_s"][0] == w["gamma_s"][1]:
+        assert {f["gamma_s"] for f in facts} == {w["gamma_s"][0]} and c["accepted"] >= 10 and c["rejected"] >= 10
+
+
+def test_the_edge_worlds_are_invalid_in_the_ways_they_claim(oracle):
+    for name in ("rosenbrock7_own_row", "mvn8_own_row", "mvn10_own_row"):
+        _, _, own = sc.reference(oracle, name)
+        assert sum(f["e2"] == 0.0 for _, _, f in own.steps) >= 3, name
+    for name in ("mvn8_inf", "mvn10_inf"):
+        _, ref, inf = sc.reference(oracle, name)
+        assert any(math.isinf(f["e2"]) for _, _, f in inf.steps) and any(math.isnan(v) or math.isinf(v) for v in (f.get("f2", 1.0) for _, _, f in inf.steps)), name
+        assert np.isfinite(ref["chain"][:, :, [g - 1 for g in inf.snooker_generations]]).all(), name
+
+
+@pytest.mark.parametrize("name,E", sc.LAGGED)
+def test_the_lagged_worlds_accept_steps_at_their_boundaries(oracle, name, E):
+    """A kernel that stored the state from before the step as the boundary snapshot would be wrong in every accepted step of a
+    snooker generation that is a multiple of K; the lag shows inside the run, not only in the final archive."""
+    w, ref, run = sc.lagged_reference(oracle, name, E)
+    assert w["temperature"] is None and w["closure"] is None
+    c = sc.step_counts(oracle, w, run)
+    assert c["b_acc"] >= 3 and c["b_rej"] >= 3, (name, c["b_acc"], c["b_rej"])
+    _, plain, _ = sc.reference(oracle, name)
+    first_seen = (-(-1 // E) * E + E) * w["K"] + 1
+    assert first_seen <= w["G"] and ref["M"] == plain["M"] and ref["Z"].shape == plain["Z"].shape
+    assert np.array_equal(ref["chain"][:, :, :w["K"]], plain["chain"][:, :, :w["K"]]) and not np.array_equal(ref["chain"], plain["chain"])
+    assert not np.array_equal(ref["Z"], plain["Z"])
+
+
+def test_the_planned_kernel_names_are_every_instantiation(oracle):
+    """The ten specialised built-in instantiations, the three run-time-d ones and the program units of d = 2, 3, 4, 7 and 32: a world
+    dropped later is noticed here."""
+    assert len(sc.PLANNED_NAMES) == 10 + 3 + 5
+    assert {sc.planned_kernel(sc.world(n)) for n in sc.MAIN} == sc.PLANNED_NAMES
+    assert {sc.planned_kernel(sc.world(n)) for n in sc.MAIN if n.endswith("_tempered")} == {
+        "demcz::snooker_kernel<MVNORMAL, 5>", "demcz::snooker_kernel<MVNORMAL, 8>", "demcz::snooker_kernel<MVNORMAL, 10>",
+        "demcz::snooker_kernel<MVNORMAL, 20>", "demcz::snooker_kernel_generic<MVNORMAL>", "demcz::snooker_kernel<ISO_QUAD, 10>",
+        "demcz::snooker_kernel_generic<ISO_QUAD>", "demcz::snooker_kernel<LINREG_SSE, 10>", "demcz::snooker_kernel<LINREG_SSE, 26>",
+        "demcz::snooker_kernel_generic<LINREG_SSE>", "demcz::snooker_kernel<4, 7> (program)"}
+
+
+def test_the_schedules_end_calls_on_and_in_front_of_snooker_generations():
+    for name in sc.ALL:
+        w = sc.world(name)
+        sn, ends = set(sc.snooker_generations(w)), [b for _, b, _ in w["pieces"]]
+        assert [a for a, _, _ in w["pieces"]] == [1] + [b + 1 for b in ends[:-1]] and ends[-1] == w["G"], name
+        if sn:
+            assert any(b in sn for b in ends) and any(b + 1 in sn and b not in sn or (w["every"] == 1 and b + 1 in sn) for b in ends), name
+        counts = sc.launches_after(w)
+        assert counts == sorted(counts) and counts[-1] >= len(sn) + (0 if w["every"] == 1 else 1), name
+    # the rule by hand: K = 10, every = 3, calls that end at 2, 3, 20, 30, 40
+    # 1-2 | 3 | 4-5 6 7-8 9 10 11 12 13-14 15 16-17 18 19-20 | 21 22-23 24 25-26 27 28-29 30 | 31-32 33 34-35 36 37-38 39 40
+    assert sc.launches_after(sc.world("mvn7")) == [1, 2, 14, 21, 28]
+    assert sc.launches_after(sc.world("mvn5_never")) == [1, 3, 5] and sc.launches_after(sc.world("mvn5_k1")) == [1, 2, 20, 31, 40]
 
 
 def test_the_marked_worlds_are_invalid_in_the_ways_they_claim(oracle):
