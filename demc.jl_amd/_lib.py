@@ -53,6 +53,7 @@ SYMBOLS = [
     "demcz_quantile_plan", "demcz_select_counts", "demcz_select_step", "demcz_quantile_finish", "demcz_quantiles",
     "demcz_quantiles_array", "demcz_best", "demcz_best_array",
     "demcz_derive_check", "demcz_derive", "demcz_derive_array",
+    "demcz_predict_check", "demcz_predict", "demcz_predict_array", "demcz_ppc", "demcz_ppc_array",
     "demcz_rank_to_z", "demcz_rank_normalize", "demcz_rank_normalize_array", "demcz_indicator_le", "demcz_rank_diagnostics",
     "demcz_rank_diagnostics_array",
     "demcz_set_snooker", "demcz_get_snooker",
@@ -225,6 +226,15 @@ def load():
     L.demcz_derive.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_char_p, C.c_char_p, _dp, C.c_int64, C.POINTER(C.c_void_p)]
     L.demcz_derive_array.argtypes = [C.c_int32, _dp, _dp, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_char_p, C.c_char_p, _dp,
                                      C.c_int64, C.POINTER(C.c_void_p)]
+    L.demcz_predict_check.argtypes = [C.c_int32, C.c_int32, C.c_char_p, C.c_char_p]
+    L.demcz_predict.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_char_p, C.c_char_p, _dp, C.c_int64, C.c_uint64, C.c_int64,
+                                C.POINTER(C.c_void_p)]
+    L.demcz_predict_array.argtypes = [C.c_int32, _dp, _dp, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_char_p, C.c_char_p, _dp,
+                                      C.c_int64, C.c_uint64, C.c_int64, C.POINTER(C.c_void_p)]
+    L.demcz_ppc.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_char_p, C.c_char_p, _dp, C.c_int64, C.c_uint64, C.c_int64,
+                            _dp, _lp]
+    L.demcz_ppc_array.argtypes = [C.c_int32, _dp, _dp, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_char_p, C.c_char_p, _dp,
+                                  C.c_int64, C.c_uint64, C.c_int64, _dp, _lp]
     L.demcz_rank_to_z.argtypes = [C.c_int64, _dp, C.c_int64, _dp]
     L.demcz_rank_normalize.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, _dp, C.POINTER(C.c_void_p)]
     L.demcz_rank_normalize_array.argtypes = [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int64, C.c_int32, _dp, C.POINTER(C.c_void_p)]

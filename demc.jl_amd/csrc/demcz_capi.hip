@@ -4752,6 +4752,139 @@ extern "C" int32_t demcz_derive_array(int32_t device_id, const double* chain, co
                        [&](demcz_handle* h) { return derive_from(h, 1, G, m, source, options, data, ndata, derived); });
 }
 
+// ---- posterior predictive programs: functions of the draws and of each draw's own random stream (demcz_kernels_predict.h) -------
+extern "C" int32_t demcz_predict_check(int32_t d, int32_t m, const char* source, const char* options)
+{
+    std::shared_ptr<const demcz_prog::Code> code;
+    std::string err;
+    if (demcz_prog::get_code(d, source, options, demcz_prog::UNIT_PREDICT, code, err, m) != 0) return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, err);
+    return DEMCZ_OK;
+}
+
+namespace {
+// What demcz_predict and demcz_ppc share up to their allocations: the window, the arguments, the stream's two 32-bit halves
+// (generation and global chain: DESIGN.md section 3), the device, the program's module.
+int32_t predict_open(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t m, const char* source, const char* options, const double* data,
+                     int64_t ndata, int64_t chain_id0, const char* who, Window& win, demcz_prog::Module& mod)
+{
+    int32_t rc = open_window(h, g_from, g_to, who, win);
+    if (rc) return rc;
+    if (ndata < 0 || (ndata > 0 && !data)) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": need ndata >= 0 and data for ndata > 0");
+    constexpr int64_t TWO32 = (int64_t)1 << 32;
+    if (g_to >= TWO32 || chain_id0 < 0 || chain_id0 > TWO32 - win.N)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": the stream of a draw is keyed by (generation, global chain), 32 bits each: need "
+                                                   "g_to < 2^32 and 0 <= chain_id0, chain_id0 + N <= 2^32");
+    rc = enter_device(h);
+    if (rc) return rc;
+    std::shared_ptr<const demcz_prog::Code> code;
+    std::string err;
+    if (demcz_prog::get_code(win.d, source, options, demcz_prog::UNIT_PREDICT, code, err, m) != 0) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, err);
+    if (demcz_prog::get_module(code, h->cfg.device_id, mod, err) != 0) return fail(h, DEMCZ_ERR_HIP, err);
+    return quiesce_all(h);                      // (a sharded handle: the allocations that follow synchronise the device)
+}
+
+// demcz_predict on a source that holds an N x d x Gcap history (a sampling handle, a derived history, a ScratchHandle)
+int32_t predict_from(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t m, const char* source, const char* options,
+                     const double* data, int64_t ndata, uint64_t seed, int64_t chain_id0, demcz_handle** derived)
+{
+    const char* who = "demcz_predict";
+    Window win;
+    demcz_prog::Module mod;
+    int32_t rc = predict_open(h, g_from, g_to, m, source, options, data, ndata, chain_id0, who, win, mod);
+    if (rc) return rc;
+    std::string err;
+    NewDerived dh = derived_create(h->cfg.device_id, win.N, m, win.w, g_from - 1, data, ndata, err, who);
+    if (!dh) return fail(h, DEMCZ_ERR_HIP, err);
+    const double* chain = h->dchain;
+    const double* logobj = h->dlogobj;          // (nullptr on a derived history and on arrays given without log_obj: logp is NaN)
+    const double* ddata = ndata > 0 ? dh->d_design : nullptr;
+    double* out = dh->dchain;
+    void* args[] = {&chain, &logobj, &win.N, &win.s0, &win.total, &ddata, &ndata, &seed, &g_from, &chain_id0, &out};
+    const hipError_t e = hipModuleLaunchKernel(mod.derive, derive_blocks(win.total), 1, 1, DERIVE_THREADS, 1, 1, 0, h->stream, args, nullptr);
+    return finish(h, who, "predict_kernel", e, dh, derived);
+}
+
+// demcz_ppc on such a source.  One pool block holds what the kernel reads and writes besides the history: the 3 m counters,
+// observed, the program's data.
+int32_t ppc_from(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t m, const char* source, const char* options, const double* data,
+                 int64_t ndata, uint64_t seed, int64_t chain_id0, const double* observed, int64_t* counts)
+{
+    const char* who = "demcz_ppc";
+    Window win;
+    demcz_prog::Module mod;
+    int32_t rc = predict_open(h, g_from, g_to, m, source, options, data, ndata, chain_id0, who, win, mod);
+    if (rc) return rc;
+    static_assert(sizeof(unsigned long long) == sizeof(double) && sizeof(int64_t) == sizeof(double), "one block of 8-byte words");
+    const size_t nc = 3 * (size_t)m;
+    std::vector<double> up((size_t)m + (size_t)ndata, 0.0);         // observed (NULL: zeros), then data
+    if (observed) std::copy(observed, observed + m, up.begin());
+    if (ndata > 0) std::copy(data, data + ndata, up.begin() + m);
+    std::vector<int64_t> hc(nc);
+    DevBlock blk;
+    if (blk.alloc(h->cfg.device_id, (nc + up.size()) * sizeof(double)) != hipSuccess)
+        return fail(h, DEMCZ_ERR_HIP, std::string(who) + ": the counters, observed and the program's data: out of device memory");
+    unsigned long long* dcounts = static_cast<unsigned long long*>(blk.p);
+    const double* dobs = reinterpret_cast<const double*>(dcounts + nc);
+    const double* ddata = ndata > 0 ? dobs + m : nullptr;
+    auto body = [&]() -> int32_t {
+        HIPCHK(h, hipMemsetAsync(dcounts, 0, nc * sizeof(unsigned long long), h->stream));
+        HIPCHK(h, hipMemcpyAsync(const_cast<double*>(dobs), up.data(), up.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        const double* chain = h->dchain;
+        const double* logobj = h->dlogobj;
+        void* args[] = {&chain, &logobj, &win.N, &win.s0, &win.total, &ddata, &ndata, &seed, &g_from, &chain_id0, &dobs, &dcounts};
+        const hipError_t e = hipModuleLaunchKernel(mod.ppc, derive_blocks(win.total), 1, 1, DERIVE_THREADS, 1, 1, 0, h->stream, args, nullptr);
+        if (e != hipSuccess) return fail(h, DEMCZ_ERR_HIP, std::string(who) + ": launching ppc_kernel: " + hipGetErrorString(e));
+        HIPCHK(h, hipMemcpyAsync(hc.data(), dcounts, nc * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+        return sync_stream(h, h->stream, who);
+    };
+    rc = body();
+    if (rc) { (void)hipStreamSynchronize(h->stream); return settle(rc); }   // (copies from and into this call's vectors may be under way)
+    std::copy(hc.begin(), hc.end(), counts);
+    return DEMCZ_OK;
+}
+}  // namespace
+
+extern "C" int32_t demcz_predict(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t m, const char* source, const char* options,
+                                 const double* data, int64_t ndata, uint64_t seed, int64_t chain_id0, demcz_handle** derived)
+{
+    if (!h || !derived) return DEMCZ_ERR_INVALID_ARGUMENT;
+    *derived = nullptr;
+    DEADCHK(h);
+    return predict_from(h, g_from, g_to, m, source, options, data, ndata, seed, chain_id0, derived);
+}
+
+extern "C" int32_t demcz_predict_array(int32_t device_id, const double* chain, const double* log_obj, int64_t N, int32_t d, int64_t G,
+                                       int32_t m, const char* source, const char* options, const double* data, int64_t ndata,
+                                       uint64_t seed, int64_t chain_id0, demcz_handle** derived)
+{
+    if (!chain || !derived) return DEMCZ_ERR_INVALID_ARGUMENT;
+    *derived = nullptr;
+    // (compiled before anything is uploaded: a program that does not compile costs no copy)
+    int32_t rc = demcz_predict_check(d, m, source, options);
+    if (rc) return rc;
+    return with_arrays(device_id, N, d, G, chain, log_obj,
+                       [&](demcz_handle* h) { return predict_from(h, 1, G, m, source, options, data, ndata, seed, chain_id0, derived); });
+}
+
+extern "C" int32_t demcz_ppc(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t m, const char* source, const char* options,
+                             const double* data, int64_t ndata, uint64_t seed, int64_t chain_id0, const double* observed, int64_t* counts)
+{
+    if (!h || !counts) return DEMCZ_ERR_INVALID_ARGUMENT;
+    DEADCHK(h);
+    return ppc_from(h, g_from, g_to, m, source, options, data, ndata, seed, chain_id0, observed, counts);
+}
+
+extern "C" int32_t demcz_ppc_array(int32_t device_id, const double* chain, const double* log_obj, int64_t N, int32_t d, int64_t G,
+                                   int32_t m, const char* source, const char* options, const double* data, int64_t ndata,
+                                   uint64_t seed, int64_t chain_id0, const double* observed, int64_t* counts)
+{
+    if (!chain || !counts) return DEMCZ_ERR_INVALID_ARGUMENT;
+    int32_t rc = demcz_predict_check(d, m, source, options);
+    if (rc) return rc;
+    return with_arrays(device_id, N, d, G, chain, log_obj,
+                       [&](demcz_handle* h) { return ppc_from(h, 1, G, m, source, options, data, ndata, seed, chain_id0, observed, counts); });
+}
+
 // ---- rank-normalised diagnostics (K10, demcz_kernels_rank.h): average ranks, normal scores, indicator columns -----------------
 namespace {
 // Everything a ranking needs besides the two key buffers, carved from ONE pool allocation so that there is one thing to free.

@@ -23,7 +23,9 @@ constexpr int MAX_DERIVE_M = demcz::DERIVE_MAX_M;
 // A pointwise program (demcz_pointwise) likewise: the user's demcz_loglik and pointwise_kernel of demcz_kernels_pointwise.h.
 // A program target's bridge unit (demcz_bridge_proposal): the user's demcz_logobj and bridge_proposal_program_kernel of
 // demcz_kernels_bridge.h.
-enum { UNIT_ONE_LANE = 0, UNIT_WAVE = 1, UNIT_DERIVE = 2, UNIT_POINTWISE = 3, UNIT_BRIDGE = 4 };
+// A predictive program (demcz_predict, demcz_ppc): demcz_device.h, the demcz_rng of demcz_predict_rng.h, the user's demcz_predict,
+// and predict_kernel and ppc_kernel of demcz_kernels_predict.h.
+enum { UNIT_ONE_LANE = 0, UNIT_WAVE = 1, UNIT_DERIVE = 2, UNIT_POINTWISE = 3, UNIT_BRIDGE = 4, UNIT_PREDICT = 5 };
 constexpr int WAVE_MIN_D = 2;
 
 // One compiled program: the gfx950 code object and the mangled names of its kernels.
@@ -36,9 +38,10 @@ struct Code {
     std::string wave[2][2];       // UNIT_WAVE: window_kernel_ps / _pw<TARGET_PROGRAM, d, LIVE, TEMPER>, [LIVE][TEMPER] (the one-lane
                                   // kernels are not in that unit, and these not in the one-lane unit)
     std::string derive;           // UNIT_DERIVE: derive_kernel, the only kernel of that unit; UNIT_POINTWISE: pointwise_kernel;
-                                  // UNIT_BRIDGE: bridge_proposal_program_kernel
+                                  // UNIT_BRIDGE: bridge_proposal_program_kernel; UNIT_PREDICT: predict_kernel
+    std::string ppc;              // UNIT_PREDICT: ppc_kernel
     int d = 0;
-    int m = 0;                    // UNIT_DERIVE: derived quantities per draw (DEMCZ_M)
+    int m = 0;                    // UNIT_DERIVE, UNIT_PREDICT: derived quantities per draw (DEMCZ_M)
     int unit = UNIT_ONE_LANE;
 };
 
@@ -47,12 +50,14 @@ struct Module {
     hipModule_t module = nullptr;
     hipFunction_t window_full = nullptr, window_blocks = nullptr, snooker = nullptr, logp = nullptr;
     hipFunction_t wave[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    hipFunction_t derive = nullptr;   // (UNIT_POINTWISE: pointwise_kernel; UNIT_BRIDGE: bridge_proposal_program_kernel)
+    hipFunction_t derive = nullptr;   // (UNIT_POINTWISE: pointwise_kernel; UNIT_BRIDGE: bridge_proposal_program_kernel; UNIT_PREDICT: predict_kernel)
+    hipFunction_t ppc = nullptr;      // UNIT_PREDICT: ppc_kernel
     std::shared_ptr<const Code> code;
 };
 
 // Compile `source` for dimension d into `unit` (or take it from the process-wide cache, whose key includes the unit).  Needs no
-// device.  Returns 0, or 1 with the compiler log (or what else went wrong) in err.  m: UNIT_DERIVE only, 1..32 (part of the key).
+// device.  Returns 0, or 1 with the compiler log (or what else went wrong) in err.  m: UNIT_DERIVE and UNIT_PREDICT only, 1..32 (part of
+// the key).
 int32_t get_code(int d, const char* source, const char* options, int unit, std::shared_ptr<const Code>& out, std::string& err, int m = 0);
 // Load a code object on `device` (or take it from the cache).  Returns 0, or 2 (a HIP error) with the message in err.
 int32_t get_module(const std::shared_ptr<const Code>& code, int device, Module& out, std::string& err);

@@ -27,6 +27,9 @@
 // The bridge unit (UNIT_BRIDGE, demcz_bridge_proposal): DEMCZ_D, DEMCZ_BRIDGE_UNIT, the user's demcz_logobj exactly as a program
 // target defines it, then demcz_device.h (Philox, dm_log, the Box-Muller pair) and demcz_kernels_bridge.h, whose
 // bridge_proposal_program_kernel is its only kernel.  No struct of the library's is in it.  A key of its own in the same caches.
+// The predict unit (UNIT_PREDICT, demcz_predict and demcz_ppc): the derive unit's defines with DEMCZ_PREDICT_UNIT in place of
+// DEMCZ_DERIVE_UNIT, demcz_device.h, demcz_predict_rng.h (the demcz_rng of a draw and its four helpers), the user's demcz_predict
+// (#line 1 "program"), and demcz_kernels_predict.h with predict_kernel and ppc_kernel.  Same options, same caches, a key of its own.
 // Compile options: --offload-arch=gfx950 -O3 -ffp-contract=off -I<rocm>/include, the library's own layout switches (not for
 // the derive unit, which sees no struct of the library's), then the user's.  Code objects are cached per (composed text,
 // options), loaded modules per (code object, device); both for the life of the process.
@@ -94,6 +97,13 @@ const char k_pointwise_h[] = {
 const char k_bridge_h[] = {
 #embed "demcz_kernels_bridge.h"
     , 0};
+// the predict unit's headers (on top of demcz_device.h and the derive unit's launch constants)
+const char k_predict_rng_h[] = {
+#embed "demcz_predict_rng.h"
+    , 0};
+const char k_predict_h[] = {
+#embed "demcz_kernels_predict.h"
+    , 0};
 #pragma clang diagnostic pop
 
 // -D switches of the library build that change the layout of WindowParams: the program's kernels must see the same struct
@@ -134,6 +144,14 @@ std::string compose(int d, int m, const std::string& source, int unit)
           << "#include <hip/hip_runtime.h>\n#include <stdint.h>\n" << k_math_macros
           << "#line 1 \"program\"\n" << source << "\n"
           << "#line 1 \"demcz_unit_bridge\"\n#include \"demcz_kernels_bridge.h\"\n";
+        return s.str();
+    }
+    if (unit == demcz_prog::UNIT_PREDICT) {
+        s << "#define DEMCZ_D " << d << "\n#define DEMCZ_M " << m << "\n#define DEMCZ_PREDICT_UNIT\n"
+          << "#include <hip/hip_runtime.h>\n#include <stdint.h>\n" << k_math_macros
+          << "#include \"demcz_device.h\"\n#include \"demcz_predict_rng.h\"\n"
+          << "#line 1 \"program\"\n" << source << "\n"
+          << "#line 1 \"demcz_unit_predict\"\n#include \"demcz_kernels_predict.h\"\n";
         return s.str();
     }
     if (unit == demcz_prog::UNIT_WAVE) {
@@ -219,7 +237,8 @@ std::string trim_log(std::string log)
 // what a failed call says first: which of the two kinds of program it was about
 const char* who_of(int unit)
 {
-    return unit == demcz_prog::UNIT_DERIVE ? "derive program: " : unit == demcz_prog::UNIT_POINTWISE ? "pointwise program: " : "program target: ";
+    return unit == demcz_prog::UNIT_DERIVE ? "derive program: " : unit == demcz_prog::UNIT_POINTWISE ? "pointwise program: " :
+           unit == demcz_prog::UNIT_PREDICT ? "predictive program: " : "program target: ";
 }
 
 bool compile(const std::string& text, const std::vector<std::string>& opts, int d, int m, int unit, demcz_prog::Code& code, std::string& err)
@@ -229,8 +248,8 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
     const char* headers[] = {k_device_h, k_kernels_h, k_rec_h, k_ml_h, k_mlb_inc, k_pc_h, k_ps_h, k_pw_h};
     const char* names[] = {"demcz_device.h", "demcz_kernels.h", "demcz_kernels_rec.h", "demcz_kernels_ml.h", "demcz_mlb_dpp_20_5.inc",
                            "demcz_kernels_pc.h", "demcz_kernels_ps.h", "demcz_kernels_pw.h"};
-    const bool pointwise = unit == demcz_prog::UNIT_POINTWISE, bridge = unit == demcz_prog::UNIT_BRIDGE;
-    const bool wave = unit == demcz_prog::UNIT_WAVE, derive = unit == demcz_prog::UNIT_DERIVE || pointwise || bridge;   // (derive: a streaming unit)
+    const bool pointwise = unit == demcz_prog::UNIT_POINTWISE, bridge = unit == demcz_prog::UNIT_BRIDGE, predict = unit == demcz_prog::UNIT_PREDICT;
+    const bool wave = unit == demcz_prog::UNIT_WAVE, derive = unit == demcz_prog::UNIT_DERIVE || pointwise || bridge || predict;   // (derive: a streaming unit)
     const char* lane_headers[] = {k_device_h, k_kernels_h, k_snooker_h};
     const char* lane_names[] = {"demcz_device.h", "demcz_kernels.h", "demcz_kernels_snooker.h"};
     const char* derive_headers[] = {k_derive_h};
@@ -239,7 +258,10 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
     const char* pointwise_names[] = {"demcz_kernels_derive.h", "demcz_kernels_pointwise.h"};
     const char* bridge_headers[] = {k_device_h, k_derive_h, k_bridge_h};
     const char* bridge_names[] = {"demcz_device.h", "demcz_kernels_derive.h", "demcz_kernels_bridge.h"};
-    if (bridge) RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_unit_bridge.hip", 3, bridge_headers, bridge_names));
+    const char* predict_headers[] = {k_device_h, k_derive_h, k_predict_rng_h, k_predict_h};
+    const char* predict_names[] = {"demcz_device.h", "demcz_kernels_derive.h", "demcz_predict_rng.h", "demcz_kernels_predict.h"};
+    if (predict) RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_unit_predict.hip", 4, predict_headers, predict_names));
+    else if (bridge) RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_unit_bridge.hip", 3, bridge_headers, bridge_names));
     else if (pointwise) RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_unit_pointwise.hip", 2, pointwise_headers, pointwise_names));
     else if (derive) RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_unit_derive.hip", 1, derive_headers, derive_names));
     else if (wave) RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_program_wave_unit.hip", 8, headers, names));
@@ -248,7 +270,8 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
     const std::string ds = std::to_string(d);
     std::vector<std::string> exprs;
     if (derive) {
-        exprs = {bridge ? "&demcz::bridge_proposal_program_kernel" : pointwise ? "&demcz::pointwise_kernel" : "&demcz::derive_kernel"};
+        exprs = {predict ? "&demcz::predict_kernel" : bridge ? "&demcz::bridge_proposal_program_kernel" : pointwise ? "&demcz::pointwise_kernel" : "&demcz::derive_kernel"};
+        if (predict) exprs.push_back("&demcz::ppc_kernel");
     } else if (wave) {
         const std::string kn = (d <= 5) ? "&demcz::window_kernel_ps<4, " : "&demcz::window_kernel_pw<4, ";
         for (int live = 0; live < 2; ++live)
@@ -277,7 +300,10 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
         if (pointwise && text.find("demcz_loglik") == std::string::npos)
             err += "; the program does not define demcz_loglik -- it must define "
                    "__device__ double demcz_loglik(const double* x, const double* data, int64_t ndata, int64_t i)";
-        if (derive && !pointwise && !bridge && text.find("demcz_derive") == std::string::npos)    // (... and derive_kernel's in demcz_kernels_derive.h)
+        if (predict && text.find("demcz_predict(") == std::string::npos)    // (the unit's headers are included, not in `text`)
+            err += "; the program does not define demcz_predict -- it must define "
+                   "__device__ void demcz_predict(const double* x, double logp, const double* data, int64_t ndata, demcz_rng* rng, double* out)";
+        if (derive && !pointwise && !bridge && !predict && text.find("demcz_derive") == std::string::npos)    // (... and derive_kernel's in demcz_kernels_derive.h)
             err += "; the program does not define demcz_derive -- it must define "
                    "__device__ void demcz_derive(const double* x, double logp, const double* data, int64_t ndata, double* out)";
         err += ":\n" + trim_log(log);
@@ -289,12 +315,13 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
     RTCCHK(hiprtcGetCode(prog, code.object.data()));
     if (const char* dump = getenv("DEMCZ_PROGRAM_DUMP"); dump && *dump) {
         // diagnosis (scripts/kernel_regs.py, llvm-objdump): the code object as a file in that directory
-        const std::string path = std::string(dump) + "/demcz_program_" + (bridge ? "bridge" : pointwise ? "pointwise" : derive ? "derive" : wave ? "wave" : "lane") + "_d" + ds + "_" +
+        const std::string path = std::string(dump) + "/demcz_program_" + (predict ? "predict" : bridge ? "bridge" : pointwise ? "pointwise" : derive ? "derive" : wave ? "wave" : "lane") + "_d" + ds + "_" +
                                  std::to_string(std::hash<std::string>{}(text) % 1000000007ull) + ".co";
         if (FILE* f = fopen(path.c_str(), "wb")) { (void)fwrite(code.object.data(), 1, code.object.size(), f); fclose(f); }
     }
     std::vector<std::string*> lowered;
-    if (derive) lowered = {&code.derive};
+    if (predict) lowered = {&code.derive, &code.ppc};
+    else if (derive) lowered = {&code.derive};
     else if (wave) lowered = {&code.wave[0][0], &code.wave[0][1], &code.wave[1][0], &code.wave[1][1], &code.logp};
     else lowered = {&code.window_full, &code.window_blocks, &code.snooker, &code.logp};
     for (size_t i = 0; i < lowered.size(); ++i) {
@@ -315,7 +342,7 @@ namespace demcz_prog {
 
 int32_t get_code(int d, const char* source, const char* options, int unit, std::shared_ptr<const Code>& out, std::string& err, int m)
 {
-    if (unit != UNIT_ONE_LANE && unit != UNIT_WAVE && unit != UNIT_DERIVE && unit != UNIT_POINTWISE && unit != UNIT_BRIDGE) {
+    if (unit != UNIT_ONE_LANE && unit != UNIT_WAVE && unit != UNIT_DERIVE && unit != UNIT_POINTWISE && unit != UNIT_BRIDGE && unit != UNIT_PREDICT) {
         err = "program target: lanes_per_chain must be 0, 1 or DEMCZ_LAYOUT_PROGRAM_WAVE";
         return 1;
     }
@@ -324,7 +351,7 @@ int32_t get_code(int d, const char* source, const char* options, int unit, std::
         err = who + "d must be in 1.." + std::to_string(MAX_PROGRAM_D);
         return 1;
     }
-    if (unit == UNIT_DERIVE && (m < 1 || m > MAX_DERIVE_M)) {
+    if ((unit == UNIT_DERIVE || unit == UNIT_PREDICT) && (m < 1 || m > MAX_DERIVE_M)) {
         err = who + "m must be in 1.." + std::to_string(MAX_DERIVE_M);
         return 1;
     }
@@ -340,7 +367,7 @@ int32_t get_code(int d, const char* source, const char* options, int unit, std::
     std::string inc;
     if (!rocm_include(inc, err)) return 1;
     std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-I" + inc};
-    if (unit != UNIT_DERIVE && unit != UNIT_POINTWISE && unit != UNIT_BRIDGE)
+    if (unit != UNIT_DERIVE && unit != UNIT_POINTWISE && unit != UNIT_BRIDGE && unit != UNIT_PREDICT)
         for (const char* const* s = k_layout_switches; *s; ++s) opts.push_back(*s);
     for (auto& o : split_options(options)) opts.push_back(o);
     // (the text is the key: it names the unit's kernel header and, for a derive unit, DEMCZ_M)
@@ -369,9 +396,10 @@ int32_t get_module(const std::shared_ptr<const Code>& code, int device, Module& 
     Module m;
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipModuleLoadData(&m.module, code->object.data());
-    const bool streaming = code->unit == UNIT_DERIVE || code->unit == UNIT_POINTWISE || code->unit == UNIT_BRIDGE;
+    const bool streaming = code->unit == UNIT_DERIVE || code->unit == UNIT_POINTWISE || code->unit == UNIT_BRIDGE || code->unit == UNIT_PREDICT;
     if (streaming) {
         if (e == hipSuccess) e = hipModuleGetFunction(&m.derive, m.module, code->derive.c_str());
+        if (e == hipSuccess && code->unit == UNIT_PREDICT) e = hipModuleGetFunction(&m.ppc, m.module, code->ppc.c_str());
     } else if (code->unit == UNIT_WAVE) {
         for (int live = 0; live < 2; ++live)
             for (int temper = 0; temper < 2; ++temper)

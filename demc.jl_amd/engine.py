@@ -45,6 +45,43 @@ Best = namedtuple("Best", "bestval chain generation bestpar")
 RankDiagnostics = namedtuple("RankDiagnostics", "rhat_rank ess_bulk ess_tail")
 
 
+class PPC(namedtuple("PPC", "gt eq nan total names")):
+    """A posterior predictive check (demcz_ppc): per column of the program, how many of the ``total`` draws had a value greater
+    than the observed one (``gt``), equal to it (``eq``), or NaN (``nan``) -- int64 arrays of m entries; integer counts, so the
+    records of shards add field by field (``+``)."""
+    __slots__ = ()
+
+    @property
+    def p_value(self):
+        """P(T_rep >= T_obs) over the draws whose value is a number: (gt + eq) / (total - nan)."""
+        with np.errstate(all="ignore"):
+            return (self.gt + self.eq) / (self.total - self.nan)
+
+    @property
+    def mid_p(self):
+        """The mid p-value, which counts a tie as half: (gt + eq / 2) / (total - nan)."""
+        with np.errstate(all="ignore"):
+            return (self.gt + self.eq / 2) / (self.total - self.nan)
+
+    def __add__(self, other):
+        return PPC(self.gt + other.gt, self.eq + other.eq, self.nan + other.nan, self.total + other.total, self.names)
+
+
+def _ppc_observed(observed, m):
+    if observed is None:
+        return None
+    obs = _lib.f64(np.ravel(observed))
+    if obs.shape != (m,):
+        raise ValueError("observed must have m entries")
+    return obs
+
+
+def ppc_record(counts, total, names=None):
+    """The ``PPC`` of demcz_ppc's 3 m counts (gt, eq, nan of column 0, then of column 1, ...)."""
+    c = np.asarray(counts, dtype=np.int64).reshape(-1, 3)
+    return PPC(c[:, 0].copy(), c[:, 1].copy(), c[:, 2].copy(), int(total), names)
+
+
 class Histogram(namedtuple("Histogram", "counts edges below above nan")):
     """Marginal histograms (demcz_histogram): counts d x nbins int64, edges d x (nbins + 1), and per parameter the draws below the
     range, above it, and NaN.  Bin k holds edges[k] <= x < edges[k+1]; the last bin also holds x == edges[nbins]."""
@@ -463,6 +500,40 @@ class _HistoryStatistics:
         self._chk(self._L.demcz_derive(self._h, int(g_from), int(g_to), program.m, src, opts, data, ndata, C.byref(out)))
         return DerivedHistory(self._L, out, self.N, program.m, int(g_from), int(g_to), program.names, getattr(self, "chain_id0", 0))
 
+    def _stream_seed(self, seed):
+        """The key of the draws' random streams: ``seed``, or the run's own where this object has one."""
+        if seed is None:
+            seed = getattr(self, "seed", None)
+            if seed is None:
+                raise ValueError("seed is required: this history does not know the seed of a run")
+        return int(seed) & (2**64 - 1)
+
+    def predict(self, program, g_from, g_to, seed=None):
+        """``program`` (a ``PredictiveProgram``) at every draw of generations g_from..g_to, each draw with its own random stream
+        keyed by (seed, generation, global chain) (demcz_predict): a ``DerivedHistory`` whose generations keep their numbers.
+        ``seed``: default the engine's run seed (the streams cannot meet the sampler's); required on a ``DerivedHistory``."""
+        if program.d != self.d:
+            raise ValueError("the program's d is not the history's")
+        seed = self._stream_seed(seed)
+        src, opts, data, ndata = program._args()
+        out = C.c_void_p()
+        c0 = getattr(self, "chain_id0", 0)
+        self._chk(self._L.demcz_predict(self._h, int(g_from), int(g_to), program.m, src, opts, data, ndata, seed, c0, C.byref(out)))
+        return DerivedHistory(self._L, out, self.N, program.m, int(g_from), int(g_to), program.names, c0)
+
+    def ppc(self, program, g_from, g_to, observed=None, seed=None):
+        """The posterior predictive check of ``program`` (a ``PredictiveProgram``) over generations g_from..g_to (demcz_ppc): the
+        calls ``predict`` makes, but only the counts of its m columns against ``observed`` (m values; None: zeros) leave the
+        device -- a ``PPC`` record.  ``seed`` as for ``predict``."""
+        if program.d != self.d:
+            raise ValueError("the program's d is not the history's")
+        seed = self._stream_seed(seed)
+        obs = _ppc_observed(observed, program.m)
+        src, opts, data, ndata = program._args()
+        counts = np.zeros(3 * program.m, dtype=np.int64)
+        self._chk(self._L.demcz_ppc(self._h, int(g_from), int(g_to), program.m, src, opts, data, ndata, seed, getattr(self, "chain_id0", 0),
+                                    _lib.ptr(obs), _lib.ptr(counts, _lib._lp)))
+        return ppc_record(counts, self.N * (int(g_to) - int(g_from) + 1), program.names)
 
     def rank_normalize(self, g_from, g_to, center=None, ranks=False):
         """The normal scores of the exact average ranks of every draw of generations g_from..g_to among all the window's draws of
@@ -578,7 +649,7 @@ class _HistoryStatistics:
 class DerivedHistory(_HistoryStatistics):
     """An N x m x w history of derived quantities on the device (``demcz_derive``): generations ``g_from..g_to``, numbered as in
     the history it came from.  ``rhat``, ``rhat_partial``, ``autocov_sums``, ``ess``, ``select_counts``, ``quantiles``, ``mean_cov``,
-    ``derive``, ``rank_normalize``, ``indicator_le``, ``rank_diagnostics``, ``histogram``, ``histogram2d``, ``hdi``, ``pointwise``, ``loo_columns`` and ``loo`` are ``HipEngine``'s; nothing else of an engine applies (the library answers ERR_STATE)."""
+    ``derive``, ``predict``, ``ppc``, ``rank_normalize``, ``indicator_le``, ``rank_diagnostics``, ``histogram``, ``histogram2d``, ``hdi``, ``pointwise``, ``loo_columns`` and ``loo`` are ``HipEngine``'s; nothing else of an engine applies (the library answers ERR_STATE)."""
 
     def __init__(self, L, handle, N, m, g_from, g_to, names=None, chain_id0=0):
         self._L, self._h = L, handle

@@ -191,6 +191,33 @@ class DerivedProgram:
             raise _lib.DemczError(rc, (L.demcz_last_error(None) or b"").decode())
 
 
+class PredictiveProgram(DerivedProgram):
+    """A ``DerivedProgram`` that is also given random numbers (``demcz_predict`` and ``demcz_ppc``, include/demcz.h): replicated
+    data ``y_rep ~ p(y | theta)``, predictive draws at new covariates, posterior predictive p-values.
+
+    ``source`` defines ``__device__ void demcz_predict(const double* x, double logp, const double* data, int64_t ndata,
+    demcz_rng* rng, double* out)``; everything but ``rng`` is ``DerivedProgram``'s, limits and compile options included.  ``rng``
+    is the draw's own stream, consumed through ``demcz_uniform(rng)`` (in (0, 1)), ``demcz_normal(rng)``,
+    ``demcz_exponential(rng)`` and ``demcz_bits(rng, &r1, &r2)`` (128 raw bits).  The stream of the draw of global chain ``c`` at
+    generation ``g`` is keyed by ``(seed, g, c)`` and by nothing else: the numbers do not depend on the
+    window asked for, the launch, the sharding or ``set_history_origin``, and a draw may take as many as it likes.
+
+    Two programs run with one seed are given the same random numbers: pass different seeds where their results must be
+    independent.
+
+    Used through ``HipEngine.predict`` and ``HipEngine.ppc`` (also on a ``DerivedHistory``), ``demc.predict_chain`` and
+    ``demc.ppc_chain``.
+    """
+
+    def check(self):
+        """Compile the program (no device needed); raises ``DemczError`` with the compiler log if it does not compile."""
+        L = _lib.load()
+        src, opts, _, _ = self._args()
+        rc = L.demcz_predict_check(self.d, self.m, src, opts)
+        if rc != 0:
+            raise _lib.DemczError(rc, (L.demcz_last_error(None) or b"").decode())
+
+
 class PointwiseProgram:
     """The log-likelihood of every observation at a draw, written as HIP C++ and run on the device over a history
     (``demcz_pointwise`` and ``demcz_loo``, include/demcz.h): the input of PSIS-LOO and WAIC.

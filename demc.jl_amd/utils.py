@@ -227,11 +227,8 @@ def posterior_summary(chain, device_id=0, probs=None, rank_normalized=False, hdi
     return out
 
 
-def derive_chain(chain, log_obj, program, device_id=0):
-    """``program`` (a ``DerivedProgram``) evaluated on every draw of an Npop x Npar x Ngeneration history and its
-    Npop x Ngeneration ``log_obj`` (or None: the program's ``logp`` is NaN) -- a ``DerivedHistory`` on the device, generations
-    1..Ngeneration (demcz_derive_array).  The uploaded arrays are not kept.  Not in the reference."""
-    from .engine import DerivedHistory
+def _program_arrays(chain, log_obj, program):
+    """The column-major arrays of a history as the _array entry points of a per-draw program take them, checked against it."""
     chain = _lib.f64(chain, "F")
     N, d, G = chain.shape
     if program.d != d:
@@ -241,11 +238,47 @@ def derive_chain(chain, log_obj, program, device_id=0):
         lo = _lib.f64(log_obj, "F")
         if lo.shape != (N, G):
             raise ValueError("log_obj must be Npop x Ngeneration")
+    return chain, lo, N, d, G
+
+
+def derive_chain(chain, log_obj, program, device_id=0):
+    """``program`` (a ``DerivedProgram``) evaluated on every draw of an Npop x Npar x Ngeneration history and its
+    Npop x Ngeneration ``log_obj`` (or None: the program's ``logp`` is NaN) -- a ``DerivedHistory`` on the device, generations
+    1..Ngeneration (demcz_derive_array).  The uploaded arrays are not kept.  Not in the reference."""
+    from .engine import DerivedHistory
+    chain, lo, N, d, G = _program_arrays(chain, log_obj, program)
     src, opts, data, ndata = program._args()
     L = _lib.load()
     out = C.c_void_p()
     _chk(L.demcz_derive_array(device_id, _lib.ptr(chain), _lib.ptr(lo), N, d, G, program.m, src, opts, data, ndata, C.byref(out)))
     return DerivedHistory(L, out, N, program.m, 1, G, program.names)
+
+
+def predict_chain(chain, log_obj, program, seed, chain_id0=0, device_id=0):
+    """``program`` (a ``PredictiveProgram``) at every draw of an Npop x Npar x Ngeneration history (``log_obj`` or None as for
+    ``derive_chain``), the draw of row ``i`` at generation ``g`` with the random stream of (seed, g, chain_id0 + i) -- a
+    ``DerivedHistory`` on the device, generations 1..Ngeneration (demcz_predict_array).  Not in the reference."""
+    from .engine import DerivedHistory
+    chain, lo, N, d, G = _program_arrays(chain, log_obj, program)
+    src, opts, data, ndata = program._args()
+    L = _lib.load()
+    out = C.c_void_p()
+    _chk(L.demcz_predict_array(device_id, _lib.ptr(chain), _lib.ptr(lo), N, d, G, program.m, src, opts, data, ndata,
+                               int(seed) & (2**64 - 1), int(chain_id0), C.byref(out)))
+    return DerivedHistory(L, out, N, program.m, 1, G, program.names, int(chain_id0))
+
+
+def ppc_chain(chain, log_obj, program, seed, chain_id0=0, observed=None, device_id=0):
+    """The posterior predictive check of ``program`` over such a history (demcz_ppc_array): a ``PPC`` record of the counts of its m
+    columns against ``observed`` (m values; None: zeros), of the values ``predict_chain`` would have written.  Not in the reference."""
+    from .engine import _ppc_observed, ppc_record
+    chain, lo, N, d, G = _program_arrays(chain, log_obj, program)
+    obs = _ppc_observed(observed, program.m)
+    src, opts, data, ndata = program._args()
+    counts = np.zeros(3 * program.m, dtype=np.int64)
+    _chk(_lib.load().demcz_ppc_array(device_id, _lib.ptr(chain), _lib.ptr(lo), N, d, G, program.m, src, opts, data, ndata,
+                                     int(seed) & (2**64 - 1), int(chain_id0), _lib.ptr(obs), _lib.ptr(counts, _lib._lp)))
+    return ppc_record(counts, N * G, program.names)
 
 
 def pointwise_chain(chain, program, obs_from=0, obs_to=None, device_id=0):

@@ -492,7 +492,7 @@ int32_t demcz_best_array(int32_t device_id, const double* log_obj, int64_t N, in
  * the statistics are asked for g_from..g_to or any window inside.  It owns its memory, outlives the handle it came from and is
  * freed by demcz_destroy.  It takes demcz_rhat, demcz_rhat_partial, demcz_autocov_sums, demcz_ess, demcz_select_counts,
  * demcz_quantiles, demcz_mean_cov, demcz_get_history with log_obj = NULL, demcz_synchronize, demcz_last_error, demcz_destroy,
- * demcz_derive (a derived history of a derived history; its logp is NaN) and demcz_rank_normalize, demcz_indicator_le,
+ * demcz_derive (a derived history of a derived history; its logp is NaN), demcz_predict, demcz_ppc and demcz_rank_normalize, demcz_indicator_le,
  * demcz_rank_diagnostics, demcz_histogram, demcz_histogram2d, demcz_hdi, demcz_pointwise, demcz_loo_columns, demcz_loo and (a one-column one, as either argument)
  * demcz_bridge_iterate (below).  Every other call that takes a handle returns
  * DEMCZ_ERR_STATE on it, with a message that says so. */
@@ -502,6 +502,51 @@ int32_t demcz_derive(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t m, c
 int32_t demcz_derive_array(int32_t device_id, const double* chain, const double* log_obj /* may be NULL */,
                            int64_t N, int32_t d, int64_t G, int32_t m, const char* source, const char* options,
                            const double* data, int64_t ndata, demcz_handle** derived);
+
+/* Posterior predictive programs (not in the reference): a derive program that is also given random numbers, so that a replicated
+ * data set y_rep ~ p(y | theta), a predictive draw at a new covariate or a posterior predictive p-value is computed where the
+ * history lies.  A predictive program is HIP C++ that defines
+ *     __device__ void demcz_predict(const double* x, double logp, const double* data, int64_t ndata, demcz_rng* rng, double* out);
+ * with x, logp, data, out, DEMCZ_D, DEMCZ_M, the compile options, the limits 1 <= d, m <= 32 and the advice on run-time indices
+ * exactly demcz_derive's, and rng the draw's own random stream, consumed through
+ *     void   demcz_bits(demcz_rng*, uint64_t* r1, uint64_t* r2)   the next 128 bits of the stream
+ *     double demcz_uniform(demcz_rng*)                            in (0, 1)
+ *     double demcz_normal(demcz_rng*)                             standard normal (Box-Muller)
+ *     double demcz_exponential(demcz_rng*)                        -log(uniform)
+ * THE STREAM OF A DRAW (DESIGN.md section 3 has the specification to the bit): the draw of global chain c = chain_id0 + local
+ * chain at generation g owns the Philox4x32-10 stream of key `seed` and subsequence (g << 32) | c.  What a draw is given therefore
+ * depends on (seed, g, c) and on nothing else: not on the window asked for, the launch, how the chains are sharded over handles
+ * or demcz_set_history_origin; a call repeated is the same bits, and a draw may consume as many numbers as it likes.  With the
+ * run's own seed these streams cannot meet the sampler's or the bridge's, whose subsequences are chain numbers below 2^32 while
+ * g >= 1 puts these at 2^32 and above.  Two programs run with one seed are given the same numbers: give them different seeds
+ * where their results must be independent.  seed and chain_id0 are the caller's to give; nothing is read off the handle.  Needs
+ * g_to < 2^32 and 0 <= chain_id0, chain_id0 + N <= 2^32 (DEMCZ_ERR_INVALID_ARGUMENT otherwise).
+ *   demcz_predict_check  compiles the program and needs no device; errors as demcz_derive_check's.
+ *   demcz_predict        the program at every draw of generations g_from..g_to of h's history: a DERIVED HISTORY (see demcz_derive)
+ *                        of m columns.  Range, state, refusals, the voided LIVE slab and the error codes are demcz_derive's; h may
+ *                        be a derived history (its logp is NaN).
+ *   demcz_predict_array  the same from host arrays, generations 1..G.
+ *   demcz_ppc            the same calls of the program, but no history is written: out[k] of every draw is compared with
+ *                        observed[k] (m values; NULL: zeros) and counts[3 k], [3 k + 1], [3 k + 2] return how many draws had
+ *                        out[k] > observed[k], out[k] == observed[k], and out[k] NaN.  A posterior predictive p-value of the
+ *                        statistic T is (gt + eq) / (N w - nan) with out[k] = T(y_rep, theta) and observed[k] = T(y, theta), or
+ *                        with out[k] their difference and observed NULL.  Integer counts: the same bits however the window is
+ *                        cut or the chains are sharded, and the counts of shards add.  A NaN observed[k] counts every draw in
+ *                        neither gt nor eq.  Nothing is leaked on any failure.
+ *   demcz_ppc_array      the same from host arrays, generations 1..G. */
+int32_t demcz_predict_check(int32_t d, int32_t m, const char* source, const char* options);
+int32_t demcz_predict(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t m, const char* source, const char* options,
+                      const double* data, int64_t ndata, uint64_t seed, int64_t chain_id0, demcz_handle** derived);
+int32_t demcz_predict_array(int32_t device_id, const double* chain, const double* log_obj /* may be NULL */,
+                            int64_t N, int32_t d, int64_t G, int32_t m, const char* source, const char* options,
+                            const double* data, int64_t ndata, uint64_t seed, int64_t chain_id0, demcz_handle** derived);
+int32_t demcz_ppc(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t m, const char* source, const char* options,
+                  const double* data, int64_t ndata, uint64_t seed, int64_t chain_id0, const double* observed /* m, or NULL: zeros */,
+                  int64_t* counts /* 3 m: gt, eq, nan of each column */);
+int32_t demcz_ppc_array(int32_t device_id, const double* chain, const double* log_obj /* may be NULL */,
+                        int64_t N, int32_t d, int64_t G, int32_t m, const char* source, const char* options,
+                        const double* data, int64_t ndata, uint64_t seed, int64_t chain_id0, const double* observed /* m, or NULL: zeros */,
+                        int64_t* counts /* 3 m */);
 
 /* Rank-normalised diagnostics (Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021; not in the reference): rank-normalised split
  * R-hat, bulk-ESS and tail-ESS, from the exact average rank of every draw among all S = N w draws of its parameter (DESIGN.md

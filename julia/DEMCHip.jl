@@ -449,6 +449,64 @@ function derive_chain(chain::Array{Float64,3}, log_obj::Union{Array{Float64,2},N
                              join(p.options, " "), isempty(p.data) ? C_NULL : pointer(p.data), length(p.data), out))
     out[]
 end
+# ---- posterior predictive programs: a derive program that is given the draw's own random stream (include/demcz.h: demcz_predict)
+# `source` defines
+#     __device__ void demcz_predict(const double* x, double logp, const double* data, int64_t ndata, demcz_rng* rng, double* out)
+# and draws with demcz_uniform(rng), demcz_normal(rng), demcz_exponential(rng), demcz_bits(rng, &r1, &r2).  The stream of the draw of
+# global chain c at generation g is keyed by (seed, g, c) and by nothing else; `seed` and `chain_id0` are the caller's to give (the
+# run's own seed is safe: these streams cannot meet the sampler's).  Two programs run with one seed share their random numbers.
+struct PredictiveProgram
+    source::String; d::Int; m::Int; data::Vector{Float64}; options::Vector{String}; names::Vector{String}
+end
+PredictiveProgram(source, d, m; data=Float64[], options=String[], names=String[]) =
+    PredictiveProgram(String(source), Int(d), Int(m), Vector{Float64}(data), Vector{String}(options), Vector{String}(names))
+check(p::PredictiveProgram) = chk(ccall((:demcz_predict_check, libdemcz), Int32, (Int32, Int32, Cstring, Cstring),
+                                        Int32(p.d), Int32(p.m), p.source, join(p.options, " ")))
+# predict(h, p, g_from, g_to; seed, chain_id0) -> the handle of a derived history (N x m x w), as derive's
+function predict(h, p::PredictiveProgram, g_from, g_to; seed, chain_id0=0)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve p chk(ccall((:demcz_predict, libdemcz), Int32,
+                             (Ptr{Cvoid}, Int64, Int64, Int32, Cstring, Cstring, Ptr{Float64}, Int64, UInt64, Int64, Ref{Ptr{Cvoid}}),
+                             h, g_from, g_to, Int32(p.m), p.source, join(p.options, " "),
+                             isempty(p.data) ? C_NULL : pointer(p.data), length(p.data), UInt64(seed), chain_id0, out), h)
+    out[]
+end
+function predict_chain(chain::Array{Float64,3}, log_obj::Union{Array{Float64,2},Nothing}, p::PredictiveProgram; seed, chain_id0=0, device_id=0)
+    Npop, Npar, Ngeneration = size(chain)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve p chk(ccall((:demcz_predict_array, libdemcz), Int32,
+                             (Int32, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Int64, Int32, Cstring, Cstring, Ptr{Float64}, Int64, UInt64, Int64, Ref{Ptr{Cvoid}}),
+                             device_id, chain, log_obj === nothing ? C_NULL : log_obj, Npop, Npar, Ngeneration, Int32(p.m), p.source,
+                             join(p.options, " "), isempty(p.data) ? C_NULL : pointer(p.data), length(p.data), UInt64(seed), chain_id0, out))
+    out[]
+end
+# the posterior predictive check: per column k the draws with out[k] > observed[k], == observed[k] and NaN (observed: m values, or
+# nothing for zeros); p_value = (gt + eq) / (total - nan), mid_p = (gt + eq / 2) / (total - nan)
+function ppc_record(counts, total)
+    gt, eq, nan = counts[1:3:end], counts[2:3:end], counts[3:3:end]
+    (gt=gt, eq=eq, nan=nan, total=total, p_value=(gt .+ eq) ./ (total .- nan), mid_p=(gt .+ eq ./ 2) ./ (total .- nan))
+end
+function ppc(h, p::PredictiveProgram, N, g_from, g_to; seed, chain_id0=0, observed=nothing)
+    counts = zeros(Int64, 3 * p.m)
+    obs = observed === nothing ? Float64[] : Vector{Float64}(observed)
+    GC.@preserve p obs chk(ccall((:demcz_ppc, libdemcz), Int32,
+                                 (Ptr{Cvoid}, Int64, Int64, Int32, Cstring, Cstring, Ptr{Float64}, Int64, UInt64, Int64, Ptr{Float64}, Ptr{Int64}),
+                                 h, g_from, g_to, Int32(p.m), p.source, join(p.options, " "),
+                                 isempty(p.data) ? C_NULL : pointer(p.data), length(p.data), UInt64(seed), chain_id0,
+                                 isempty(obs) ? C_NULL : pointer(obs), counts), h)
+    ppc_record(counts, N * (g_to - g_from + 1))
+end
+function ppc_chain(chain::Array{Float64,3}, log_obj::Union{Array{Float64,2},Nothing}, p::PredictiveProgram; seed, chain_id0=0, observed=nothing, device_id=0)
+    Npop, Npar, Ngeneration = size(chain)
+    counts = zeros(Int64, 3 * p.m)
+    obs = observed === nothing ? Float64[] : Vector{Float64}(observed)
+    GC.@preserve p obs chk(ccall((:demcz_ppc_array, libdemcz), Int32,
+                                 (Int32, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Int64, Int32, Cstring, Cstring, Ptr{Float64}, Int64, UInt64, Int64, Ptr{Float64}, Ptr{Int64}),
+                                 device_id, chain, log_obj === nothing ? C_NULL : log_obj, Npop, Npar, Ngeneration, Int32(p.m), p.source,
+                                 join(p.options, " "), isempty(p.data) ? C_NULL : pointer(p.data), length(p.data), UInt64(seed), chain_id0,
+                                 isempty(obs) ? C_NULL : pointer(obs), counts))
+    ppc_record(counts, Npop * Ngeneration)
+end
 # the values of a derived history: N x m x w
 function derived_values(hd, N, m, g_from, g_to)
     v = zeros(N, m, g_to - g_from + 1)
