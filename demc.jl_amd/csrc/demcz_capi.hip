@@ -3824,7 +3824,6 @@ extern "C" int32_t demcz_propose(demcz_handle* h, int64_t g, int32_t ib, double 
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
     const int64_t N = h->cfg.N;
     const int d = h->cfg.d;
-    h->gen_open = true;
     int64_t off = 0;
     for (int t = 0; t < ib; ++t) off += blockstep_nblk(h->block_offsets[t + 1] - h->block_offsets[t]);
     WindowParams P{};
@@ -3860,6 +3859,7 @@ extern "C" int32_t demcz_propose(demcz_handle* h, int64_t g, int32_t ib, double 
         HIPCHK(h, hipMemcpyAsync(Xprop, h->dXprop, (size_t)N * d * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         SYNCCHK(h, h->stream);
     }
+    h->gen_open = true;                           // (only a proposal that was made opens a generation: a refused call leaves none)
     h->proposal_pending = true;
     return DEMCZ_OK;
 }

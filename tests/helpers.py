@@ -121,14 +121,18 @@ def py_fma(a, b, c):
         return math.inf if s > 0 else -math.inf
 
 
-def oracle_sample_logobj(O, logobj, Z0, N, K, G, blocks, eps, gamma, seed, temperature=None, X0=None, lp0=None, g_from=1):
+def oracle_sample_logobj(O, logobj, Z0, N, K, G, blocks, eps, gamma, seed, temperature=None, X0=None, lp0=None, g_from=1,
+                         with_xprop=False, rng_offset=0):
     """The oracle's generation loop (synchronous schedule) around a Python log-density: of every block-step only what does not
     depend on the target is taken from the oracle (O.block_step on a problem with a built-in target: the proposal and log u, the
     draw contract's bits); logobj is evaluated on a list of Python floats, and the accept test log u < (lp' - lp) [/ T] and the
     per-generation count (lp_after - lp_before) != 0 are made in NumPy float64, so that +-inf and NaN behave as IEEE says.
     Returns oracle_sample's dict, and `proposed` (N, G, blocks): the log-density of every proposal, accepted or not.
     X0, lp0, g_from: carry a run on -- Z0 is then the archive as it stands, X0 / lp0 the chains, and the G generations are
-    g_from .. g_from + G - 1 (temperature[0] is generation g_from's)."""
+    g_from .. g_from + G - 1 (temperature[0] is generation g_from's).
+    with_xprop: also `xprop` (N, d, G, blocks): every proposal itself, accepted or not -- all d coordinates, those outside the
+    block being the bits of the state the block-step started from.  rng_offset: generations a previous run already drew from
+    every chain's stream (oracle_sample's)."""
     Z0 = np.asarray(Z0, dtype=np.float64)
     M0, d = Z0.shape
     Mcap = M0 + -(-N * G // K) + (N if g_from > 1 else 0)
@@ -144,14 +148,17 @@ def oracle_sample_logobj(O, logobj, Z0, N, K, G, blocks, eps, gamma, seed, tempe
     lobj = np.zeros((N, G), order="F")
     changed = np.zeros(G, dtype=np.int64)
     proposed = np.zeros((N, G, len(blocks)))
+    xprop = np.zeros((N, d, G, len(blocks)), order="F") if with_xprop else None
     with np.errstate(all="ignore"):
         for g in range(g_from, g_from + G):
             T = None if temperature is None else np.float64(temperature[g - g_from])
             for c in range(N):
                 x, lpc = X[c].copy(), lp[c]
                 for ib in range(len(blocks)):
-                    s = O.block_step(prob, Z, M, c, g, ib, gamma, x, 0.0)
+                    s = O.block_step(prob, Z, M, c, g + rng_offset, ib, gamma, x, 0.0)
                     lpp = proposed[c, g - g_from, ib] = f(s["xprop"])
+                    if with_xprop:
+                        xprop[c, :, g - g_from, ib] = s["xprop"]
                     dlt = lpp - lpc
                     if T is not None:
                         dlt = dlt / T
@@ -164,4 +171,7 @@ def oracle_sample_logobj(O, logobj, Z0, N, K, G, blocks, eps, gamma, seed, tempe
             if g % K == 0:
                 Z[M:M + N] = X
                 M += N
-    return dict(chain=chain, log_obj=lobj, X=X, logp=lp, Z=Z[:M].copy(), M=M, changed=changed, prob=prob, proposed=proposed)
+    out = dict(chain=chain, log_obj=lobj, X=X, logp=lp, Z=Z[:M].copy(), M=M, changed=changed, prob=prob, proposed=proposed)
+    if with_xprop:
+        out["xprop"] = xprop
+    return out
