@@ -63,6 +63,7 @@ SYMBOLS = [
     "demcz_bridge_proposal_program", "demcz_bridge_iterate", "demcz_bridge", "demcz_bridge_array",
     "demcz_histogram_edges", "demcz_histogram", "demcz_histogram_array", "demcz_histogram2d", "demcz_histogram2d_array",
     "demcz_hdi_steps", "demcz_hdi", "demcz_hdi_array",
+    "demcz_set_crossover", "demcz_get_crossover",
 ]
 
 
@@ -92,11 +93,12 @@ def sources() -> list:
     """The library's translation units: the C ABI with most kernels (demcz_capi.hip), the eight units that instantiate
     window_kernel_pw for every dimension from 6 to 32 (demcz_pw_inst_<g>.hip, csrc/demcz_pw_dispatch.h), the two with the
     sixteen-lane regression kernels for every dimension from 2 to 28 (demcz_mlr_inst_<g>.hip, csrc/demcz_mlr_dispatch.h), the one
-    with the snooker generation's kernels (demcz_snooker_inst.hip, csrc/demcz_kernels_snooker.h), the one with the bridge-sampling
+    with the snooker generation's kernels (demcz_snooker_inst.hip, csrc/demcz_kernels_snooker.h), the one with the crossover
+    generation's (demcz_crossover_inst.hip, csrc/demcz_kernels_crossover.h), the one with the bridge-sampling
     kernels for every dimension from 1 to 32 (demcz_bridge_inst.hip, csrc/demcz_kernels_bridge.h) and the host code of program targets (demcz_program.hip: hipRTC, the kernel headers embedded as text)."""
     csrc = PKG_DIR / "csrc"
     return ([csrc / "demcz_capi.hip"] + sorted(csrc.glob("demcz_pw_inst_*.hip")) + sorted(csrc.glob("demcz_mlr_inst_*.hip"))
-            + [csrc / "demcz_snooker_inst.hip", csrc / "demcz_bridge_inst.hip", csrc / "demcz_program.hip"])
+            + [csrc / "demcz_snooker_inst.hip", csrc / "demcz_crossover_inst.hip", csrc / "demcz_bridge_inst.hip", csrc / "demcz_program.hip"])
 
 
 def build_command(out: Path = LIB_PATH) -> list:
@@ -181,6 +183,8 @@ def load():
     L.demcz_set_rng_offset.argtypes = [C.c_void_p, C.c_int64]
     L.demcz_set_snooker.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_double]
     L.demcz_get_snooker.argtypes = [C.c_void_p, _ip, _dp, _dp, _lp]
+    L.demcz_set_crossover.argtypes = [C.c_void_p, C.c_int32, _ip, C.c_int32]
+    L.demcz_get_crossover.argtypes = [C.c_void_p, _ip, _ip, _ip, _lp, _lp]
     L.demcz_set_append_lag.argtypes = [C.c_void_p, C.c_int32]
     L.demcz_rhat_array.argtypes = [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int64, _dp]
     L.demcz_autocov_sums.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _dp]

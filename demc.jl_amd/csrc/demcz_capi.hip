@@ -20,6 +20,7 @@
 #include "demcz_kernels_ps2.h"
 #include "demcz_kernels_ps2d.h"
 #include "demcz_kernels_snooker.h"
+#include "demcz_kernels_crossover.h"
 #include "demcz_pw_dispatch.h"
 #include "demcz_mlr_dispatch.h"
 #include "demcz_program.h"
@@ -169,7 +170,7 @@ enum SplitKind {
 // One window launch's kernel, as window_kernel_of() resolves it: everything that launches, sizes, counts or names a window kernel
 // reads this description and decides nothing about the instantiation itself.
 enum KernelArm { ARM_ONE_LANE, ARM_ML, ARM_ML_COOP, ARM_MLB, ARM_LR16, ARM_PC8, ARM_ML_REC, ARM_MLB_REC, ARM_LR16_REC, ARM_LR8S,
-                 ARM_PS, ARM_PS2, ARM_PS2D, ARM_PW, ARM_PROGRAM_WAVE, ARM_SNOOKER };
+                 ARM_PS, ARM_PS2, ARM_PS2D, ARM_PW, ARM_PROGRAM_WAVE, ARM_SNOOKER, ARM_CROSSOVER };
 struct WindowKernel {
     const void* fn = nullptr;       // host symbol of a built-in kernel ...
     hipFunction_t mod = nullptr;    // ... or the function of the program's module; neither: not built (or no program yet)
@@ -195,6 +196,7 @@ struct LaunchFacts {
     bool coop = false;        // ml_coop(h)
     bool lr16 = false;        // uses_lr16(h)
     bool snooker = false;     // the launch is one snooker generation (LaunchPlan::snooker)
+    bool crossover = false;   // the launch's generations are crossover generations (demcz_set_crossover; not a snooker launch)
 };
 
 // A replica group of one process (demcz_peer_group): R handles on one device, each with its own archive replica and shard of
@@ -434,6 +436,13 @@ struct demcz_handle {
     double snooker_lo = 1.2, snooker_hi = 2.2;
     int64_t snooker_steps = 0;        // snooker launches made in the handle's life
     bool snooker_now = false;         // the launch being prepared is one (LaunchPlan::snooker)
+    // crossover generations (demcz_set_crossover; one-lane handles with one block): every generation that is not a snooker
+    // generation is one crossover step of every chain; cr_ncr == 0: off.  While it is on, S is crossover_stride(d, cr_delta_max)
+    // (S_plain keeps the stride of the block structure).
+    int32_t cr_ncr = 0, cr_delta_max = 1;
+    int32_t cr_weights[CR_MAX_CLASSES] = {1, 1, 1, 1, 1, 1, 1, 1};
+    unsigned long long* d_cr_counts = nullptr;      // [workgroup][8][2], zeroed when crossover is switched on
+    int64_t S_plain = 0;
 };
 
 #define HIPCHK(h, expr)                                                                          \
@@ -728,6 +737,7 @@ static void free_all(demcz_handle* h)
     for (hipStream_t st : {h->stream, h->prod_stream, h->diag_stream, h->comm_stream, h->hs_stream})
         if (st && hipStreamQuery(st) != hipSuccess) drained = false;
     if (h->d_acc) (void)dev_free(h->cfg.device_id, h->d_acc);
+    if (h->d_cr_counts) (void)dev_free(h->cfg.device_id, h->d_cr_counts);
     if (h->d_err_all) (void)dev_free(h->cfg.device_id, h->d_err_all);
     if (h->archive_fine) { if (h->dZ) (void)hipFree(h->dZ); h->dZ = nullptr; }     // (an allocation of its own: demcz_comm_init)
     if (h->pooled_dev) {               // (the two big ones)
@@ -897,6 +907,7 @@ extern "C" int32_t demcz_create(demcz_handle** out, const demcz_config* cfg)
         for (int t = a; t < b; ++t) h->slot_of[(size_t)ib * d + h->block_indices[t]] = t - a;
         h->S += blockstep_nblk(b - a);
     }
+    h->S_plain = h->S;
     h->full_block = (cfg->Nblocks == 1 && h->block_offsets[1] == d);
     if (h->full_block)
         for (int p = 0; p < d; ++p) h->full_block = h->full_block && (h->block_indices[p] == p);
@@ -1468,6 +1479,21 @@ static void allow_dynamic_lds(int device, const WindowKernel& k)
     done.push_back(key);
 }
 
+// what a crossover launch is told beside WindowParams
+static CrossoverParams crossover_params(const demcz_handle* h)
+{
+    CrossoverParams cp{};
+    cp.ncr = h->cr_ncr;
+    cp.delta_max = h->cr_delta_max;
+    uint32_t sum = 0;
+    for (int k = 0; k < CR_MAX_CLASSES; ++k) {
+        if (k < h->cr_ncr) sum += (uint32_t)h->cr_weights[k];
+        cp.cum[k] = sum;
+    }
+    cp.counts = h->d_cr_counts;
+    return cp;
+}
+
 // the one launch of a window kernel: each takes the launch's WindowParams by value
 static int32_t launch_kernel(demcz_handle* h, const WindowKernel& k, int64_t blocks, const WindowParams& P)
 {
@@ -1476,7 +1502,8 @@ static int32_t launch_kernel(demcz_handle* h, const WindowKernel& k, int64_t blo
     if (!k.fn && !k.mod) return fail(h, DEMCZ_ERR_STATE, "window launch: target / dimension not built for this handle's layout");
     // (a snooker launch has a second argument; a kernel that takes one never looks at the other)
     SnookerParams sp{h->snooker_lo, h->snooker_hi};
-    void* args[] = {const_cast<WindowParams*>(&P), &sp};
+    CrossoverParams cp = crossover_params(h);
+    void* args[] = {const_cast<WindowParams*>(&P), k.arm == ARM_CROSSOVER ? (void*)&cp : (void*)&sp};
     if (k.mod) {
         HIPCHK(h, hipModuleLaunchKernel(k.mod, (unsigned)blocks, 1, 1, (unsigned)k.threads, 1, 1, (unsigned)k.dyn_lds, h->stream, args, nullptr));
     } else {
@@ -1835,6 +1862,7 @@ static LaunchFacts launch_facts(const demcz_handle* h, const WindowParams* P, bo
     f.temper = P && P->temperature != nullptr;
     f.dual = h->dual_now;
     f.snooker = h->snooker_now;
+    f.crossover = h->cr_ncr > 0 && !h->snooker_now;
     if (h->lanes == DEMCZ_LAYOUT_SPLIT) {
         if (h->split_kind == SPLIT_WAVE && !h->prog_wave) {
             f.ps2 = P && ps2_applicable(h, *P);
@@ -1864,6 +1892,16 @@ static WindowKernel window_kernel_of(const demcz_handle* h, const LaunchFacts& f
         k.waves = 1;
         if (tk == DEMCZ_TARGET_PROGRAM) { if (h->prog_ready) k.mod = h->prog.snooker; }
         else k.fn = snooker_kernel_fn(tk, d, &k.dyn_lds);
+        return k;
+    }
+    if (f.crossover) {
+        // crossover generations of a one-lane handle with one block (demcz_set_crossover admits no other): window_kernel_cr<TARGET, D>
+        // where the one-lane dispatch specialises the dimension, window_kernel_cr_generic<TARGET> otherwise, or the program's own
+        k.arm = ARM_CROSSOVER;
+        k.threads = WINDOW_BS;
+        k.waves = 1;
+        if (tk == DEMCZ_TARGET_PROGRAM) { if (h->prog_ready) k.mod = h->prog.crossover; }
+        else k.fn = crossover_kernel_fn(tk, d, &k.dyn_lds);
         return k;
     }
     if (h->lanes == DEMCZ_LAYOUT_SPLIT) {
@@ -2741,6 +2779,9 @@ static int32_t run_call(demcz_handle* h, int64_t g_from, int64_t g_to, double ga
         if (h->external_append && nb == 1 && (g_to % K) != 0)
             return fail(h, DEMCZ_ERR_STATE, "demcz_run: with external append the K boundary must be the last generation of the call");
     }
+    if (h->cr_ncr > 0 && h->M < 2)
+        return fail(h, DEMCZ_ERR_STATE, "demcz_run: crossover generations draw pairs of distinct archive rows: the archive has fewer than two "
+                                        "(demcz_set_crossover with ncr = 0 switches them off)");
     if (h->snooker_every > 0 && h->M < 3)
         return fail(h, DEMCZ_ERR_STATE, "demcz_run: snooker generations draw three distinct archive rows: the archive has fewer than three "
                                         "(demcz_set_snooker with every = 0 switches them off)");
@@ -3817,6 +3858,7 @@ extern "C" int32_t demcz_propose(demcz_handle* h, int64_t g, int32_t ib, double 
 {
     NOT_DERIVED(h);
     if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
+    if (h->cr_ncr > 0) return fail(h, DEMCZ_ERR_STATE, "demcz_propose: the handle has crossover generations (demcz_set_crossover): the closure mode has no crossover");
     if (h->cfg.target_kind != DEMCZ_TARGET_HOST_CALLBACK) return fail(h, DEMCZ_ERR_STATE, "demcz_propose: handle was not created with DEMCZ_TARGET_HOST_CALLBACK");
     if (!h->has_state) return fail(h, DEMCZ_ERR_STATE, "demcz_propose: call demcz_set_state first");
     if (g < 1 || ib < 0 || ib >= h->cfg.Nblocks) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_propose: bad generation or block");
@@ -3998,6 +4040,7 @@ extern "C" int32_t demcz_peer_group(demcz_handle** handles, int32_t R)
         for (int q = 0; q < r; ++q) if (handles[q] == m) return fail(m, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_peer_group: a handle appears twice");
         if (m->comm || m->peer_mode != 0) return fail(m, DEMCZ_ERR_STATE, "demcz_peer_group: handle is already sharded");
         if (m->snooker_every > 0) return fail(m, DEMCZ_ERR_STATE, "demcz_peer_group: a handle with snooker generations (demcz_set_snooker) does not join a replica group");
+        if (m->cr_ncr > 0) return fail(m, DEMCZ_ERR_STATE, "demcz_peer_group: a handle with crossover generations (demcz_set_crossover) does not join a replica group");
         if (m->prog_wave)
             return fail(m, DEMCZ_ERR_STATE, "demcz_peer_group: a program target on DEMCZ_LAYOUT_PROGRAM_WAVE does not join a replica group (sharded "
                                             "in-launch hand-off is not built for programs): shard it from the host or use the one-lane layout");
@@ -4465,6 +4508,79 @@ extern "C" int32_t demcz_get_snooker(const demcz_handle* h, int32_t* every, doub
     if (gamma_lo) *gamma_lo = h->snooker_lo;
     if (gamma_hi) *gamma_hi = h->snooker_hi;
     if (steps_launched) *steps_launched = h->snooker_steps;
+    return DEMCZ_OK;
+}
+
+// Crossover generations.  The choices differ from chain to chain and are made inside the kernel;
+// the host knows only that the handle's generations are crossover generations (window_kernel_of: ARM_CROSSOVER) and that a
+// generation takes crossover_stride(d, delta_max) Philox blocks.
+extern "C" int32_t demcz_set_crossover(demcz_handle* h, int32_t ncr, const int32_t* weights, int32_t delta_max)
+{
+    NOT_DERIVED(h);
+    if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
+    DEADCHK(h);
+    if (ncr < 0 || ncr > CR_MAX_CLASSES) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_crossover: ncr must be 0 (off) or 1 ... 8");
+    if (delta_max < 1 || delta_max > CR_MAX_PAIRS) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_crossover: delta_max must be 1, 2 or 3");
+    int64_t W = 0;
+    for (int k = 0; k < ncr; ++k) {
+        const int32_t wk = weights ? weights[k] : 1;
+        if (wk < 0) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_crossover: a weight is negative");
+        W += wk;
+    }
+    if (ncr > 0 && (W < 1 || W >= (int64_t)1 << 31))
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_crossover: the weights must sum to a W with 1 <= W < 2^31");
+    if (h->cfg.target_kind == DEMCZ_TARGET_HOST_CALLBACK)
+        return fail(h, DEMCZ_ERR_STATE, "demcz_set_crossover: a host-callback handle proposes through demcz_propose: the closure mode has no crossover");
+    if (h->peer_mode != 0)
+        return fail(h, DEMCZ_ERR_STATE, "demcz_set_crossover: the handle is in a replica group or has IPC peers: crossover is not built for them");
+    if (h->launches > 0 || h->g_done != h->g0)
+        return fail(h, DEMCZ_ERR_STATE, "demcz_set_crossover: the handle has already run a generation: the stride of the Philox streams cannot "
+                                        "change in mid-life (set crossover on the fresh handle, before demcz_set_rng_offset and demcz_run)");
+    if (h->cfg.d < 2) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_crossover: crossover needs d >= 2");
+    if (!h->full_block)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_crossover: the handle has more than one block (or not the block 0 .. d-1 in order): "
+                                                   "crossover draws its own subsets and is not built for blocked handles");
+    if (h->lanes != 1)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_crossover: the handle was not created on the one-lane layout (create it with "
+                                                   "lanes_per_chain = 1): the other layouts draw ahead of the chains");
+    HIPCHK(h, hipSetDevice(h->cfg.device_id));
+    if (ncr > 0) {
+        const size_t n = (size_t)((h->cfg.N + WINDOW_BS - 1) / WINDOW_BS) * 2 * CR_MAX_CLASSES;
+        if (!h->d_cr_counts) HIPCHK(h, dev_malloc(h->cfg.device_id, (void**)&h->d_cr_counts, n * sizeof(unsigned long long)));
+        HIPCHK(h, hipMemsetAsync(h->d_cr_counts, 0, n * sizeof(unsigned long long), h->stream));
+    }
+    h->cr_ncr = ncr;
+    h->cr_delta_max = delta_max;
+    for (int k = 0; k < CR_MAX_CLASSES; ++k) h->cr_weights[k] = (k < ncr) ? (weights ? weights[k] : 1) : 1;
+    h->S = ncr > 0 ? crossover_stride(h->cfg.d, delta_max) : h->S_plain;
+    return DEMCZ_OK;
+}
+
+extern "C" int32_t demcz_get_crossover(const demcz_handle* h, int32_t* ncr, int32_t* weights, int32_t* delta_max, int64_t* tried, int64_t* accepted)
+{
+    NOT_DERIVED(h);
+    if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
+    if (ncr) *ncr = h->cr_ncr;
+    if (delta_max) *delta_max = h->cr_delta_max;
+    if (weights) for (int k = 0; k < h->cr_ncr; ++k) weights[k] = h->cr_weights[k];
+    if (tried || accepted) {
+        demcz_handle* hm = const_cast<demcz_handle*>(h);
+        int64_t sums[2 * CR_MAX_CLASSES] = {0};
+        if (h->d_cr_counts && h->cr_ncr > 0) {
+            // the workgroups' slots, summed on the host: a few kilobytes, on request only
+            HIPCHK(hm, hipSetDevice(h->cfg.device_id));
+            const size_t nwg = (size_t)((h->cfg.N + WINDOW_BS - 1) / WINDOW_BS);
+            std::vector<unsigned long long> host(nwg * 2 * CR_MAX_CLASSES);
+            HIPCHK(hm, hipMemcpyAsync(host.data(), h->d_cr_counts, host.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hm, hipStreamSynchronize(h->stream));
+            for (size_t w = 0; w < nwg; ++w)
+                for (int i = 0; i < 2 * CR_MAX_CLASSES; ++i) sums[i] += (int64_t)host[w * 2 * CR_MAX_CLASSES + i];
+        }
+        for (int k = 0; k < CR_MAX_CLASSES; ++k) {
+            if (tried) tried[k] = sums[2 * k];
+            if (accepted) accepted[k] = sums[2 * k + 1];
+        }
+    }
     return DEMCZ_OK;
 }
 
@@ -6477,6 +6593,11 @@ extern "C" int32_t demcz_debug_kernel_name(const demcz_handle* h, char* buf, int
         if (h->cfg.target_kind == DEMCZ_TARGET_PROGRAM) snprintf(tmp, sizeof tmp, "snooker_kernel<%d, %d> (program)", (int)TARGET_PROGRAM, d);
         else if (k.dyn_lds) snprintf(tmp, sizeof tmp, "snooker_kernel_generic<%s>", tg);
         else snprintf(tmp, sizeof tmp, "snooker_kernel<%s, %d>", tg, d);
+        break;
+    case ARM_CROSSOVER:
+        if (h->cfg.target_kind == DEMCZ_TARGET_PROGRAM) snprintf(tmp, sizeof tmp, "window_kernel_cr<%d, %d> (program)", (int)TARGET_PROGRAM, d);
+        else if (k.dyn_lds) snprintf(tmp, sizeof tmp, "window_kernel_cr_generic<%s>", tg);
+        else snprintf(tmp, sizeof tmp, "window_kernel_cr<%s, %d>", tg, d);
         break;
     case ARM_ONE_LANE:
         // Known misreport: a dimension with no specialisation launches window_kernel_generic<TARGET> and is still named

@@ -34,6 +34,7 @@ struct Code {
     std::string window_full;      // window_kernel<TARGET_PROGRAM, d, true>: one block covering 0..d-1 in order
     std::string window_blocks;    // window_kernel<TARGET_PROGRAM, d, false>: blocks from the CSR tables
     std::string snooker;          // snooker_kernel<TARGET_PROGRAM, d> (demcz_kernels_snooker.h): one-lane unit only
+    std::string crossover;        // window_kernel_cr<TARGET_PROGRAM, d> (demcz_kernels_crossover.h): one-lane unit only
     std::string logp;             // logp_kernel<TARGET_PROGRAM>: the initial log_objcurrent (both units)
     std::string wave[2][2];       // UNIT_WAVE: window_kernel_ps / _pw<TARGET_PROGRAM, d, LIVE, TEMPER>, [LIVE][TEMPER] (the one-lane
                                   // kernels are not in that unit, and these not in the one-lane unit)
@@ -48,7 +49,7 @@ struct Code {
 // A code object loaded on one device (kept until the process exits).
 struct Module {
     hipModule_t module = nullptr;
-    hipFunction_t window_full = nullptr, window_blocks = nullptr, snooker = nullptr, logp = nullptr;
+    hipFunction_t window_full = nullptr, window_blocks = nullptr, snooker = nullptr, crossover = nullptr, logp = nullptr;
     hipFunction_t wave[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
     hipFunction_t derive = nullptr;   // (UNIT_POINTWISE: pointwise_kernel; UNIT_BRIDGE: bridge_proposal_program_kernel; UNIT_PREDICT: predict_kernel)
     hipFunction_t ppc = nullptr;      // UNIT_PREDICT: ppc_kernel

@@ -7,7 +7,9 @@
 //     the user's source                      (#line 1 "program": compiler messages carry the user's own line numbers)
 //     #include "demcz_kernels.h"             (its text and demcz_device.h's are embedded into this library at build time)
 //     #include "demcz_kernels_snooker.h"     (the snooker generation's kernel: a program that cannot be built for it fails here)
-//     explicit instantiations of window_kernel<TARGET_PROGRAM, DEMCZ_D, true / false>, snooker_kernel<TARGET_PROGRAM, DEMCZ_D>
+//     #include "demcz_kernels_crossover.h"   (the crossover generation's kernel, in the same way)
+//     explicit instantiations of window_kernel<TARGET_PROGRAM, DEMCZ_D, true / false>, snooker_kernel<TARGET_PROGRAM, DEMCZ_D>,
+//     window_kernel_cr<TARGET_PROGRAM, DEMCZ_D>
 //     and logp_kernel<TARGET_PROGRAM>
 // The wave unit (UNIT_WAVE, handles created with DEMCZ_LAYOUT_PROGRAM_WAVE; composed and compiled only for them, cached under a
 // key of its own) has the same head, then
@@ -65,6 +67,9 @@ const char k_kernels_h[] = {
     , 0};
 const char k_snooker_h[] = {
 #embed "demcz_kernels_snooker.h"
+    , 0};
+const char k_crossover_h[] = {
+#embed "demcz_kernels_crossover.h"
     , 0};
 // the wave unit's headers
 const char k_rec_h[] = {
@@ -171,12 +176,13 @@ std::string compose(int d, int m, const std::string& source, int unit)
     s << "#define DEMCZ_D " << d << "\n#define DEMCZ_PROGRAM_TARGET\n#define DEMCZ_NO_AUX_KERNELS\n"
       << "#include <hip/hip_runtime.h>\n#include <stdint.h>\n" << k_math_macros
       << "#line 1 \"program\"\n" << source << "\n"
-      << "#line 1 \"demcz_program_unit\"\n#include \"demcz_kernels.h\"\n#include \"demcz_kernels_snooker.h\"\n"
+      << "#line 1 \"demcz_program_unit\"\n#include \"demcz_kernels.h\"\n#include \"demcz_kernels_snooker.h\"\n#include \"demcz_kernels_crossover.h\"\n"
       << "template __global__ void demcz::window_kernel<demcz::TARGET_PROGRAM, DEMCZ_D, true>(const demcz::WindowParams);\n"
       << "template __global__ void demcz::window_kernel<demcz::TARGET_PROGRAM, DEMCZ_D, false>(const demcz::WindowParams);\n"
       << "template __global__ void demcz::snooker_kernel<demcz::TARGET_PROGRAM, DEMCZ_D>(const demcz::WindowParams, const demcz::SnookerParams);\n"
       << "template __global__ void demcz::logp_kernel<demcz::TARGET_PROGRAM>(demcz::TargetParams, int, const double*, int64_t, "
          "int64_t, double*);\n";
+    s << "template __global__ void demcz::window_kernel_cr<demcz::TARGET_PROGRAM, DEMCZ_D>(const demcz::WindowParams, const demcz::CrossoverParams);\n";
     return s.str();
 }
 
@@ -250,8 +256,8 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
                            "demcz_kernels_pc.h", "demcz_kernels_ps.h", "demcz_kernels_pw.h"};
     const bool pointwise = unit == demcz_prog::UNIT_POINTWISE, bridge = unit == demcz_prog::UNIT_BRIDGE, predict = unit == demcz_prog::UNIT_PREDICT;
     const bool wave = unit == demcz_prog::UNIT_WAVE, derive = unit == demcz_prog::UNIT_DERIVE || pointwise || bridge || predict;   // (derive: a streaming unit)
-    const char* lane_headers[] = {k_device_h, k_kernels_h, k_snooker_h};
-    const char* lane_names[] = {"demcz_device.h", "demcz_kernels.h", "demcz_kernels_snooker.h"};
+    const char* lane_headers[] = {k_device_h, k_kernels_h, k_snooker_h, k_crossover_h};
+    const char* lane_names[] = {"demcz_device.h", "demcz_kernels.h", "demcz_kernels_snooker.h", "demcz_kernels_crossover.h"};
     const char* derive_headers[] = {k_derive_h};
     const char* derive_names[] = {"demcz_kernels_derive.h"};
     const char* pointwise_headers[] = {k_derive_h, k_pointwise_h};
@@ -265,7 +271,7 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
     else if (pointwise) RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_unit_pointwise.hip", 2, pointwise_headers, pointwise_names));
     else if (derive) RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_unit_derive.hip", 1, derive_headers, derive_names));
     else if (wave) RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_program_wave_unit.hip", 8, headers, names));
-    else RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_program_unit.hip", 3, lane_headers, lane_names));
+    else RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_program_unit.hip", 4, lane_headers, lane_names));
     struct Guard { hiprtcProgram& p; ~Guard() { if (p) (void)hiprtcDestroyProgram(&p); } } guard{prog};
     const std::string ds = std::to_string(d);
     std::vector<std::string> exprs;
@@ -278,7 +284,8 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
             for (int temper = 0; temper < 2; ++temper)
                 exprs.push_back(kn + ds + (live ? ", true" : ", false") + (temper ? ", true>" : ", false>"));
     } else {
-        exprs = {"&demcz::window_kernel<4, " + ds + ", true>", "&demcz::window_kernel<4, " + ds + ", false>", "&demcz::snooker_kernel<4, " + ds + ">"};
+        exprs = {"&demcz::window_kernel<4, " + ds + ", true>", "&demcz::window_kernel<4, " + ds + ", false>", "&demcz::snooker_kernel<4, " + ds + ">",
+                 "&demcz::window_kernel_cr<4, " + ds + ">"};
     }
     if (!derive) exprs.push_back("&demcz::logp_kernel<4>");
     for (const auto& e : exprs) RTCCHK(hiprtcAddNameExpression(prog, e.c_str()));
@@ -323,7 +330,7 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
     if (predict) lowered = {&code.derive, &code.ppc};
     else if (derive) lowered = {&code.derive};
     else if (wave) lowered = {&code.wave[0][0], &code.wave[0][1], &code.wave[1][0], &code.wave[1][1], &code.logp};
-    else lowered = {&code.window_full, &code.window_blocks, &code.snooker, &code.logp};
+    else lowered = {&code.window_full, &code.window_blocks, &code.snooker, &code.crossover, &code.logp};
     for (size_t i = 0; i < lowered.size(); ++i) {
         const char* nm = nullptr;
         RTCCHK(hiprtcGetLoweredName(prog, exprs[i].c_str(), &nm));
@@ -408,6 +415,7 @@ int32_t get_module(const std::shared_ptr<const Code>& code, int device, Module& 
         if (e == hipSuccess) e = hipModuleGetFunction(&m.window_full, m.module, code->window_full.c_str());
         if (e == hipSuccess) e = hipModuleGetFunction(&m.window_blocks, m.module, code->window_blocks.c_str());
         if (e == hipSuccess) e = hipModuleGetFunction(&m.snooker, m.module, code->snooker.c_str());
+        if (e == hipSuccess) e = hipModuleGetFunction(&m.crossover, m.module, code->crossover.c_str());
     }
     if (!streaming && e == hipSuccess) e = hipModuleGetFunction(&m.logp, m.module, code->logp.c_str());
     if (e != hipSuccess) {

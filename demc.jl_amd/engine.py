@@ -45,6 +45,18 @@ Best = namedtuple("Best", "bestval chain generation bestpar")
 RankDiagnostics = namedtuple("RankDiagnostics", "rhat_rank ess_bulk ess_tail")
 
 
+class Crossover(namedtuple("Crossover", "ncr delta_max weights tried accepted")):
+    """HipEngine.crossover: the setting and, per CR class, the crossover steps tried and accepted over the handle's life."""
+    __slots__ = ()
+
+    @property
+    def accept_rate(self):
+        """accepted / tried per class (NaN where a class was never tried)"""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return self.accepted / self.tried.astype(np.float64)
+
+
+
 class PPC(namedtuple("PPC", "gt eq nan total names")):
     """A posterior predictive check (demcz_ppc): per column of the program, how many of the ``total`` draws had a value greater
     than the observed one (``gt``), equal to it (``eq``), or NaN (``nan``) -- int64 arrays of m entries; integer counts, so the
@@ -868,6 +880,32 @@ class HipEngine(_HistoryStatistics):
         ev, lo, hi, n = C.c_int32(0), C.c_double(0.0), C.c_double(0.0), C.c_int64(0)
         self._chk(self._L.demcz_get_snooker(self._h, C.byref(ev), C.byref(lo), C.byref(hi), C.byref(n)))
         return int(ev.value), float(lo.value), float(hi.value), int(n.value)
+
+    def set_crossover(self, ncr=3, delta_max=3, weights=None):
+        """demcz_set_crossover: with ``ncr >= 1`` every generation that is not a snooker generation is a crossover generation of
+        DREAM(ZS) -- each chain moves a random subset of its parameters (CR class m of ``ncr``, drawn with the integer
+        ``weights``, selects a parameter with probability (m + 1) / ncr) by the sum of 1 ... ``delta_max`` archive differences,
+        one log-density evaluation a generation.  ``ncr=0`` switches off.  One-lane handles (``lanes_per_chain=1``) with one
+        block, before the first generation (and before ``set_rng_offset`` on a resumed run)."""
+        ncr = int(ncr)
+        wp = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.int32)
+            if w.shape != (ncr,):
+                raise ValueError("weights: one integer per CR class")
+            wp = w.ctypes.data_as(C.POINTER(C.c_int32))
+        self._chk(self._L.demcz_set_crossover(self._h, C.c_int32(ncr), wp, C.c_int32(int(delta_max))))
+
+    @property
+    def crossover(self):
+        """``Crossover(ncr, delta_max, weights, tried, accepted)`` -- demcz_get_crossover; ``tried`` and ``accepted`` are the
+        steps per CR class over the handle's life (arrays of length ncr), ``.accept_rate`` their ratio."""
+        n, dm = C.c_int32(0), C.c_int32(0)
+        w, tr, ac = np.zeros(8, dtype=np.int32), np.zeros(8, dtype=np.int64), np.zeros(8, dtype=np.int64)
+        self._chk(self._L.demcz_get_crossover(self._h, C.byref(n), w.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(dm),
+                                              tr.ctypes.data_as(C.POINTER(C.c_int64)), ac.ctypes.data_as(C.POINTER(C.c_int64))))
+        k = int(n.value)
+        return Crossover(k, int(dm.value), w[:k].copy(), tr[:k].copy(), ac[:k].copy())
 
     def set_history_origin(self, g0):
         self._chk(self._L.demcz_set_history_origin(self._h, int(g0)))

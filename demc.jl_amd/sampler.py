@@ -536,11 +536,14 @@ class _DerivedRunner(_Runner):
 
 
 def make_runner(logobj, Zmat, N, K, Ngeneration, blockindex, eps_scale, X, logp, *, seed, sharding, device_id,
-                 engine_factory, lanes_per_chain, stream, rng_offset=0, append_lag=0, snooker_every=0, snooker_gamma=(1.2, 2.2)):
+                 engine_factory, lanes_per_chain, stream, rng_offset=0, append_lag=0, snooker_every=0, snooker_gamma=(1.2, 2.2), crossover=None):
     M0, d = Zmat.shape
     if M0 < 2:
         raise ValueError("Zmat needs at least 2 rows (two distinct archive rows per proposal, demcz.jl:176-179)")
     lanes_per_chain = _snooker_layout(logobj, lanes_per_chain, snooker_every)
+    crossover = _crossover_option(crossover)
+    if crossover:
+        lanes_per_chain = _crossover_layout(logobj, lanes_per_chain, blockindex, d)
     if snooker_every and M0 < 3:
         raise ValueError("Zmat needs at least 3 rows with snooker generations (three distinct archive rows per snooker step)")
     sh = sharding
@@ -559,6 +562,10 @@ def make_runner(logobj, Zmat, N, K, Ngeneration, blockindex, eps_scale, X, logp,
                     seed=seed, target=logobj, chain_id0=c0, device_id=device_id, stream=stream,
                     lanes_per_chain=lanes_per_chain)
         e.set_state(X[c0:c0 + n_loc], None if logp is None else logp[c0:c0 + n_loc], Zmat)
+        if crossover:          # (before the stream offset: the stride of a generation positions the streams)
+            if not hasattr(e, "set_crossover"):
+                raise ValueError("crossover: the engine_factory's engine has no set_crossover")
+            e.set_crossover(*crossover)
         if rng_offset:
             e.set_rng_offset(rng_offset)
         if snooker_every:
@@ -587,6 +594,35 @@ def _snooker_layout(logobj, lanes_per_chain, snooker_every):
         raise ValueError("snooker_every > 0 needs a device target: the host-closure mode has no snooker generations")
     if lanes_per_chain not in (0, 1):
         raise ValueError("snooker_every > 0 runs on the one-lane layout: lanes_per_chain must be 0 or 1")
+    return 1
+
+
+def _crossover_option(crossover):
+    """None / (ncr, delta_max) / (ncr, delta_max, weights) -> None (off) or (ncr, delta_max, weights)"""
+    if crossover is None:
+        return None
+    c = tuple(crossover)
+    if len(c) not in (2, 3):
+        raise ValueError("crossover: (ncr, delta_max) or (ncr, delta_max, weights)")
+    ncr, delta_max = int(c[0]), int(c[1])
+    if not 0 <= ncr <= 8 or not 1 <= delta_max <= 3:
+        raise ValueError("crossover: ncr must be 0 ... 8 and delta_max 1 ... 3")
+    if ncr == 0:
+        return None
+    return ncr, delta_max, (None if len(c) == 2 or c[2] is None else [int(v) for v in c[2]])
+
+
+def _crossover_layout(logobj, lanes_per_chain, blockindex, d):
+    """The layout a run with crossover generations is created on: one lane per chain (the library's choice, 0, becomes 1), a
+    device target, the one block 0 .. d-1."""
+    if not is_device_target(logobj):
+        raise ValueError("crossover needs a device target: the host-closure mode has no crossover")
+    if len(blockindex) != 1 or [int(i) for i in blockindex[0]] != list(range(d)):
+        raise ValueError("crossover draws its own subsets: it runs with one block covering all parameters in order")
+    if d < 2:
+        raise ValueError("crossover needs at least two parameters")
+    if lanes_per_chain not in (0, 1):
+        raise ValueError("crossover runs on the one-lane layout: lanes_per_chain must be 0 or 1")
     return 1
 
 
@@ -724,9 +760,11 @@ def demcz_sample(logobj, Zmat, N=4, K=10, Ngeneration=5000, Nblocks=1, blockinde
                  prevrun=None, verbose=True, print_step=100, autostop="no", autostop_Rhat=1.01,
                  autostop_every=1000, seed=0, init="last_rows", padded_Z=False, sharding=None, device_id=0,
                  lanes_per_chain=0, stream=None, engine_factory=None, return_runner=False, rng_offset=None,
-                 append_lag=0, snooker_every=0, snooker_gamma=(1.2, 2.2)):
+                 append_lag=0, snooker_every=0, snooker_gamma=(1.2, 2.2), crossover=None):
     """``snooker_every=s > 0``: every s-th generation is a snooker generation of DE-MCzs with gamma_s ~ U(*snooker_gamma)
     (``HipEngine.set_snooker``; the paper's choice is 10 and (1.2, 2.2)).
+    ``crossover=(ncr, delta_max)`` or ``(ncr, delta_max, weights)``: every other generation is a crossover generation of
+    DREAM(ZS) (``HipEngine.set_crossover``): one block, a device target, the one-lane layout.
 
     Serial-driver surface of src/demcz.jl: pass a ``DEMCopt`` as the third argument
     (``demcz_sample(logobj, Zmat, opts; prevrun)``, :1-3) or the positional arguments with
@@ -751,7 +789,7 @@ def demcz_sample(logobj, Zmat, N=4, K=10, Ngeneration=5000, Nblocks=1, blockinde
     runner = make_runner(logobj, Zmat, N, K, Ngeneration, blockindex, eps_scale, X, logp, seed=seed,
                           sharding=sharding, device_id=device_id, engine_factory=engine_factory,
                           lanes_per_chain=lanes_per_chain, stream=stream, rng_offset=rng_offset, append_lag=append_lag,
-                          snooker_every=snooker_every, snooker_gamma=snooker_gamma)
+                          snooker_every=snooker_every, snooker_gamma=snooker_gamma, crossover=crossover)
     if prevrun is None:
         if not (is_device_target(logobj) and runner.stream_history()):
             runner.prepare_result_arrays(Ngeneration)
@@ -803,8 +841,9 @@ def demcz_anneal(logobj, Zmat, N=4, K=10, Ngeneration=5000, Nblocks=1, blockinde
                  prevrun=None, verbose=True, print_step=100, temperaturefun=tempbaseline, T0=3, TN=0.0,
                  adaptγ=None, seed=0, init="last_rows", padded_Z=False, compat_serial_temp=False, sharding=None,
                  device_id=0, lanes_per_chain=0, stream=None, engine_factory=None, rng_offset=None, append_lag=0,
-                 snooker_every=0, snooker_gamma=(1.2, 2.2)):
-    """``snooker_every`` / ``snooker_gamma``: as in ``demcz_sample`` (the Jacobian term of a snooker step is not tempered).
+                 snooker_every=0, snooker_gamma=(1.2, 2.2), crossover=None):
+    """``snooker_every`` / ``snooker_gamma`` / ``crossover``: as in ``demcz_sample`` (the Jacobian term of a snooker step is
+    not tempered).
 
     Simulated-annealing variant, src/demcz_anneal.jl:14-65: tempered accept
     ``log(u) < (lp' - lp)/T(ig)`` (:172-178), ``T(ig) = temperaturefun(ig, Ngeneration, T0, TN)``,
@@ -831,7 +870,7 @@ def demcz_anneal(logobj, Zmat, N=4, K=10, Ngeneration=5000, Nblocks=1, blockinde
     runner = make_runner(logobj, Zmat, N, K, Ngeneration, blockindex, eps_scale, X, logp, seed=seed,
                           sharding=sharding, device_id=device_id, engine_factory=engine_factory,
                           lanes_per_chain=lanes_per_chain, stream=stream, rng_offset=rng_offset, append_lag=append_lag,
-                          snooker_every=snooker_every, snooker_gamma=snooker_gamma)
+                          snooker_every=snooker_every, snooker_gamma=snooker_gamma, crossover=crossover)
     if prevrun is None:
         if not (is_device_target(logobj) and runner.stream_history()):
             runner.prepare_result_arrays(Ngeneration)

@@ -440,6 +440,28 @@ int32_t demcz_set_snooker(demcz_handle* h, int32_t every, double gamma_lo, doubl
 /* What was set, and the snooker launches made in the handle's life (any pointer may be NULL). */
 int32_t demcz_get_snooker(const demcz_handle* h, int32_t* every, double* gamma_lo, double* gamma_hi, int64_t* steps_launched);
 
+/* Crossover generations: the subspace sampling and the multi-pair jump of DREAM(ZS) (Vrugt et al. 2009; Laloy & Vrugt 2012).
+ * Off by default (ncr = 0 switches off).  With ncr >= 1 every generation that is not a snooker generation is a crossover
+ * generation: every chain makes ONE step with ONE log-density evaluation, in which it draws a CR class m with the integer
+ * weights (P(m) = w_m / W), a number of pairs delta ~ U{1 .. delta_max}, and moves a random subset of its parameters -- each
+ * selected with probability (m + 1) / ncr, one at random if none was -- by
+ *   x'_p = x_p + (gamma / sqrt(2 delta d') (sum over delta pairs of Z[i1, p] - Z[i2, p]) + eps_p z_p),   d' = the subset's size;
+ * the other parameters keep their bits.  Accept rule, temperature, history, changed counts and the K-boundary append are those
+ * of any generation.  A generation takes S_cr = 1 + delta_max + ceil(d / 4) + ceil(d / 2) + 1 Philox blocks of the chain's
+ * stream, at fixed positions (DESIGN.md section 3 has the arithmetic, word by word); a snooker generation reads the first three
+ * of them.  weights: ncr values >= 0 whose sum W has 1 <= W < 2^31, or NULL for all 1.
+ * DEMCZ_ERR_INVALID_ARGUMENT: ncr outside 0 ... 8; delta_max outside 1 ... 3; a negative weight or W outside [1, 2^31); d < 2;
+ * more than one block; a handle not created on the one-lane layout (lanes_per_chain = 1).  DEMCZ_ERR_STATE: a host-callback
+ * handle, a derived history, a handle in a replica group or with IPC peers, and a handle that has already run a generation
+ * (the stride positions the streams: a resumed run sets crossover on the fresh handle, before demcz_set_rng_offset).
+ * demcz_run with crossover on and fewer than two archive rows returns DEMCZ_ERR_STATE before anything is enqueued;
+ * demcz_peer_group and demcz_propose refuse such a handle. */
+int32_t demcz_set_crossover(demcz_handle* h, int32_t ncr, const int32_t* weights, int32_t delta_max);
+/* What was set, and per CR class the steps tried and those whose accept test was true, summed over the handle's life (snooker
+ * generations are not counted).  weights: ncr values; tried, accepted: 8 values each.  Any pointer may be NULL.  Synchronises
+ * the handle's stream when counts are asked for. */
+int32_t demcz_get_crossover(const demcz_handle* h, int32_t* ncr, int32_t* weights, int32_t* delta_max, int64_t* tried, int64_t* accepted);
+
 /* Stateless diagnostics on caller (host) arrays, for code that post-processes returned histories
  * the way the reference's examples do (test/example_normpdf.jl:35-47): the array is uploaded, reduced
  * on the device, and nothing is kept.

@@ -118,6 +118,20 @@ function get_snooker(h)
     chk(ccall((:demcz_get_snooker, libdemcz), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Float64}, Ref{Float64}, Ref{Int64}), h, ev, lo, hi, n), h)
     Int(ev[]), lo[], hi[], Int(n[])
 end
+# crossover generations of DREAM(ZS) (one-lane handles with one block, set before the first generation): every generation that is
+# not a snooker generation moves a random subset of each chain's parameters by the sum of 1 … δmax archive differences;
+# weights: ncr integers ≥ 0 (nothing: all 1); ncr = 0 switches off
+set_crossover!(h, ncr, δmax=3, weights=nothing) =
+    chk(ccall((:demcz_set_crossover, libdemcz), Int32, (Ptr{Cvoid}, Int32, Ptr{Int32}, Int32),
+              h, ncr, weights === nothing ? C_NULL : Int32.(weights), δmax), h)
+# (ncr, δmax, weights, steps tried per class, steps accepted per class)
+function get_crossover(h)
+    n = Ref{Int32}(0); dm = Ref{Int32}(0); w = zeros(Int32, 8); tr = zeros(Int64, 8); ac = zeros(Int64, 8)
+    chk(ccall((:demcz_get_crossover, libdemcz), Int32, (Ptr{Cvoid}, Ref{Int32}, Ptr{Int32}, Ref{Int32}, Ptr{Int64}, Ptr{Int64}),
+              h, n, w, dm, tr, ac), h)
+    k = Int(n[])
+    k, Int(dm[]), Int.(w[1:k]), tr[1:k], ac[1:k]
+end
 # the loop demcz.jl:30-55 (generations + the R-hat test every `every`) as ONE call; returns the generation it stopped at
 function run_checked!(h, g_from, g_to, γ, every, threshold)
     g_stop = Ref{Int64}(0); n = Ref{Int32}(0)
