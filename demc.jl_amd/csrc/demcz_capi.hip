@@ -424,7 +424,7 @@ struct demcz_handle {
     demcz_prog::Module prog;
     std::string prog_source, prog_options;   // the program's text, for the units compiled later (demcz_bridge: UNIT_BRIDGE)
     // created with DEMCZ_LAYOUT_PROGRAM_WAVE: lanes == DEMCZ_LAYOUT_SPLIT, split_kind == SPLIT_WAVE, and the consumer is the program's own
-    // window_kernel_ps / _pw<TARGET_PROGRAM, d, LIVE, TEMPER> (prog.wave); records, producer, LIVE machinery: the library's
+    // window_kernel_ps / _pw<TARGET_PROGRAM, d, LIVE, TEMPER> (prog.fn[WAVE_KERNEL ..]); records, producer, LIVE machinery: the library's
     bool prog_wave = false;
     // a derived history (demcz_derive): N x cfg.d x cfg.Gcap values in dchain, the program's data in d_design, a stream, the
     // staging buffer and nothing else -- no state, no archive, no log_obj.  The statistics over dchain and demcz_derive itself
@@ -1257,7 +1257,7 @@ static int32_t launch_logp(demcz_handle* h, const double* X, int64_t ldX, int64_
         TargetParams tpv = tp;
         int dv = h->cfg.d;
         void* args[] = {&tpv, &dv, &X, &ldX, &n, &out};
-        HIPCHK(h, hipModuleLaunchKernel(h->prog.logp, grid.x, 1, 1, bs, 1, 1, 0, h->stream, args, nullptr));
+        HIPCHK(h, hipModuleLaunchKernel(h->prog.fn[h->prog_wave ? demcz_prog::WAVE_LOGP : demcz_prog::LANE_LOGP], grid.x, 1, 1, bs, 1, 1, 0, h->stream, args, nullptr));
         break;
     }
     default: return fail(h, DEMCZ_ERR_STATE, "host-callback target: pass logp explicitly");
@@ -1411,12 +1411,40 @@ extern "C" int32_t demcz_set_history_origin(demcz_handle* h, int64_t g0)
 }
 
 // ---- program targets (demcz_program.hip) ---------------------------------------------------------
-extern "C" int32_t demcz_program_check(int32_t d, const char* source, const char* options)
+namespace {
+// Compile `source` into `unit` (or find it in the process-wide cache); needs no device.  What the *_check entry points do, with
+// h == nullptr: the message goes where demcz_last_error(NULL) reads it.
+int32_t program_compile(demcz_handle* h, int unit, int d, int m, const char* source, const char* options,
+                        std::shared_ptr<const demcz_prog::Code>* out = nullptr)
 {
     std::shared_ptr<const demcz_prog::Code> code;
     std::string err;
-    if (demcz_prog::get_code(d, source, options, demcz_prog::UNIT_ONE_LANE, code, err) != 0) return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, err);
+    if (demcz_prog::get_code(d, source, options, unit, code, err, m) != 0) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, err);
+    if (out) *out = code;
     return DEMCZ_OK;
+}
+
+// ... and load it on h's device: the module of the unit's kernels (demcz_program.h names them)
+int32_t program_load(demcz_handle* h, int unit, int d, int m, const char* source, const char* options, demcz_prog::Module& mod)
+{
+    std::shared_ptr<const demcz_prog::Code> code;
+    if (int32_t rc = program_compile(h, unit, d, m, source, options, &code)) return rc;
+    std::string err;
+    if (demcz_prog::get_module(code, h->cfg.device_id, mod, err) != 0) return fail(h, DEMCZ_ERR_HIP, err);
+    return DEMCZ_OK;
+}
+
+// the data of a program: ndata doubles, or none
+int32_t data_check(demcz_handle* h, const char* who, const double* data, int64_t ndata)
+{
+    if (ndata < 0 || (ndata > 0 && !data)) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": need ndata >= 0 and data for ndata > 0");
+    return DEMCZ_OK;
+}
+}  // namespace
+
+extern "C" int32_t demcz_program_check(int32_t d, const char* source, const char* options)
+{
+    return program_compile(nullptr, demcz_prog::UNIT_ONE_LANE, d, 0, source, options);
 }
 
 extern "C" int32_t demcz_program_check_layout(int32_t d, const char* source, const char* options, int32_t lanes_per_chain)
@@ -1424,11 +1452,8 @@ extern "C" int32_t demcz_program_check_layout(int32_t d, const char* source, con
     if (lanes_per_chain != 0 && lanes_per_chain != 1 && lanes_per_chain != DEMCZ_LAYOUT_PROGRAM_WAVE)
         return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_program_check_layout: a program target runs one lane per chain: lanes_per_chain must be 0 or 1 "
                                                          "(or DEMCZ_LAYOUT_PROGRAM_WAVE: one wavefront per chain)");
-    std::shared_ptr<const demcz_prog::Code> code;
-    std::string err;
     const int unit = (lanes_per_chain == DEMCZ_LAYOUT_PROGRAM_WAVE) ? demcz_prog::UNIT_WAVE : demcz_prog::UNIT_ONE_LANE;
-    if (demcz_prog::get_code(d, source, options, unit, code, err) != 0) return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, err);
-    return DEMCZ_OK;
+    return program_compile(nullptr, unit, d, 0, source, options);
 }
 
 extern "C" int32_t demcz_set_program(demcz_handle* h, const char* source, const char* options, const double* data, int64_t ndata)
@@ -1440,15 +1465,10 @@ extern "C" int32_t demcz_set_program(demcz_handle* h, const char* source, const 
         return fail(h, DEMCZ_ERR_STATE, "demcz_set_program: the handle was not created with DEMCZ_TARGET_PROGRAM");
     if (h->prog_ready || h->has_state)
         return fail(h, DEMCZ_ERR_STATE, "demcz_set_program: a handle takes its program once, before demcz_set_state");
-    if (ndata < 0 || (ndata > 0 && !data))
-        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_program: need ndata >= 0 and data for ndata > 0");
-    std::shared_ptr<const demcz_prog::Code> code;
-    std::string err;
+    if (int32_t rc = data_check(h, "demcz_set_program", data, ndata)) return rc;
     // (a handle compiles the unit of ITS layout only: the wave unit is never built for a one-lane handle, nor the reverse)
-    if (demcz_prog::get_code(h->cfg.d, source, options, h->prog_wave ? demcz_prog::UNIT_WAVE : demcz_prog::UNIT_ONE_LANE, code, err) != 0)
-        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, err);
     demcz_prog::Module mod;
-    if (demcz_prog::get_module(code, h->cfg.device_id, mod, err) != 0) return fail(h, DEMCZ_ERR_HIP, err);
+    if (int32_t rc = program_load(h, h->prog_wave ? demcz_prog::UNIT_WAVE : demcz_prog::UNIT_ONE_LANE, h->cfg.d, 0, source, options, mod)) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device_id));
     double* dd = nullptr;
     HIPCHK(h, dev_alloc_copy(&dd, data, (size_t)ndata, h->stream, h->cfg.device_id));
@@ -1668,7 +1688,7 @@ static int32_t launch_window_pc(demcz_handle* h, const WindowParams& P, const Wi
             size_t big_d = throttle_env;
             if (h->split_kind == SPLIT_WAVE && P.d > 20) {
                 int plds = 0;       // (program: its own LIVE kernel's static LDS)
-                if (h->prog_wave && (!h->prog_ready || hipFuncGetAttribute(&plds, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, h->prog.wave[1][0]) != hipSuccess)) plds = (int)ML_MAX_DYNAMIC_LDS;
+                if (h->prog_wave && (!h->prog_ready || hipFuncGetAttribute(&plds, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, h->prog.fn[demcz_prog::WAVE_KERNEL + 2 * 1 + 0]) != hipSuccess)) plds = (int)ML_MAX_DYNAMIC_LDS;
                 size_t clds = (size_t)plds;
                 if (!h->prog_wave) {     // (built-in: the most any of its LIVE forms takes)
                     WindowKernel lk[MAX_LIVE_KERNELS];
@@ -1890,7 +1910,7 @@ static WindowKernel window_kernel_of(const demcz_handle* h, const LaunchFacts& f
         k.arm = ARM_SNOOKER;
         k.threads = WINDOW_BS;
         k.waves = 1;
-        if (tk == DEMCZ_TARGET_PROGRAM) { if (h->prog_ready) k.mod = h->prog.snooker; }
+        if (tk == DEMCZ_TARGET_PROGRAM) { if (h->prog_ready) k.mod = h->prog.fn[demcz_prog::LANE_SNOOKER]; }
         else k.fn = snooker_kernel_fn(tk, d, &k.dyn_lds);
         return k;
     }
@@ -1900,7 +1920,7 @@ static WindowKernel window_kernel_of(const demcz_handle* h, const LaunchFacts& f
         k.arm = ARM_CROSSOVER;
         k.threads = WINDOW_BS;
         k.waves = 1;
-        if (tk == DEMCZ_TARGET_PROGRAM) { if (h->prog_ready) k.mod = h->prog.crossover; }
+        if (tk == DEMCZ_TARGET_PROGRAM) { if (h->prog_ready) k.mod = h->prog.fn[demcz_prog::LANE_CROSSOVER]; }
         else k.fn = crossover_kernel_fn(tk, d, &k.dyn_lds);
         return k;
     }
@@ -1917,7 +1937,7 @@ static WindowKernel window_kernel_of(const demcz_handle* h, const LaunchFacts& f
                 // the program's own wave-per-chain consumer (demcz_program.hip, UNIT_WAVE), with the workgroup shape of the built-in
                 // one (its LDS is static)
                 k.arm = ARM_PROGRAM_WAVE;
-                if (h->prog_ready) k.mod = h->prog.wave[f.live ? 1 : 0][f.temper ? 1 : 0];
+                if (h->prog_ready) k.mod = h->prog.fn[demcz_prog::WAVE_KERNEL + 2 * (f.live ? 1 : 0) + (f.temper ? 1 : 0)];
             } else if (d <= 5) {
                 // regular launches: the steady-state kernel -- of a two-chain handle the one with two chains to a wave
                 k.arm = (f.dual && f.ps2) ? ARM_PS2D : (!h->ps_dual && f.ps2) ? ARM_PS2 : ARM_PS;
@@ -2027,7 +2047,7 @@ static WindowKernel window_kernel_of(const demcz_handle* h, const LaunchFacts& f
             break;
         case DEMCZ_TARGET_PROGRAM:
             // the program's own window_kernel<TARGET_PROGRAM, d, FULL> (demcz_program.hip), from its module
-            if (h->prog_ready) k.mod = h->full_block ? h->prog.window_full : h->prog.window_blocks;
+            if (h->prog_ready) k.mod = h->prog.fn[h->full_block ? demcz_prog::LANE_FULL : demcz_prog::LANE_BLOCKS];
             break;
         default: break;       // (host-callback target: demcz_propose / demcz_accept_commit, no window kernel)
         }
@@ -4691,10 +4711,7 @@ extern "C" int32_t demcz_mean_cov_array(int32_t device_id, const double* chain, 
 // ---- derived quantities: user functions of the draws (demcz_kernels_derive.h) -----------------------------------------------
 extern "C" int32_t demcz_derive_check(int32_t d, int32_t m, const char* source, const char* options)
 {
-    std::shared_ptr<const demcz_prog::Code> code;
-    std::string err;
-    if (demcz_prog::get_code(d, source, options, demcz_prog::UNIT_DERIVE, code, err, m) != 0) return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, err);
-    return DEMCZ_OK;
+    return program_compile(nullptr, demcz_prog::UNIT_DERIVE, d, m, source, options);
 }
 
 namespace {
@@ -4822,16 +4839,16 @@ int32_t derive_from(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t m, co
     Window win;
     int32_t rc = open_window(h, g_from, g_to, who, win);
     if (rc) return rc;
-    if (ndata < 0 || (ndata > 0 && !data)) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_derive: need ndata >= 0 and data for ndata > 0");
+    rc = data_check(h, who, data, ndata);
+    if (rc) return rc;
     rc = enter_device(h);
     if (rc) return rc;
-    std::shared_ptr<const demcz_prog::Code> code;
-    std::string err;
-    if (demcz_prog::get_code(win.d, source, options, demcz_prog::UNIT_DERIVE, code, err, m) != 0) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, err);
     demcz_prog::Module mod;
-    if (demcz_prog::get_module(code, h->cfg.device_id, mod, err) != 0) return fail(h, DEMCZ_ERR_HIP, err);
+    rc = program_load(h, demcz_prog::UNIT_DERIVE, win.d, m, source, options, mod);
+    if (rc) return rc;
     rc = quiesce_all(h);                        // (a sharded handle: the allocations below synchronise the device)
     if (rc) return rc;
+    std::string err;
     NewDerived dh = derived_create(h->cfg.device_id, win.N, m, win.w, g_from - 1, data, ndata, err);
     if (!dh) return fail(h, DEMCZ_ERR_HIP, err);
     const double* chain = h->dchain;
@@ -4840,7 +4857,7 @@ int32_t derive_from(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t m, co
     double* out = dh->dchain;
     void* args[] = {&chain, &logobj, &win.N, &win.s0, &win.total, &ddata, &ndata, &out};
     // on the source's stream: behind the window launches that write the history, and behind whatever else is queued there
-    const hipError_t e = hipModuleLaunchKernel(mod.derive, derive_blocks(win.total), 1, 1, DERIVE_THREADS, 1, 1, 0, h->stream, args, nullptr);
+    const hipError_t e = hipModuleLaunchKernel(mod.fn[demcz_prog::DERIVE_KERNEL], derive_blocks(win.total), 1, 1, DERIVE_THREADS, 1, 1, 0, h->stream, args, nullptr);
     return finish(h, who, "derive_kernel", e, dh, derived);
 }
 }  // namespace
@@ -4871,10 +4888,7 @@ extern "C" int32_t demcz_derive_array(int32_t device_id, const double* chain, co
 // ---- posterior predictive programs: functions of the draws and of each draw's own random stream (demcz_kernels_predict.h) -------
 extern "C" int32_t demcz_predict_check(int32_t d, int32_t m, const char* source, const char* options)
 {
-    std::shared_ptr<const demcz_prog::Code> code;
-    std::string err;
-    if (demcz_prog::get_code(d, source, options, demcz_prog::UNIT_PREDICT, code, err, m) != 0) return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, err);
-    return DEMCZ_OK;
+    return program_compile(nullptr, demcz_prog::UNIT_PREDICT, d, m, source, options);
 }
 
 namespace {
@@ -4885,18 +4899,17 @@ int32_t predict_open(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t m, c
 {
     int32_t rc = open_window(h, g_from, g_to, who, win);
     if (rc) return rc;
-    if (ndata < 0 || (ndata > 0 && !data)) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": need ndata >= 0 and data for ndata > 0");
+    rc = data_check(h, who, data, ndata);
+    if (rc) return rc;
     constexpr int64_t TWO32 = (int64_t)1 << 32;
     if (g_to >= TWO32 || chain_id0 < 0 || chain_id0 > TWO32 - win.N)
         return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": the stream of a draw is keyed by (generation, global chain), 32 bits each: need "
                                                    "g_to < 2^32 and 0 <= chain_id0, chain_id0 + N <= 2^32");
     rc = enter_device(h);
     if (rc) return rc;
-    std::shared_ptr<const demcz_prog::Code> code;
-    std::string err;
-    if (demcz_prog::get_code(win.d, source, options, demcz_prog::UNIT_PREDICT, code, err, m) != 0) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, err);
-    if (demcz_prog::get_module(code, h->cfg.device_id, mod, err) != 0) return fail(h, DEMCZ_ERR_HIP, err);
-    return quiesce_all(h);                      // (a sharded handle: the allocations that follow synchronise the device)
+    rc = program_load(h, demcz_prog::UNIT_PREDICT, win.d, m, source, options, mod);
+    if (rc) return rc;
+    return quiesce_all(h);                     // (a sharded handle: the allocations that follow synchronise the device)
 }
 
 // demcz_predict on a source that holds an N x d x Gcap history (a sampling handle, a derived history, a ScratchHandle)
@@ -4916,7 +4929,7 @@ int32_t predict_from(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t m, c
     const double* ddata = ndata > 0 ? dh->d_design : nullptr;
     double* out = dh->dchain;
     void* args[] = {&chain, &logobj, &win.N, &win.s0, &win.total, &ddata, &ndata, &seed, &g_from, &chain_id0, &out};
-    const hipError_t e = hipModuleLaunchKernel(mod.derive, derive_blocks(win.total), 1, 1, DERIVE_THREADS, 1, 1, 0, h->stream, args, nullptr);
+    const hipError_t e = hipModuleLaunchKernel(mod.fn[demcz_prog::PREDICT_KERNEL], derive_blocks(win.total), 1, 1, DERIVE_THREADS, 1, 1, 0, h->stream, args, nullptr);
     return finish(h, who, "predict_kernel", e, dh, derived);
 }
 
@@ -4948,7 +4961,7 @@ int32_t ppc_from(demcz_handle* h, int64_t g_from, int64_t g_to, int32_t m, const
         const double* chain = h->dchain;
         const double* logobj = h->dlogobj;
         void* args[] = {&chain, &logobj, &win.N, &win.s0, &win.total, &ddata, &ndata, &seed, &g_from, &chain_id0, &dobs, &dcounts};
-        const hipError_t e = hipModuleLaunchKernel(mod.ppc, derive_blocks(win.total), 1, 1, DERIVE_THREADS, 1, 1, 0, h->stream, args, nullptr);
+        const hipError_t e = hipModuleLaunchKernel(mod.fn[demcz_prog::PREDICT_PPC], derive_blocks(win.total), 1, 1, DERIVE_THREADS, 1, 1, 0, h->stream, args, nullptr);
         if (e != hipSuccess) return fail(h, DEMCZ_ERR_HIP, std::string(who) + ": launching ppc_kernel: " + hipGetErrorString(e));
         HIPCHK(h, hipMemcpyAsync(hc.data(), dcounts, nc * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
         return sync_stream(h, h->stream, who);
@@ -5573,10 +5586,7 @@ extern "C" int32_t demcz_hdi_array(int32_t device_id, const double* chain, int64
 // ---- PSIS-LOO and WAIC (demcz_kernels_pointwise.h, K11 demcz_kernels_loo.h, demcz_loo_host.h) -----------------------------------
 extern "C" int32_t demcz_pointwise_check(int32_t d, const char* source, const char* options)
 {
-    std::shared_ptr<const demcz_prog::Code> code;
-    std::string err;
-    if (demcz_prog::get_code(d, source, options, demcz_prog::UNIT_POINTWISE, code, err) != 0) return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, err);
-    return DEMCZ_OK;
+    return program_compile(nullptr, demcz_prog::UNIT_POINTWISE, d, 0, source, options);
 }
 
 namespace {
@@ -5588,18 +5598,18 @@ int32_t pointwise_from(demcz_handle* h, int64_t g_from, int64_t g_to, int64_t ob
     Window win;
     int32_t rc = open_window(h, g_from, g_to, who, win);
     if (rc) return rc;
-    if (ndata < 0 || (ndata > 0 && !data)) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_pointwise: need ndata >= 0 and data for ndata > 0");
+    rc = data_check(h, who, data, ndata);
+    if (rc) return rc;
     if (mc < 1 || mc > LOO_MAX_CHUNK || obs_from < 0)
         return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "pointwise program: mc must be in 1.." + std::to_string(LOO_MAX_CHUNK) + " and obs_from >= 0");
     rc = enter_device(h);
     if (rc) return rc;
-    std::shared_ptr<const demcz_prog::Code> code;
-    std::string err;
-    if (demcz_prog::get_code(win.d, source, options, demcz_prog::UNIT_POINTWISE, code, err) != 0) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, err);
     demcz_prog::Module mod;
-    if (demcz_prog::get_module(code, h->cfg.device_id, mod, err) != 0) return fail(h, DEMCZ_ERR_HIP, err);
+    rc = program_load(h, demcz_prog::UNIT_POINTWISE, win.d, 0, source, options, mod);
+    if (rc) return rc;
     rc = quiesce_all(h);                        // (a sharded handle: the allocations below synchronise the device)
     if (rc) return rc;
+    std::string err;
     NewDerived dh = derived_create(h->cfg.device_id, win.N, mc, win.w, g_from - 1, data, ndata, err, who);
     if (!dh) return fail(h, DEMCZ_ERR_HIP, err);
     const double* chain = h->dchain;
@@ -5607,7 +5617,7 @@ int32_t pointwise_from(demcz_handle* h, int64_t g_from, int64_t g_to, int64_t ob
     double* out = dh->dchain;
     int mcount = mc;
     void* args[] = {&chain, &win.N, &win.s0, &win.total, &ddata, &ndata, &obs_from, &mcount, &out};
-    const hipError_t e = hipModuleLaunchKernel(mod.derive, derive_blocks(win.total), 1, 1, DERIVE_THREADS, 1, 1, 0, h->stream, args, nullptr);
+    const hipError_t e = hipModuleLaunchKernel(mod.fn[demcz_prog::POINTWISE_KERNEL], derive_blocks(win.total), 1, 1, DERIVE_THREADS, 1, 1, 0, h->stream, args, nullptr);
     return finish(h, who, "pointwise_kernel", e, dh, derived);
 }
 
@@ -5776,10 +5786,7 @@ extern "C" int32_t demcz_loo_array(int32_t device_id, const double* chain, int64
 // ---- the marginal likelihood by bridge sampling (K12, demcz_kernels_bridge.h; DESIGN.md sections 3 and 4.17) ---------------------
 extern "C" int32_t demcz_bridge_check(int32_t d, const char* source, const char* options)
 {
-    std::shared_ptr<const demcz_prog::Code> code;
-    std::string err;
-    if (demcz_prog::get_code(d, source, options, demcz_prog::UNIT_BRIDGE, code, err) != 0) return fail(nullptr, DEMCZ_ERR_INVALID_ARGUMENT, err);
-    return DEMCZ_OK;
+    return program_compile(nullptr, demcz_prog::UNIT_BRIDGE, d, 0, source, options);
 }
 
 namespace {
@@ -5897,13 +5904,9 @@ int32_t bridge_target_of(demcz_handle* h, const char* who, BridgeTarget& t)
         return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": d must be in 1.." + std::to_string(BRIDGE_MAX_D));
     if (h->cfg.target_kind == DEMCZ_TARGET_PROGRAM) {
         if (!h->prog_ready) return fail(h, DEMCZ_ERR_STATE, "program target: call demcz_set_program first");
-        std::shared_ptr<const demcz_prog::Code> code;
-        std::string err;
-        if (demcz_prog::get_code(d, h->prog_source.c_str(), h->prog_options.c_str(), demcz_prog::UNIT_BRIDGE, code, err) != 0)
-            return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, err);
         demcz_prog::Module mod;
-        if (demcz_prog::get_module(code, h->cfg.device_id, mod, err) != 0) return fail(h, DEMCZ_ERR_HIP, err);
-        t.prog = mod.derive;
+        if (int32_t rc = program_load(h, demcz_prog::UNIT_BRIDGE, d, 0, h->prog_source.c_str(), h->prog_options.c_str(), mod)) return rc;
+        t.prog = mod.fn[demcz_prog::BRIDGE_KERNEL];
         t.data = h->cfg.nobs > 0 ? h->d_design : nullptr;
         t.ndata = h->cfg.nobs;
         return DEMCZ_OK;
@@ -5921,13 +5924,10 @@ int32_t bridge_target_of(demcz_handle* h, const char* who, BridgeTarget& t)
 int32_t bridge_target_program(demcz_handle* h, int d, const char* source, const char* options, const double* data, int64_t ndata,
                               const char* who, BridgeTarget& t)
 {
-    if (ndata < 0 || (ndata > 0 && !data)) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, std::string(who) + ": need ndata >= 0 and data for ndata > 0");
-    std::shared_ptr<const demcz_prog::Code> code;
-    std::string err;
-    if (demcz_prog::get_code(d, source, options, demcz_prog::UNIT_BRIDGE, code, err) != 0) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, err);
+    if (int32_t rc = data_check(h, who, data, ndata)) return rc;
     demcz_prog::Module mod;
-    if (demcz_prog::get_module(code, h->cfg.device_id, mod, err) != 0) return fail(h, DEMCZ_ERR_HIP, err);
-    t.prog = mod.derive;
+    if (int32_t rc = program_load(h, demcz_prog::UNIT_BRIDGE, d, 0, source, options, mod)) return rc;
+    t.prog = mod.fn[demcz_prog::BRIDGE_KERNEL];
     t.hdata = data;
     t.ndata = ndata;
     return DEMCZ_OK;

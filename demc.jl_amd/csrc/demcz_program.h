@@ -16,43 +16,44 @@ namespace demcz_prog {
 constexpr int MAX_PROGRAM_D = 32;
 constexpr int MAX_DERIVE_M = demcz::DERIVE_MAX_M;
 
-// The two units a program can be compiled into (demcz_program.hip, compose): the one-lane window kernel, or the wave-per-chain
-// consumers of the split layout (DEMCZ_LAYOUT_PROGRAM_WAVE: window_kernel_ps for d = 2..5, window_kernel_pw for d = 6..32).
-// A derive program (demcz_derive, include/demcz.h) has a unit of its own: the user's demcz_derive and derive_kernel of
-// demcz_kernels_derive.h, nothing else.
-// A pointwise program (demcz_pointwise) likewise: the user's demcz_loglik and pointwise_kernel of demcz_kernels_pointwise.h.
-// A program target's bridge unit (demcz_bridge_proposal): the user's demcz_logobj and bridge_proposal_program_kernel of
-// demcz_kernels_bridge.h.
-// A predictive program (demcz_predict, demcz_ppc): demcz_device.h, the demcz_rng of demcz_predict_rng.h, the user's demcz_predict,
-// and predict_kernel and ppc_kernel of demcz_kernels_predict.h.
-enum { UNIT_ONE_LANE = 0, UNIT_WAVE = 1, UNIT_DERIVE = 2, UNIT_POINTWISE = 3, UNIT_BRIDGE = 4, UNIT_PREDICT = 5 };
+// The units a program can be compiled into: each is one row of the table in demcz_program.hip, which says what the unit consists
+// of.  A program target runs in the one-lane unit or, on the wave-per-chain layout (DEMCZ_LAYOUT_PROGRAM_WAVE), in the wave unit;
+// the bridge unit evaluates such a target at a proposal's draws (demcz_bridge_proposal).  Derive, pointwise and predictive programs
+// (demcz_derive, demcz_pointwise, demcz_predict / demcz_ppc) have a unit each.
+enum { UNIT_ONE_LANE = 0, UNIT_WAVE = 1, UNIT_DERIVE = 2, UNIT_POINTWISE = 3, UNIT_BRIDGE = 4, UNIT_PREDICT = 5, UNIT_COUNT };
 constexpr int WAVE_MIN_D = 2;
 
-// One compiled program: the gfx950 code object and the mangled names of its kernels.
+// The kernels of each unit: indices into Code::names and Module::fn, in the order of the unit's row.
+enum {
+    LANE_FULL = 0,         // window_kernel<TARGET_PROGRAM, d, true>: one block covering 0..d-1 in order
+    LANE_BLOCKS,           // window_kernel<TARGET_PROGRAM, d, false>: blocks from the CSR tables
+    LANE_SNOOKER,          // snooker_kernel<TARGET_PROGRAM, d> (demcz_kernels_snooker.h)
+    LANE_CROSSOVER,        // window_kernel_cr<TARGET_PROGRAM, d> (demcz_kernels_crossover.h)
+    LANE_LOGP              // logp_kernel<TARGET_PROGRAM>: the initial log_objcurrent
+};
+enum {
+    WAVE_KERNEL = 0,       // + 2 * LIVE + TEMPER: window_kernel_ps (d <= 5) / _pw<TARGET_PROGRAM, d, LIVE, TEMPER>
+    WAVE_LOGP = 4          // logp_kernel<TARGET_PROGRAM>
+};
+enum { DERIVE_KERNEL = 0 };                        // derive_kernel
+enum { POINTWISE_KERNEL = 0 };                     // pointwise_kernel
+enum { BRIDGE_KERNEL = 0 };                        // bridge_proposal_program_kernel
+enum { PREDICT_KERNEL = 0, PREDICT_PPC = 1 };      // predict_kernel, ppc_kernel
+constexpr int MAX_KERNELS = 5;
+
+// One compiled program: the gfx950 code object and the mangled names of its unit's kernels.
 struct Code {
     std::vector<char> object;
-    std::string window_full;      // window_kernel<TARGET_PROGRAM, d, true>: one block covering 0..d-1 in order
-    std::string window_blocks;    // window_kernel<TARGET_PROGRAM, d, false>: blocks from the CSR tables
-    std::string snooker;          // snooker_kernel<TARGET_PROGRAM, d> (demcz_kernels_snooker.h): one-lane unit only
-    std::string crossover;        // window_kernel_cr<TARGET_PROGRAM, d> (demcz_kernels_crossover.h): one-lane unit only
-    std::string logp;             // logp_kernel<TARGET_PROGRAM>: the initial log_objcurrent (both units)
-    std::string wave[2][2];       // UNIT_WAVE: window_kernel_ps / _pw<TARGET_PROGRAM, d, LIVE, TEMPER>, [LIVE][TEMPER] (the one-lane
-                                  // kernels are not in that unit, and these not in the one-lane unit)
-    std::string derive;           // UNIT_DERIVE: derive_kernel, the only kernel of that unit; UNIT_POINTWISE: pointwise_kernel;
-                                  // UNIT_BRIDGE: bridge_proposal_program_kernel; UNIT_PREDICT: predict_kernel
-    std::string ppc;              // UNIT_PREDICT: ppc_kernel
+    std::string names[MAX_KERNELS];
     int d = 0;
-    int m = 0;                    // UNIT_DERIVE, UNIT_PREDICT: derived quantities per draw (DEMCZ_M)
+    int m = 0;                    // the units with DEMCZ_M: derived quantities per draw
     int unit = UNIT_ONE_LANE;
 };
 
 // A code object loaded on one device (kept until the process exits).
 struct Module {
     hipModule_t module = nullptr;
-    hipFunction_t window_full = nullptr, window_blocks = nullptr, snooker = nullptr, crossover = nullptr, logp = nullptr;
-    hipFunction_t wave[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    hipFunction_t derive = nullptr;   // (UNIT_POINTWISE: pointwise_kernel; UNIT_BRIDGE: bridge_proposal_program_kernel; UNIT_PREDICT: predict_kernel)
-    hipFunction_t ppc = nullptr;      // UNIT_PREDICT: ppc_kernel
+    hipFunction_t fn[MAX_KERNELS] = {};
     std::shared_ptr<const Code> code;
 };
 

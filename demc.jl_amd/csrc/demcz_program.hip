@@ -1,40 +1,18 @@
-// demcz_program.hip -- program targets (DEMCZ_TARGET_PROGRAM): a log-density the user writes as HIP C++, compiled at run time
-// with hipRTC for gfx950 together with the one-lane window kernel of demcz_kernels.h, and loaded as a module on the handle's
-// device.  Host code only: the kernels of a program live in its code object, not in this library.
+// demcz_program.hip -- program targets (DEMCZ_TARGET_PROGRAM) and the other programs the user writes as HIP C++: compiled at run
+// time with hipRTC for gfx950 together with kernels of the library's, and loaded as a module on the handle's device.  Host code
+// only: the kernels of a program live in its code object, not in this library.
 //
-// The composed translation unit (compose):
-//     #define DEMCZ_D <d> / DEMCZ_PROGRAM_TARGET / DEMCZ_NO_AUX_KERNELS, INFINITY and NAN as <math.h> has them
-//     the user's source                      (#line 1 "program": compiler messages carry the user's own line numbers)
-//     #include "demcz_kernels.h"             (its text and demcz_device.h's are embedded into this library at build time)
-//     #include "demcz_kernels_snooker.h"     (the snooker generation's kernel: a program that cannot be built for it fails here)
-//     #include "demcz_kernels_crossover.h"   (the crossover generation's kernel, in the same way)
-//     explicit instantiations of window_kernel<TARGET_PROGRAM, DEMCZ_D, true / false>, snooker_kernel<TARGET_PROGRAM, DEMCZ_D>,
-//     window_kernel_cr<TARGET_PROGRAM, DEMCZ_D>
-//     and logp_kernel<TARGET_PROGRAM>
-// The wave unit (UNIT_WAVE, handles created with DEMCZ_LAYOUT_PROGRAM_WAVE; composed and compiled only for them, cached under a
-// key of its own) has the same head, then
-//     #define ML_LRDPP 0 / PW_DDPP 0         (the generated DPP texts of the built-in targets are not part of the unit: the
-//                                             candidate adds read their increments from LDS -- the same doubles,
-//                                             tests/test_switch_variants.py -- and 54 generated files stay out of the library's
-//                                             text and out of every first-use compile)
-//     #include "demcz_kernels_pw.h"          (which brings _ps.h, _pc.h with the producer half, _ml.h, _rec.h, demcz_kernels.h)
-//     window_kernel_ps<TARGET_PROGRAM, DEMCZ_D, LIVE, TEMPER> (d <= 5) or window_kernel_pw<TARGET_PROGRAM, DEMCZ_D, LIVE, TEMPER>,
-//     LIVE and TEMPER both ways, and logp_kernel<TARGET_PROGRAM>
-// The derive unit (UNIT_DERIVE, demcz_derive): #define DEMCZ_D <d> / DEMCZ_M <m> / DEMCZ_DERIVE_UNIT, INFINITY and NAN, the
-// user's source (#line 1 "program"), #include "demcz_kernels_derive.h" and nothing else of the library: derive_kernel is its
-// only kernel, and the unit compiles in a fraction of the time a program target takes.
-// The pointwise unit (UNIT_POINTWISE, demcz_pointwise) is the derive unit with DEMCZ_POINTWISE_UNIT in place of DEMCZ_DERIVE_UNIT
-// and DEMCZ_M, the user's demcz_loglik, and demcz_kernels_pointwise.h (which includes demcz_kernels_derive.h for the launch
-// constants): pointwise_kernel is its only kernel.  Same options, same caches.
-// The bridge unit (UNIT_BRIDGE, demcz_bridge_proposal): DEMCZ_D, DEMCZ_BRIDGE_UNIT, the user's demcz_logobj exactly as a program
-// target defines it, then demcz_device.h (Philox, dm_log, the Box-Muller pair) and demcz_kernels_bridge.h, whose
-// bridge_proposal_program_kernel is its only kernel.  No struct of the library's is in it.  A key of its own in the same caches.
-// The predict unit (UNIT_PREDICT, demcz_predict and demcz_ppc): the derive unit's defines with DEMCZ_PREDICT_UNIT in place of
-// DEMCZ_DERIVE_UNIT, demcz_device.h, demcz_predict_rng.h (the demcz_rng of a draw and its four helpers), the user's demcz_predict
-// (#line 1 "program"), and demcz_kernels_predict.h with predict_kernel and ppc_kernel.  Same options, same caches, a key of its own.
-// Compile options: --offload-arch=gfx950 -O3 -ffp-contract=off -I<rocm>/include, the library's own layout switches (not for
-// the derive unit, which sees no struct of the library's), then the user's.  Code objects are cached per (composed text,
-// options), loaded modules per (code object, device); both for the life of the process.
+// What a unit consists of is its row of k_units (below); compose, compile, get_code and get_module read the row.  What the
+// table does not show:
+//   - the wave unit defines ML_LRDPP 0 / PW_DDPP 0: the generated DPP texts of the built-in targets are not part of the unit.  The
+//     candidate adds read their increments from LDS -- the same doubles, tests/test_switch_variants.py -- and 54 generated files
+//     stay out of the library's text and out of every first-use compile;
+//   - the streaming units (derive, pointwise, bridge, predict) get no layout switches: they see no struct of the library's;
+//   - the header texts are embedded into this library at build time, and the #line before the user's source gives compiler
+//     messages the user's own line numbers.
+// Compile options: --offload-arch=gfx950 -O3 -ffp-contract=off -I<rocm>/include, the library's own layout switches where the row
+// says so, then the user's.  Code objects are cached per (composed text, options) -- the text names the unit's kernel header and
+// DEMCZ_M, so every unit has keys of its own --, loaded modules per (code object, device); both for the life of the process.
 #include "demcz_program.h"
 
 #include <hip/hip_runtime.h>
@@ -71,7 +49,6 @@ const char k_snooker_h[] = {
 const char k_crossover_h[] = {
 #embed "demcz_kernels_crossover.h"
     , 0};
-// the wave unit's headers
 const char k_rec_h[] = {
 #embed "demcz_kernels_rec.h"
     , 0};
@@ -90,19 +67,15 @@ const char k_ps_h[] = {
 const char k_pw_h[] = {
 #embed "demcz_kernels_pw.h"
     , 0};
-// the derive unit's only header
 const char k_derive_h[] = {
 #embed "demcz_kernels_derive.h"
     , 0};
-// the pointwise unit's header (on top of the derive unit's)
 const char k_pointwise_h[] = {
 #embed "demcz_kernels_pointwise.h"
     , 0};
-// the bridge unit's header (on top of demcz_device.h and the derive unit's launch constants)
 const char k_bridge_h[] = {
 #embed "demcz_kernels_bridge.h"
     , 0};
-// the predict unit's headers (on top of demcz_device.h and the derive unit's launch constants)
 const char k_predict_rng_h[] = {
 #embed "demcz_predict_rng.h"
     , 0};
@@ -127,62 +100,138 @@ std::map<std::pair<const demcz_prog::Code*, int>, demcz_prog::Module> g_module_c
 // <math.h>'s INFINITY and NAN, which hipRTC's built-in headers leave undefined: a log-density with bounded support returns -INFINITY
 const char k_math_macros[] = "#ifndef INFINITY\n#define INFINITY (__builtin_inff())\n#endif\n#ifndef NAN\n#define NAN (__builtin_nanf(\"\"))\n#endif\n";
 
-std::string compose(int d, int m, const std::string& source, int unit)
+// ---- the units -----------------------------------------------------------------------------------------------------------------
+struct Header { const char* name; const char* text; };
+// A kernel of a unit: demcz::<name><targs>.  In targs {T} is the target and {d} the dimension -- 4 and the number in the name
+// expression, demcz::TARGET_PROGRAM and DEMCZ_D in the explicit instantiation --; {k} in the name is Unit::stem(d).
+struct Kernel { const char* name; const char* targs; const char* params; };
+struct Unit {
+    const char* tag;                        // in the name of the DEMCZ_PROGRAM_DUMP file
+    const char* name;                       // the #line name of what follows the user's source; with ".hip", the translation unit's
+    const char* who;                        // what an error message says first
+    bool has_m = false;                     // DEMCZ_M is defined after DEMCZ_D: m is validated and part of the key
+    const char* defines;                    // after DEMCZ_D (and DEMCZ_M)
+    const char* before = "";                // the includes before the user's source
+    const char* after;                      // the includes after it
+    std::vector<Header> headers;            // the embedded headers the unit is given
+    bool layout_switches = false;           // k_layout_switches are passed
+    int min_d = 1;
+    const char* min_d_what = "";            // what needs d >= min_d, for the message
+    std::vector<Kernel> kernels;            // in the order of the unit's indices in demcz_program.h
+    std::vector<int> instantiate = {};      // the kernels the text instantiates explicitly, in the text's order (the text is the cache
+                                            // key: the order stays as it grew)
+    const char* (*stem)(int d) = nullptr;   // {k}, where the kernel depends on d
+    const char* needle;                     // the entry point the user must define, as searched in the composed text (the library's own
+    const char* hint;                       // call is in an included header, not in the text); what a failed compile without it adds
+};
+
+const char k_logobj_hint[] = "; the program does not define demcz_logobj -- it must define "
+                             "__device__ double demcz_logobj(const double* x, const double* data, int64_t ndata)";
+const char k_window_params[] = "const demcz::WindowParams";
+const Kernel k_logp = {"logp_kernel", "<{T}>", "demcz::TargetParams, int, const double*, int64_t, int64_t, double*"};
+
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wc++20-designator"
+const Unit k_units[] = {
+    {   // UNIT_ONE_LANE: the one-lane window kernel, the snooker and the crossover generation's kernels (a program that cannot be
+        // built for them fails here) and logp_kernel
+        .tag = "lane", .name = "demcz_program_unit", .who = "program target: ",
+        .defines = "#define DEMCZ_PROGRAM_TARGET\n#define DEMCZ_NO_AUX_KERNELS\n",
+        .after = "#include \"demcz_kernels.h\"\n#include \"demcz_kernels_snooker.h\"\n#include \"demcz_kernels_crossover.h\"\n",
+        .headers = {{"demcz_device.h", k_device_h}, {"demcz_kernels.h", k_kernels_h}, {"demcz_kernels_snooker.h", k_snooker_h},
+                    {"demcz_kernels_crossover.h", k_crossover_h}},
+        .layout_switches = true,
+        .kernels = {{"window_kernel", "<{T}, {d}, true>", k_window_params},
+                    {"window_kernel", "<{T}, {d}, false>", k_window_params},
+                    {"snooker_kernel", "<{T}, {d}>", "const demcz::WindowParams, const demcz::SnookerParams"},
+                    {"window_kernel_cr", "<{T}, {d}>", "const demcz::WindowParams, const demcz::CrossoverParams"},
+                    k_logp},
+        .instantiate = {demcz_prog::LANE_FULL, demcz_prog::LANE_BLOCKS, demcz_prog::LANE_SNOOKER, demcz_prog::LANE_LOGP, demcz_prog::LANE_CROSSOVER},
+        .needle = "demcz_logobj", .hint = k_logobj_hint,
+    },
+    {   // UNIT_WAVE: the wave-per-chain consumers of the split layout, LIVE and TEMPER both ways, and logp_kernel; demcz_kernels_pw.h
+        // brings _ps.h, _pc.h with the producer half, _ml.h, _rec.h and demcz_kernels.h
+        .tag = "wave", .name = "demcz_program_wave_unit", .who = "program target: ",
+        .defines = "#define DEMCZ_PROGRAM_TARGET\n#define DEMCZ_NO_AUX_KERNELS\n#define ML_LRDPP 0\n#define PW_DDPP 0\n",
+        .after = "#include \"demcz_kernels_pw.h\"\n",
+        .headers = {{"demcz_device.h", k_device_h}, {"demcz_kernels.h", k_kernels_h}, {"demcz_kernels_rec.h", k_rec_h},
+                    {"demcz_kernels_ml.h", k_ml_h}, {"demcz_mlb_dpp_20_5.inc", k_mlb_inc}, {"demcz_kernels_pc.h", k_pc_h},
+                    {"demcz_kernels_ps.h", k_ps_h}, {"demcz_kernels_pw.h", k_pw_h}},
+        .layout_switches = true, .min_d = demcz_prog::WAVE_MIN_D, .min_d_what = "the wave-per-chain layout (DEMCZ_LAYOUT_PROGRAM_WAVE)",
+        .kernels = {{"{k}", "<{T}, {d}, false, false>", k_window_params}, {"{k}", "<{T}, {d}, false, true>", k_window_params},
+                    {"{k}", "<{T}, {d}, true, false>", k_window_params}, {"{k}", "<{T}, {d}, true, true>", k_window_params}, k_logp},
+        .instantiate = {0, 1, 2, 3, demcz_prog::WAVE_LOGP},
+        .stem = [](int d) { return d <= 5 ? "window_kernel_ps" : "window_kernel_pw"; },
+        .needle = "demcz_logobj", .hint = k_logobj_hint,
+    },
+    {   // UNIT_DERIVE: the user's demcz_derive and derive_kernel, nothing else of the library: it compiles in a fraction of the
+        // time a program target takes
+        .tag = "derive", .name = "demcz_unit_derive", .who = "derive program: ", .has_m = true,
+        .defines = "#define DEMCZ_DERIVE_UNIT\n",
+        .after = "#include \"demcz_kernels_derive.h\"\n",
+        .headers = {{"demcz_kernels_derive.h", k_derive_h}},
+        .kernels = {{"derive_kernel", "", nullptr}},
+        .needle = "demcz_derive",
+        .hint = "; the program does not define demcz_derive -- it must define "
+                "__device__ void demcz_derive(const double* x, double logp, const double* data, int64_t ndata, double* out)",
+    },
+    {   // UNIT_POINTWISE: the user's demcz_loglik and pointwise_kernel (its header includes the derive unit's for the launch constants)
+        .tag = "pointwise", .name = "demcz_unit_pointwise", .who = "pointwise program: ",
+        .defines = "#define DEMCZ_POINTWISE_UNIT\n",
+        .after = "#include \"demcz_kernels_pointwise.h\"\n",
+        .headers = {{"demcz_kernels_derive.h", k_derive_h}, {"demcz_kernels_pointwise.h", k_pointwise_h}},
+        .kernels = {{"pointwise_kernel", "", nullptr}},
+        .needle = "demcz_loglik",
+        .hint = "; the program does not define demcz_loglik -- it must define "
+                "__device__ double demcz_loglik(const double* x, const double* data, int64_t ndata, int64_t i)",
+    },
+    {   // UNIT_BRIDGE: the user's demcz_logobj exactly as a program target defines it, and bridge_proposal_program_kernel, whose
+        // header includes demcz_device.h (Philox, dm_log, the Box-Muller pair) itself
+        .tag = "bridge", .name = "demcz_unit_bridge", .who = "program target: ",
+        .defines = "#define DEMCZ_BRIDGE_UNIT\n",
+        .after = "#include \"demcz_kernels_bridge.h\"\n",
+        .headers = {{"demcz_device.h", k_device_h}, {"demcz_kernels_derive.h", k_derive_h}, {"demcz_kernels_bridge.h", k_bridge_h}},
+        .kernels = {{"bridge_proposal_program_kernel", "", nullptr}},
+        .needle = "demcz_logobj", .hint = k_logobj_hint,
+    },
+    {   // UNIT_PREDICT: the demcz_rng of a draw and its four helpers before the user's demcz_predict, then predict_kernel and ppc_kernel
+        .tag = "predict", .name = "demcz_unit_predict", .who = "predictive program: ", .has_m = true,
+        .defines = "#define DEMCZ_PREDICT_UNIT\n",
+        .before = "#include \"demcz_device.h\"\n#include \"demcz_predict_rng.h\"\n",
+        .after = "#include \"demcz_kernels_predict.h\"\n",
+        .headers = {{"demcz_device.h", k_device_h}, {"demcz_kernels_derive.h", k_derive_h}, {"demcz_predict_rng.h", k_predict_rng_h},
+                    {"demcz_kernels_predict.h", k_predict_h}},
+        .kernels = {{"predict_kernel", "", nullptr}, {"ppc_kernel", "", nullptr}},
+        .needle = "demcz_predict(",
+        .hint = "; the program does not define demcz_predict -- it must define "
+                "__device__ void demcz_predict(const double* x, double logp, const double* data, int64_t ndata, demcz_rng* rng, double* out)",
+    },
+};
+#pragma clang diagnostic pop
+static_assert(sizeof(k_units) / sizeof(k_units[0]) == demcz_prog::UNIT_COUNT, "one row per unit, in the order of the enum");
+
+// a kernel's name expression, or its explicit instantiation
+std::string kernel_text(const Unit& u, const Kernel& k, int d, bool instantiation)
+{
+    std::string s = std::string(instantiation ? "template __global__ void demcz::" : "&demcz::") + k.name + k.targs;
+    auto put = [&s](const std::string& what, const std::string& with) {
+        for (size_t p; (p = s.find(what)) != std::string::npos;) s.replace(p, what.size(), with);
+    };
+    if (u.stem) put("{k}", u.stem(d));
+    put("{T}", instantiation ? "demcz::TARGET_PROGRAM" : "4");
+    put("{d}", instantiation ? "DEMCZ_D" : std::to_string(d));
+    return instantiation ? s + "(" + k.params + ");\n" : s;
+}
+
+std::string compose(int d, int m, const std::string& source, const Unit& u)
 {
     std::ostringstream s;
-    if (unit == demcz_prog::UNIT_DERIVE) {
-        s << "#define DEMCZ_D " << d << "\n#define DEMCZ_M " << m << "\n#define DEMCZ_DERIVE_UNIT\n"
-          << "#include <hip/hip_runtime.h>\n#include <stdint.h>\n" << k_math_macros
-          << "#line 1 \"program\"\n" << source << "\n"
-          << "#line 1 \"demcz_unit_derive\"\n#include \"demcz_kernels_derive.h\"\n";
-        return s.str();
-    }
-    if (unit == demcz_prog::UNIT_POINTWISE) {
-        s << "#define DEMCZ_D " << d << "\n#define DEMCZ_POINTWISE_UNIT\n"
-          << "#include <hip/hip_runtime.h>\n#include <stdint.h>\n" << k_math_macros
-          << "#line 1 \"program\"\n" << source << "\n"
-          << "#line 1 \"demcz_unit_pointwise\"\n#include \"demcz_kernels_pointwise.h\"\n";
-        return s.str();
-    }
-    if (unit == demcz_prog::UNIT_BRIDGE) {
-        s << "#define DEMCZ_D " << d << "\n#define DEMCZ_BRIDGE_UNIT\n"
-          << "#include <hip/hip_runtime.h>\n#include <stdint.h>\n" << k_math_macros
-          << "#line 1 \"program\"\n" << source << "\n"
-          << "#line 1 \"demcz_unit_bridge\"\n#include \"demcz_kernels_bridge.h\"\n";
-        return s.str();
-    }
-    if (unit == demcz_prog::UNIT_PREDICT) {
-        s << "#define DEMCZ_D " << d << "\n#define DEMCZ_M " << m << "\n#define DEMCZ_PREDICT_UNIT\n"
-          << "#include <hip/hip_runtime.h>\n#include <stdint.h>\n" << k_math_macros
-          << "#include \"demcz_device.h\"\n#include \"demcz_predict_rng.h\"\n"
-          << "#line 1 \"program\"\n" << source << "\n"
-          << "#line 1 \"demcz_unit_predict\"\n#include \"demcz_kernels_predict.h\"\n";
-        return s.str();
-    }
-    if (unit == demcz_prog::UNIT_WAVE) {
-        const char* kn = (d <= 5) ? "window_kernel_ps" : "window_kernel_pw";
-        s << "#define DEMCZ_D " << d << "\n#define DEMCZ_PROGRAM_TARGET\n#define DEMCZ_NO_AUX_KERNELS\n#define ML_LRDPP 0\n#define PW_DDPP 0\n"
-          << "#include <hip/hip_runtime.h>\n#include <stdint.h>\n" << k_math_macros
-          << "#line 1 \"program\"\n" << source << "\n"
-          << "#line 1 \"demcz_program_wave_unit\"\n#include \"demcz_kernels_pw.h\"\n";
-        for (int live = 0; live < 2; ++live)
-            for (int temper = 0; temper < 2; ++temper)
-                s << "template __global__ void demcz::" << kn << "<demcz::TARGET_PROGRAM, DEMCZ_D, " << (live ? "true" : "false") << ", "
-                  << (temper ? "true" : "false") << ">(const demcz::WindowParams);\n";
-        s << "template __global__ void demcz::logp_kernel<demcz::TARGET_PROGRAM>(demcz::TargetParams, int, const double*, int64_t, "
-             "int64_t, double*);\n";
-        return s.str();
-    }
-    s << "#define DEMCZ_D " << d << "\n#define DEMCZ_PROGRAM_TARGET\n#define DEMCZ_NO_AUX_KERNELS\n"
-      << "#include <hip/hip_runtime.h>\n#include <stdint.h>\n" << k_math_macros
+    s << "#define DEMCZ_D " << d << "\n";
+    if (u.has_m) s << "#define DEMCZ_M " << m << "\n";
+    s << u.defines << "#include <hip/hip_runtime.h>\n#include <stdint.h>\n" << k_math_macros << u.before
       << "#line 1 \"program\"\n" << source << "\n"
-      << "#line 1 \"demcz_program_unit\"\n#include \"demcz_kernels.h\"\n#include \"demcz_kernels_snooker.h\"\n#include \"demcz_kernels_crossover.h\"\n"
-      << "template __global__ void demcz::window_kernel<demcz::TARGET_PROGRAM, DEMCZ_D, true>(const demcz::WindowParams);\n"
-      << "template __global__ void demcz::window_kernel<demcz::TARGET_PROGRAM, DEMCZ_D, false>(const demcz::WindowParams);\n"
-      << "template __global__ void demcz::snooker_kernel<demcz::TARGET_PROGRAM, DEMCZ_D>(const demcz::WindowParams, const demcz::SnookerParams);\n"
-      << "template __global__ void demcz::logp_kernel<demcz::TARGET_PROGRAM>(demcz::TargetParams, int, const double*, int64_t, "
-         "int64_t, double*);\n";
-    s << "template __global__ void demcz::window_kernel_cr<demcz::TARGET_PROGRAM, DEMCZ_D>(const demcz::WindowParams, const demcz::CrossoverParams);\n";
+      << "#line 1 \"" << u.name << "\"\n" << u.after;
+    for (int i : u.instantiate) s << kernel_text(u, u.kernels[i], d, true);
     return s.str();
 }
 
@@ -240,54 +289,18 @@ std::string trim_log(std::string log)
         }                                                                                        \
     } while (0)
 
-// what a failed call says first: which of the two kinds of program it was about
-const char* who_of(int unit)
-{
-    return unit == demcz_prog::UNIT_DERIVE ? "derive program: " : unit == demcz_prog::UNIT_POINTWISE ? "pointwise program: " :
-           unit == demcz_prog::UNIT_PREDICT ? "predictive program: " : "program target: ";
-}
-
 bool compile(const std::string& text, const std::vector<std::string>& opts, int d, int m, int unit, demcz_prog::Code& code, std::string& err)
 {
+    const Unit& u = k_units[unit];
     hiprtcProgram prog = nullptr;
-    const std::string who = who_of(unit);
-    const char* headers[] = {k_device_h, k_kernels_h, k_rec_h, k_ml_h, k_mlb_inc, k_pc_h, k_ps_h, k_pw_h};
-    const char* names[] = {"demcz_device.h", "demcz_kernels.h", "demcz_kernels_rec.h", "demcz_kernels_ml.h", "demcz_mlb_dpp_20_5.inc",
-                           "demcz_kernels_pc.h", "demcz_kernels_ps.h", "demcz_kernels_pw.h"};
-    const bool pointwise = unit == demcz_prog::UNIT_POINTWISE, bridge = unit == demcz_prog::UNIT_BRIDGE, predict = unit == demcz_prog::UNIT_PREDICT;
-    const bool wave = unit == demcz_prog::UNIT_WAVE, derive = unit == demcz_prog::UNIT_DERIVE || pointwise || bridge || predict;   // (derive: a streaming unit)
-    const char* lane_headers[] = {k_device_h, k_kernels_h, k_snooker_h, k_crossover_h};
-    const char* lane_names[] = {"demcz_device.h", "demcz_kernels.h", "demcz_kernels_snooker.h", "demcz_kernels_crossover.h"};
-    const char* derive_headers[] = {k_derive_h};
-    const char* derive_names[] = {"demcz_kernels_derive.h"};
-    const char* pointwise_headers[] = {k_derive_h, k_pointwise_h};
-    const char* pointwise_names[] = {"demcz_kernels_derive.h", "demcz_kernels_pointwise.h"};
-    const char* bridge_headers[] = {k_device_h, k_derive_h, k_bridge_h};
-    const char* bridge_names[] = {"demcz_device.h", "demcz_kernels_derive.h", "demcz_kernels_bridge.h"};
-    const char* predict_headers[] = {k_device_h, k_derive_h, k_predict_rng_h, k_predict_h};
-    const char* predict_names[] = {"demcz_device.h", "demcz_kernels_derive.h", "demcz_predict_rng.h", "demcz_kernels_predict.h"};
-    if (predict) RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_unit_predict.hip", 4, predict_headers, predict_names));
-    else if (bridge) RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_unit_bridge.hip", 3, bridge_headers, bridge_names));
-    else if (pointwise) RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_unit_pointwise.hip", 2, pointwise_headers, pointwise_names));
-    else if (derive) RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_unit_derive.hip", 1, derive_headers, derive_names));
-    else if (wave) RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_program_wave_unit.hip", 8, headers, names));
-    else RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), "demcz_program_unit.hip", 4, lane_headers, lane_names));
+    const std::string who = u.who;
+    std::vector<const char*> headers, names;
+    for (const Header& h : u.headers) { headers.push_back(h.text); names.push_back(h.name); }
+    const std::string tu = std::string(u.name) + ".hip";
+    RTCCHK(hiprtcCreateProgram(&prog, text.c_str(), tu.c_str(), (int)headers.size(), headers.data(), names.data()));
     struct Guard { hiprtcProgram& p; ~Guard() { if (p) (void)hiprtcDestroyProgram(&p); } } guard{prog};
-    const std::string ds = std::to_string(d);
     std::vector<std::string> exprs;
-    if (derive) {
-        exprs = {predict ? "&demcz::predict_kernel" : bridge ? "&demcz::bridge_proposal_program_kernel" : pointwise ? "&demcz::pointwise_kernel" : "&demcz::derive_kernel"};
-        if (predict) exprs.push_back("&demcz::ppc_kernel");
-    } else if (wave) {
-        const std::string kn = (d <= 5) ? "&demcz::window_kernel_ps<4, " : "&demcz::window_kernel_pw<4, ";
-        for (int live = 0; live < 2; ++live)
-            for (int temper = 0; temper < 2; ++temper)
-                exprs.push_back(kn + ds + (live ? ", true" : ", false") + (temper ? ", true>" : ", false>"));
-    } else {
-        exprs = {"&demcz::window_kernel<4, " + ds + ", true>", "&demcz::window_kernel<4, " + ds + ", false>", "&demcz::snooker_kernel<4, " + ds + ">",
-                 "&demcz::window_kernel_cr<4, " + ds + ">"};
-    }
-    if (!derive) exprs.push_back("&demcz::logp_kernel<4>");
+    for (const Kernel& k : u.kernels) exprs.push_back(kernel_text(u, k, d, false));
     for (const auto& e : exprs) RTCCHK(hiprtcAddNameExpression(prog, e.c_str()));
     std::vector<const char*> argv;
     for (const auto& o : opts) argv.push_back(o.c_str());
@@ -301,18 +314,7 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
             while (!log.empty() && log.back() == '\0') log.pop_back();
         }
         err = who + "compilation failed (" + std::string(hiprtcGetErrorString(rc)) + ")";
-        if ((!derive || bridge) && text.find("demcz_logobj") == std::string::npos)   // (the library's own call is in demcz_kernels.h, not in `text`)
-            err += "; the program does not define demcz_logobj -- it must define "
-                   "__device__ double demcz_logobj(const double* x, const double* data, int64_t ndata)";
-        if (pointwise && text.find("demcz_loglik") == std::string::npos)
-            err += "; the program does not define demcz_loglik -- it must define "
-                   "__device__ double demcz_loglik(const double* x, const double* data, int64_t ndata, int64_t i)";
-        if (predict && text.find("demcz_predict(") == std::string::npos)    // (the unit's headers are included, not in `text`)
-            err += "; the program does not define demcz_predict -- it must define "
-                   "__device__ void demcz_predict(const double* x, double logp, const double* data, int64_t ndata, demcz_rng* rng, double* out)";
-        if (derive && !pointwise && !bridge && !predict && text.find("demcz_derive") == std::string::npos)    // (... and derive_kernel's in demcz_kernels_derive.h)
-            err += "; the program does not define demcz_derive -- it must define "
-                   "__device__ void demcz_derive(const double* x, double logp, const double* data, int64_t ndata, double* out)";
+        if (text.find(u.needle) == std::string::npos) err += u.hint;
         err += ":\n" + trim_log(log);
         return false;
     }
@@ -322,19 +324,14 @@ bool compile(const std::string& text, const std::vector<std::string>& opts, int 
     RTCCHK(hiprtcGetCode(prog, code.object.data()));
     if (const char* dump = getenv("DEMCZ_PROGRAM_DUMP"); dump && *dump) {
         // diagnosis (scripts/kernel_regs.py, llvm-objdump): the code object as a file in that directory
-        const std::string path = std::string(dump) + "/demcz_program_" + (predict ? "predict" : bridge ? "bridge" : pointwise ? "pointwise" : derive ? "derive" : wave ? "wave" : "lane") + "_d" + ds + "_" +
+        const std::string path = std::string(dump) + "/demcz_program_" + u.tag + "_d" + std::to_string(d) + "_" +
                                  std::to_string(std::hash<std::string>{}(text) % 1000000007ull) + ".co";
         if (FILE* f = fopen(path.c_str(), "wb")) { (void)fwrite(code.object.data(), 1, code.object.size(), f); fclose(f); }
     }
-    std::vector<std::string*> lowered;
-    if (predict) lowered = {&code.derive, &code.ppc};
-    else if (derive) lowered = {&code.derive};
-    else if (wave) lowered = {&code.wave[0][0], &code.wave[0][1], &code.wave[1][0], &code.wave[1][1], &code.logp};
-    else lowered = {&code.window_full, &code.window_blocks, &code.snooker, &code.crossover, &code.logp};
-    for (size_t i = 0; i < lowered.size(); ++i) {
+    for (size_t i = 0; i < exprs.size(); ++i) {
         const char* nm = nullptr;
         RTCCHK(hiprtcGetLoweredName(prog, exprs[i].c_str(), &nm));
-        *lowered[i] = nm;
+        code.names[i] = nm;
     }
     code.d = d;
     code.m = m;
@@ -349,22 +346,22 @@ namespace demcz_prog {
 
 int32_t get_code(int d, const char* source, const char* options, int unit, std::shared_ptr<const Code>& out, std::string& err, int m)
 {
-    if (unit != UNIT_ONE_LANE && unit != UNIT_WAVE && unit != UNIT_DERIVE && unit != UNIT_POINTWISE && unit != UNIT_BRIDGE && unit != UNIT_PREDICT) {
+    if (unit < 0 || unit >= UNIT_COUNT) {
         err = "program target: lanes_per_chain must be 0, 1 or DEMCZ_LAYOUT_PROGRAM_WAVE";
         return 1;
     }
-    const std::string who = who_of(unit);
+    const Unit& u = k_units[unit];
+    const std::string who = u.who;
     if (d < 1 || d > MAX_PROGRAM_D) {
         err = who + "d must be in 1.." + std::to_string(MAX_PROGRAM_D);
         return 1;
     }
-    if ((unit == UNIT_DERIVE || unit == UNIT_PREDICT) && (m < 1 || m > MAX_DERIVE_M)) {
+    if (u.has_m && (m < 1 || m > MAX_DERIVE_M)) {
         err = who + "m must be in 1.." + std::to_string(MAX_DERIVE_M);
         return 1;
     }
-    if (unit == UNIT_WAVE && d < WAVE_MIN_D) {
-        err = "program target: the wave-per-chain layout (DEMCZ_LAYOUT_PROGRAM_WAVE) needs d in " + std::to_string(WAVE_MIN_D) + ".." +
-              std::to_string(MAX_PROGRAM_D);
+    if (d < u.min_d) {
+        err = who + u.min_d_what + " needs d in " + std::to_string(u.min_d) + ".." + std::to_string(MAX_PROGRAM_D);
         return 1;
     }
     if (!source) {
@@ -374,11 +371,10 @@ int32_t get_code(int d, const char* source, const char* options, int unit, std::
     std::string inc;
     if (!rocm_include(inc, err)) return 1;
     std::vector<std::string> opts = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-I" + inc};
-    if (unit != UNIT_DERIVE && unit != UNIT_POINTWISE && unit != UNIT_BRIDGE && unit != UNIT_PREDICT)
+    if (u.layout_switches)
         for (const char* const* s = k_layout_switches; *s; ++s) opts.push_back(*s);
     for (auto& o : split_options(options)) opts.push_back(o);
-    // (the text is the key: it names the unit's kernel header and, for a derive unit, DEMCZ_M)
-    const std::string text = compose(d, m, source, unit);
+    const std::string text = compose(d, m, source, u);
     std::string key = text;
     for (const auto& o : opts) key += '\0' + o;
     {
@@ -400,27 +396,14 @@ int32_t get_module(const std::shared_ptr<const Code>& code, int device, Module& 
     const auto key = std::make_pair(code.get(), device);
     auto it = g_module_cache.find(key);
     if (it != g_module_cache.end()) { out = it->second; return 0; }
+    const Unit& u = k_units[code->unit];
     Module m;
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipModuleLoadData(&m.module, code->object.data());
-    const bool streaming = code->unit == UNIT_DERIVE || code->unit == UNIT_POINTWISE || code->unit == UNIT_BRIDGE || code->unit == UNIT_PREDICT;
-    if (streaming) {
-        if (e == hipSuccess) e = hipModuleGetFunction(&m.derive, m.module, code->derive.c_str());
-        if (e == hipSuccess && code->unit == UNIT_PREDICT) e = hipModuleGetFunction(&m.ppc, m.module, code->ppc.c_str());
-    } else if (code->unit == UNIT_WAVE) {
-        for (int live = 0; live < 2; ++live)
-            for (int temper = 0; temper < 2; ++temper)
-                if (e == hipSuccess) e = hipModuleGetFunction(&m.wave[live][temper], m.module, code->wave[live][temper].c_str());
-    } else {
-        if (e == hipSuccess) e = hipModuleGetFunction(&m.window_full, m.module, code->window_full.c_str());
-        if (e == hipSuccess) e = hipModuleGetFunction(&m.window_blocks, m.module, code->window_blocks.c_str());
-        if (e == hipSuccess) e = hipModuleGetFunction(&m.snooker, m.module, code->snooker.c_str());
-        if (e == hipSuccess) e = hipModuleGetFunction(&m.crossover, m.module, code->crossover.c_str());
-    }
-    if (!streaming && e == hipSuccess) e = hipModuleGetFunction(&m.logp, m.module, code->logp.c_str());
+    for (size_t i = 0; i < u.kernels.size() && e == hipSuccess; ++i) e = hipModuleGetFunction(&m.fn[i], m.module, code->names[i].c_str());
     if (e != hipSuccess) {
         if (m.module) (void)hipModuleUnload(m.module);
-        err = std::string(who_of(code->unit)) + "loading the code object: " + hipGetErrorString(e);
+        err = std::string(u.who) + "loading the code object: " + hipGetErrorString(e);
         return 2;
     }
     m.code = code;          // (the cache keeps the code object alive with the module)

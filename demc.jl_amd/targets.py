@@ -97,7 +97,31 @@ class LinRegSSETarget:
         return dict(kind="linreg_sse", design=self.design, y=self.y)
 
 
-class ProgramTarget:
+class _Program:
+    """What the program classes share: the normalised ``source`` / ``d`` / ``data`` / ``options``, the arguments as the C ABI takes
+    them, and the compile-only check."""
+
+    def _set_program(self, source, d, data, options):
+        self.source = str(source)
+        self.d = int(d)
+        self.data = None if data is None else np.ascontiguousarray(np.ravel(data), dtype=np.float64)
+        self.options = (options,) if isinstance(options, str) else tuple(str(o) for o in options)
+
+    def _args(self):
+        """(source, options, data pointer or None, ndata) as the C ABI takes them; the data array is kept alive by self."""
+        n = 0 if self.data is None else self.data.size
+        return self.source.encode(), " ".join(self.options).encode(), (_lib.ptr(self.data) if n else None), n
+
+    def _check(self, name, *mid, tail=()):
+        """Call the library's ``name(d, *mid, source, options, *tail)``; raises ``DemczError`` with the last error if it refuses."""
+        L = _lib.load()
+        src, opts = _Program._args(self)[:2]
+        rc = getattr(L, name)(self.d, *mid, src, opts, *tail)
+        if rc != 0:
+            raise _lib.DemczError(rc, (L.demcz_last_error(None) or b"").decode())
+
+
+class ProgramTarget(_Program):
     """A log-density written as HIP C++ and compiled for the device at run time (``demcz_set_program``, include/demcz.h).
 
     ``source`` defines ``__device__ double demcz_logobj(const double* x, const double* data, int64_t ndata)``: ``x`` holds the
@@ -113,45 +137,35 @@ class ProgramTarget:
     kind = _lib.TARGET_PROGRAM
 
     def __init__(self, source: str, d: int, data=None, options=()):
-        self.source = str(source)
-        self.d = int(d)
-        self.data = None if data is None else np.ascontiguousarray(np.ravel(data), dtype=np.float64)
-        self.options = (options,) if isinstance(options, str) else tuple(str(o) for o in options)
+        self._set_program(source, d, data, options)
 
     def _args(self):
-        return self.source.encode(), " ".join(self.options).encode()
+        return super()._args()[:2]
 
     def check(self, layout=None):
         """Compile the program (no device needed); raises ``DemczError`` with the compiler log if it does not compile.
         ``layout``: the ``lanes_per_chain`` the handle will be created with -- ``demc.LAYOUT_PROGRAM_WAVE`` compiles the unit of the
         wave-per-chain layout (d in 2..32), where a program that needs many registers or does not inline shows it; None, 0 or 1 the
         one-lane unit."""
-        L = _lib.load()
-        src, opts = self._args()
-        rc = L.demcz_program_check(self.d, src, opts) if layout is None else L.demcz_program_check_layout(self.d, src, opts, int(layout))
-        if rc != 0:
-            raise _lib.DemczError(rc, (L.demcz_last_error(None) or b"").decode())
+        if layout is None:
+            self._check("demcz_program_check")
+        else:
+            self._check("demcz_program_check_layout", tail=(int(layout),))
 
     def check_bridge(self):
         """Compile the program's bridge-sampling unit (``demcz_bridge_check``; no device needed): what ``HipEngine.bridge`` and
         ``demc.bridge_chain`` compile on first use.  Raises ``DemczError`` with the compiler log if it does not compile."""
-        L = _lib.load()
-        src, opts = self._args()
-        rc = L.demcz_bridge_check(self.d, src, opts)
-        if rc != 0:
-            raise _lib.DemczError(rc, (L.demcz_last_error(None) or b"").decode())
+        self._check("demcz_bridge_check")
 
     def fill(self, cfg, keep):
         pass                # (the program and its data go to the handle after demcz_create: attach)
 
     def attach(self, L, h):
         """``demcz_set_program`` on a freshly created handle; returns the status."""
-        src, opts = self._args()
-        n = 0 if self.data is None else self.data.size
-        return L.demcz_set_program(h, src, opts, _lib.ptr(self.data) if n else None, n)
+        return L.demcz_set_program(h, *super()._args())
 
 
-class DerivedProgram:
+class DerivedProgram(_Program):
     """``m`` functions of every draw, written as HIP C++ and run on the device over a history (``demcz_derive``, include/demcz.h):
     what Stan calls generated quantities.
 
@@ -169,26 +183,15 @@ class DerivedProgram:
     """
 
     def __init__(self, source: str, d: int, m: int, data=None, options=(), names=None):
-        self.source = str(source)
-        self.d, self.m = int(d), int(m)
-        self.data = None if data is None else np.ascontiguousarray(np.ravel(data), dtype=np.float64)
-        self.options = (options,) if isinstance(options, str) else tuple(str(o) for o in options)
+        self._set_program(source, d, data, options)
+        self.m = int(m)
         self.names = None if names is None else [str(n) for n in names]
         if self.names is not None and len(self.names) != self.m:
             raise ValueError("names must hold m labels")
 
-    def _args(self):
-        """(source, options, data pointer or None, ndata) as the C ABI takes them; the data array is kept alive by self."""
-        n = 0 if self.data is None else self.data.size
-        return self.source.encode(), " ".join(self.options).encode(), (_lib.ptr(self.data) if n else None), n
-
     def check(self):
         """Compile the program (no device needed); raises ``DemczError`` with the compiler log if it does not compile."""
-        L = _lib.load()
-        src, opts, _, _ = self._args()
-        rc = L.demcz_derive_check(self.d, self.m, src, opts)
-        if rc != 0:
-            raise _lib.DemczError(rc, (L.demcz_last_error(None) or b"").decode())
+        self._check("demcz_derive_check", self.m)
 
 
 class PredictiveProgram(DerivedProgram):
@@ -211,14 +214,10 @@ class PredictiveProgram(DerivedProgram):
 
     def check(self):
         """Compile the program (no device needed); raises ``DemczError`` with the compiler log if it does not compile."""
-        L = _lib.load()
-        src, opts, _, _ = self._args()
-        rc = L.demcz_predict_check(self.d, self.m, src, opts)
-        if rc != 0:
-            raise _lib.DemczError(rc, (L.demcz_last_error(None) or b"").decode())
+        self._check("demcz_predict_check", self.m)
 
 
-class PointwiseProgram:
+class PointwiseProgram(_Program):
     """The log-likelihood of every observation at a draw, written as HIP C++ and run on the device over a history
     (``demcz_pointwise`` and ``demcz_loo``, include/demcz.h): the input of PSIS-LOO and WAIC.
 
@@ -234,28 +233,17 @@ class PointwiseProgram:
     """
 
     def __init__(self, source: str, d: int, nobs: int, data=None, options=(), names=None):
-        self.source = str(source)
-        self.d, self.nobs = int(d), int(nobs)
+        self._set_program(source, d, data, options)
+        self.nobs = int(nobs)
         if self.nobs < 1:
             raise ValueError("nobs must be at least 1")
-        self.data = None if data is None else np.ascontiguousarray(np.ravel(data), dtype=np.float64)
-        self.options = (options,) if isinstance(options, str) else tuple(str(o) for o in options)
         self.names = None if names is None else [str(n) for n in names]
         if self.names is not None and len(self.names) != self.nobs:
             raise ValueError("names must hold nobs labels")
 
-    def _args(self):
-        """(source, options, data pointer or None, ndata) as the C ABI takes them; the data array is kept alive by self."""
-        n = 0 if self.data is None else self.data.size
-        return self.source.encode(), " ".join(self.options).encode(), (_lib.ptr(self.data) if n else None), n
-
     def check(self):
         """Compile the program (no device needed); raises ``DemczError`` with the compiler log if it does not compile."""
-        L = _lib.load()
-        src, opts, _, _ = self._args()
-        rc = L.demcz_pointwise_check(self.d, src, opts)
-        if rc != 0:
-            raise _lib.DemczError(rc, (L.demcz_last_error(None) or b"").decode())
+        self._check("demcz_pointwise_check")
 
 
 def is_device_target(obj) -> bool:
