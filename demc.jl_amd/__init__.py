@@ -10,7 +10,7 @@ All computation below the generation loop runs in ``libdemcz_hip.so`` (HIP, gfx9
 C ABI of ``include/demcz.h``; there is no CPU fallback.
 """
 from ._lib import DemczError, build, LIB_PATH, SYMBOLS, LAYOUT_SPLIT, LAYOUT_SPLIT_WAVE, LAYOUT_PROGRAM_WAVE          # noqa: F401
-from .engine import (HipEngine, DerivedHistory, selftest_draws, pool_trim, ESS, ess_from_sums, Quantiles, Best, quantile_plan, PPC, ppc_record,
+from .engine import (HipEngine, CrossoverAdapt, DerivedHistory, selftest_draws, pool_trim, ESS, ess_from_sums, Quantiles, Best, quantile_plan, PPC, ppc_record,
                      select_step, quantile_finish, select_quantiles, RankDiagnostics, rank_to_z,
                      Histogram, Histogram2D, histogram_edges, hdi_steps,
                      LOO, loo_record, loo_compare, psis_tail_length, gpd_fit,

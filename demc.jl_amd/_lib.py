@@ -64,6 +64,7 @@ SYMBOLS = [
     "demcz_histogram_edges", "demcz_histogram", "demcz_histogram_array", "demcz_histogram2d", "demcz_histogram2d_array",
     "demcz_hdi_steps", "demcz_hdi", "demcz_hdi_array",
     "demcz_set_crossover", "demcz_get_crossover",
+    "demcz_set_crossover_adapt", "demcz_get_crossover_adapt", "demcz_set_crossover_adapt_state", "demcz_set_crossover_weights",
 ]
 
 
@@ -94,11 +95,12 @@ def sources() -> list:
     window_kernel_pw for every dimension from 6 to 32 (demcz_pw_inst_<g>.hip, csrc/demcz_pw_dispatch.h), the two with the
     sixteen-lane regression kernels for every dimension from 2 to 28 (demcz_mlr_inst_<g>.hip, csrc/demcz_mlr_dispatch.h), the one
     with the snooker generation's kernels (demcz_snooker_inst.hip, csrc/demcz_kernels_snooker.h), the one with the crossover
-    generation's (demcz_crossover_inst.hip, csrc/demcz_kernels_crossover.h), the one with the bridge-sampling
+    generation's (demcz_crossover_inst.hip, csrc/demcz_kernels_crossover.h) and the one with their twins that adapt the class
+    weights (demcz_crossover_adapt_inst.hip), the one with the bridge-sampling
     kernels for every dimension from 1 to 32 (demcz_bridge_inst.hip, csrc/demcz_kernels_bridge.h) and the host code of program targets (demcz_program.hip: hipRTC, the kernel headers embedded as text)."""
     csrc = PKG_DIR / "csrc"
     return ([csrc / "demcz_capi.hip"] + sorted(csrc.glob("demcz_pw_inst_*.hip")) + sorted(csrc.glob("demcz_mlr_inst_*.hip"))
-            + [csrc / "demcz_snooker_inst.hip", csrc / "demcz_crossover_inst.hip", csrc / "demcz_bridge_inst.hip", csrc / "demcz_program.hip"])
+            + [csrc / "demcz_snooker_inst.hip", csrc / "demcz_crossover_inst.hip", csrc / "demcz_crossover_adapt_inst.hip", csrc / "demcz_bridge_inst.hip", csrc / "demcz_program.hip"])
 
 
 def build_command(out: Path = LIB_PATH) -> list:
@@ -185,6 +187,10 @@ def load():
     L.demcz_get_snooker.argtypes = [C.c_void_p, _ip, _dp, _dp, _lp]
     L.demcz_set_crossover.argtypes = [C.c_void_p, C.c_int32, _ip, C.c_int32]
     L.demcz_get_crossover.argtypes = [C.c_void_p, _ip, _ip, _ip, _lp, _lp]
+    L.demcz_set_crossover_adapt.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32]
+    L.demcz_get_crossover_adapt.argtypes = [C.c_void_p, _lp, _lp, _ip, _ip, _lp, _lp, _dp, _lp]
+    L.demcz_set_crossover_adapt_state.argtypes = [C.c_void_p, _ip, _lp, _lp, _dp, C.c_int64]
+    L.demcz_set_crossover_weights.argtypes = [C.c_void_p, _ip]
     L.demcz_set_append_lag.argtypes = [C.c_void_p, C.c_int32]
     L.demcz_rhat_array.argtypes = [C.c_int32, _dp, C.c_int64, C.c_int32, C.c_int64, _dp]
     L.demcz_autocov_sums.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _dp]

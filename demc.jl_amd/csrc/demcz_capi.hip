@@ -183,6 +183,7 @@ struct WindowKernel {
     KernelArm arm = ARM_ONE_LANE;
     bool live = false, temper = false;
     int pw_form = 0;                // ARM_PW: PW_FORM_*
+    bool adapt = false;             // ARM_CROSSOVER: the ADAPT instantiation, with its third kernel argument
 };
 
 // What window_kernel_of() is told about one launch, beside the handle's own layout
@@ -197,6 +198,7 @@ struct LaunchFacts {
     bool lr16 = false;        // uses_lr16(h)
     bool snooker = false;     // the launch is one snooker generation (LaunchPlan::snooker)
     bool crossover = false;   // the launch's generations are crossover generations (demcz_set_crossover; not a snooker launch)
+    bool adapt = false;       // ... of a handle with demcz_set_crossover_adapt: the ADAPT instantiation, for life
 };
 
 // A replica group of one process (demcz_peer_group): R handles on one device, each with its own archive replica and shard of
@@ -443,7 +445,19 @@ struct demcz_handle {
     int32_t cr_weights[CR_MAX_CLASSES] = {1, 1, 1, 1, 1, 1, 1, 1};
     unsigned long long* d_cr_counts = nullptr;      // [workgroup][8][2], zeroed when crossover is switched on
     int64_t S_plain = 0;
+    // adaptation of the class weights during burn-in (demcz_set_crossover_adapt): cr_adapt_every == 0: off.
+    // The state lives on the device, in one block (CRA_*): the kernels read and write it with no host in between.
+    int64_t cr_adapt_every = 0, cr_adapt_until = 0;
+    int32_t cr_adapt_min_weight = 656;
+    unsigned char* d_cr_adapt = nullptr;
+    bool cr_adapt_started = false;    // rsd has been computed (the first demcz_run) or restored (demcz_set_crossover_adapt_state)
+    bool cr_accumulate_now = false;   // the launch being prepared lies at or in front of `until`
 };
+
+// the block behind demcz_handle::d_cr_adapt, in bytes: weights[8] (int32), cum[8] (uint32), updates (int64), rsd[MAX_D], slots[nwg][8][2]
+constexpr size_t CRA_WEIGHTS = 0, CRA_CUM = 32, CRA_UPDATES = 64, CRA_RSD = 128, CRA_SLOTS = CRA_RSD + 8 * MAX_D;
+static size_t cra_workgroups(const demcz_handle* h) { return (size_t)((h->cfg.N + WINDOW_BS - 1) / WINDOW_BS); }
+static size_t cra_bytes(const demcz_handle* h) { return CRA_SLOTS + cra_workgroups(h) * 2 * CR_MAX_CLASSES * sizeof(unsigned long long); }
 
 #define HIPCHK(h, expr)                                                                          \
     do {                                                                                         \
@@ -738,6 +752,7 @@ static void free_all(demcz_handle* h)
         if (st && hipStreamQuery(st) != hipSuccess) drained = false;
     if (h->d_acc) (void)dev_free(h->cfg.device_id, h->d_acc);
     if (h->d_cr_counts) (void)dev_free(h->cfg.device_id, h->d_cr_counts);
+    if (h->d_cr_adapt) (void)dev_free(h->cfg.device_id, h->d_cr_adapt);
     if (h->d_err_all) (void)dev_free(h->cfg.device_id, h->d_err_all);
     if (h->archive_fine) { if (h->dZ) (void)hipFree(h->dZ); h->dZ = nullptr; }     // (an allocation of its own: demcz_comm_init)
     if (h->pooled_dev) {               // (the two big ones)
@@ -1523,7 +1538,15 @@ static int32_t launch_kernel(demcz_handle* h, const WindowKernel& k, int64_t blo
     // (a snooker launch has a second argument; a kernel that takes one never looks at the other)
     SnookerParams sp{h->snooker_lo, h->snooker_hi};
     CrossoverParams cp = crossover_params(h);
-    void* args[] = {const_cast<WindowParams*>(&P), k.arm == ARM_CROSSOVER ? (void*)&cp : (void*)&sp};
+    // (an ADAPT crossover launch has a third: where the weights, the spread and the slots of the adaptation are on the device)
+    CrossoverAdaptParams ap{};
+    if (k.adapt) {
+        ap.cum = reinterpret_cast<const uint32_t*>(h->d_cr_adapt + CRA_CUM);
+        ap.rsd = reinterpret_cast<const double*>(h->d_cr_adapt + CRA_RSD);
+        ap.slots = reinterpret_cast<unsigned long long*>(h->d_cr_adapt + CRA_SLOTS);
+        ap.accumulate = h->cr_accumulate_now ? 1 : 0;
+    }
+    void* args[] = {const_cast<WindowParams*>(&P), k.arm == ARM_CROSSOVER ? (void*)&cp : (void*)&sp, (void*)&ap};
     if (k.mod) {
         HIPCHK(h, hipModuleLaunchKernel(k.mod, (unsigned)blocks, 1, 1, (unsigned)k.threads, 1, 1, (unsigned)k.dyn_lds, h->stream, args, nullptr));
     } else {
@@ -1883,6 +1906,7 @@ static LaunchFacts launch_facts(const demcz_handle* h, const WindowParams* P, bo
     f.dual = h->dual_now;
     f.snooker = h->snooker_now;
     f.crossover = h->cr_ncr > 0 && !h->snooker_now;
+    f.adapt = f.crossover && h->cr_adapt_every > 0;
     if (h->lanes == DEMCZ_LAYOUT_SPLIT) {
         if (h->split_kind == SPLIT_WAVE && !h->prog_wave) {
             f.ps2 = P && ps2_applicable(h, *P);
@@ -1920,8 +1944,9 @@ static WindowKernel window_kernel_of(const demcz_handle* h, const LaunchFacts& f
         k.arm = ARM_CROSSOVER;
         k.threads = WINDOW_BS;
         k.waves = 1;
-        if (tk == DEMCZ_TARGET_PROGRAM) { if (h->prog_ready) k.mod = h->prog.fn[demcz_prog::LANE_CROSSOVER]; }
-        else k.fn = crossover_kernel_fn(tk, d, &k.dyn_lds);
+        k.adapt = f.adapt;
+        if (tk == DEMCZ_TARGET_PROGRAM) { if (h->prog_ready) k.mod = h->prog.fn[f.adapt ? demcz_prog::LANE_CROSSOVER_ADAPT : demcz_prog::LANE_CROSSOVER]; }
+        else k.fn = crossover_kernel_fn(tk, d, &k.dyn_lds, f.adapt);
         return k;
     }
     if (h->lanes == DEMCZ_LAYOUT_SPLIT) {
@@ -2759,6 +2784,23 @@ static void log_run_call(demcz_handle* h, int64_t g_from, int64_t g_to, double g
     h->live_log.push_back(std::move(rcall));
 }
 
+// cr_adapt_kernel on the handle's stream: the update of the class weights with the spread (d + 1 workgroups), or the spread alone
+static int32_t launch_cr_adapt(demcz_handle* h, bool update)
+{
+    CrAdaptUpdate U{};
+    U.X = h->dX; U.N = h->cfg.N; U.d = h->cfg.d; U.ncr = h->cr_ncr; U.min_weight = h->cr_adapt_min_weight;
+    U.nwg = (int32_t)cra_workgroups(h);
+    U.weights = reinterpret_cast<int32_t*>(h->d_cr_adapt + CRA_WEIGHTS);
+    U.cum = reinterpret_cast<uint32_t*>(h->d_cr_adapt + CRA_CUM);
+    U.updates = reinterpret_cast<long long*>(h->d_cr_adapt + CRA_UPDATES);
+    U.rsd = reinterpret_cast<double*>(h->d_cr_adapt + CRA_RSD);
+    U.slots = reinterpret_cast<unsigned long long*>(h->d_cr_adapt + CRA_SLOTS);
+    void* args[] = {&U};
+    HIPCHK(h, hipLaunchKernel(crossover_adapt_update_fn(), dim3((unsigned)(h->cfg.d + (update ? 1 : 0))), dim3(64), args, 0, h->stream));
+    HIPCHK(h, hipGetLastError());
+    return DEMCZ_OK;
+}
+
 // demcz_run.  The schedule -- where each window launch ends and of what kind it is -- is plan_launch's (demcz_run_plan.h); this is
 // its executor.
 static int32_t run_call(demcz_handle* h, int64_t g_from, int64_t g_to, double gamma, const double* temperature, const RunHints& hints)
@@ -2945,12 +2987,21 @@ static int32_t run_call(demcz_handle* h, int64_t g_from, int64_t g_to, double ga
     static const bool force_live = getenv("DEMCZ_FORCE_LIVE_KERNEL") != nullptr;
     F.force_live = force_live;
     F.snooker_every = h->snooker_every;
+    F.adapt_every = h->cr_adapt_every;
+    F.adapt_until = h->cr_adapt_until;
+    if (h->cr_adapt_every > 0 && !h->cr_adapt_started) {
+        // the start of adaptation: the spread of the chains as they stand (no restored state)
+        int32_t rca = launch_cr_adapt(h, false);
+        if (rca) return rca;
+        h->cr_adapt_started = true;
+    }
     for (int64_t g = g_from; g <= g_to;) {
         F.rec_in_arena = h->rec_in_arena;         // (pc_prepare moves the buffers out of the arena should a caller outrun what was reserved)
         const LaunchPlan lp = plan_launch(F, g, live_span(h), h->M, h->M_app, h->rec_desc[h->rec_cur], h->pending);
         const int64_t w_end = lp.w_end, nbound = lp.nbound;
         h->dual_now = lp.dual;
         h->snooker_now = lp.snooker;
+        h->cr_accumulate_now = adapt_accumulates(F, g);
         int32_t rc = admit_pending(h, g);
         if (rc) return rc;
         P.M = h->M;
@@ -2990,6 +3041,8 @@ static int32_t run_call(demcz_handle* h, int64_t g_from, int64_t g_to, double ga
         h->after_launch_ev = nullptr;         // (whatever was recorded before this launch says nothing about it)
         if (rc) return rc;
         if (lp.snooker) ++h->snooker_steps;
+        // the launch ended on an update position: the new weights and the spread, stream-ordered behind it and in front of the next
+        if (lp.adapt_after) { rc = launch_cr_adapt(h, true); if (rc) return rc; }
         if (h->d_acc) {
             h->acc_log.push_back({g, w_end, h->acc_next});
             h->acc_next = (h->acc_next + 1) % h->acc_slots;
@@ -4446,6 +4499,9 @@ extern "C" int32_t demcz_set_external_append(demcz_handle* h, int32_t enabled)
     NOT_DERIVED(h);
     if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (!h->live_log.empty()) { int32_t rcv = live_verify(h); if (rcv) return rcv; }
+    if (enabled && h->cr_adapt_every > 0)
+        return fail(h, DEMCZ_ERR_STATE, "demcz_set_external_append: the handle adapts its crossover weights (demcz_set_crossover_adapt) on its own "
+                                        "chains: a shard's chains are not the population");
     h->external_append = enabled != 0;
     return DEMCZ_OK;
 }
@@ -4531,6 +4587,24 @@ extern "C" int32_t demcz_get_snooker(const demcz_handle* h, int32_t* every, doub
     return DEMCZ_OK;
 }
 
+// the handle's weights (and their cumulative sums) into the adaptation's block on the device
+static int32_t cr_adapt_upload_weights(demcz_handle* h)
+{
+    int32_t w[CR_MAX_CLASSES];
+    uint32_t cum[CR_MAX_CLASSES];
+    uint32_t sum = 0;
+    for (int k = 0; k < CR_MAX_CLASSES; ++k) {
+        w[k] = k < h->cr_ncr ? h->cr_weights[k] : 0;
+        if (k < h->cr_ncr) sum += (uint32_t)h->cr_weights[k];
+        cum[k] = sum;
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device_id));
+    HIPCHK(h, hipMemcpyAsync(h->d_cr_adapt + CRA_WEIGHTS, w, sizeof w, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_cr_adapt + CRA_CUM, cum, sizeof cum, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return DEMCZ_OK;
+}
+
 // Crossover generations.  The choices differ from chain to chain and are made inside the kernel;
 // the host knows only that the handle's generations are crossover generations (window_kernel_of: ARM_CROSSOVER) and that a
 // generation takes crossover_stride(d, delta_max) Philox blocks.
@@ -4569,10 +4643,12 @@ extern "C" int32_t demcz_set_crossover(demcz_handle* h, int32_t ncr, const int32
         if (!h->d_cr_counts) HIPCHK(h, dev_malloc(h->cfg.device_id, (void**)&h->d_cr_counts, n * sizeof(unsigned long long)));
         HIPCHK(h, hipMemsetAsync(h->d_cr_counts, 0, n * sizeof(unsigned long long), h->stream));
     }
+    if (ncr == 0 || ncr != h->cr_ncr) { h->cr_adapt_every = 0; h->cr_adapt_until = 0; h->cr_adapt_started = false; }      // adaptation goes with its classes
     h->cr_ncr = ncr;
     h->cr_delta_max = delta_max;
     for (int k = 0; k < CR_MAX_CLASSES; ++k) h->cr_weights[k] = (k < ncr) ? (weights ? weights[k] : 1) : 1;
     h->S = ncr > 0 ? crossover_stride(h->cfg.d, delta_max) : h->S_plain;
+    if (h->cr_adapt_every > 0) return cr_adapt_upload_weights(h);
     return DEMCZ_OK;
 }
 
@@ -4582,7 +4658,17 @@ extern "C" int32_t demcz_get_crossover(const demcz_handle* h, int32_t* ncr, int3
     if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
     if (ncr) *ncr = h->cr_ncr;
     if (delta_max) *delta_max = h->cr_delta_max;
-    if (weights) for (int k = 0; k < h->cr_ncr; ++k) weights[k] = h->cr_weights[k];
+    if (weights) {
+        for (int k = 0; k < h->cr_ncr; ++k) weights[k] = h->cr_weights[k];
+        if (h->cr_adapt_every > 0 && h->cr_ncr > 0) {      // the device's: they change with no host in between
+            demcz_handle* hm = const_cast<demcz_handle*>(h);
+            int32_t dw[CR_MAX_CLASSES];
+            HIPCHK(hm, hipSetDevice(h->cfg.device_id));
+            HIPCHK(hm, hipMemcpyAsync(dw, h->d_cr_adapt + CRA_WEIGHTS, sizeof dw, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hm, hipStreamSynchronize(h->stream));
+            for (int k = 0; k < h->cr_ncr; ++k) weights[k] = dw[k];
+        }
+    }
     if (tried || accepted) {
         demcz_handle* hm = const_cast<demcz_handle*>(h);
         int64_t sums[2 * CR_MAX_CLASSES] = {0};
@@ -4601,6 +4687,146 @@ extern "C" int32_t demcz_get_crossover(const demcz_handle* h, int32_t* ncr, int3
             if (accepted) accepted[k] = sums[2 * k + 1];
         }
     }
+    return DEMCZ_OK;
+}
+
+// Adaptation of the class weights during burn-in.  The host knows the positions (plan_launch cuts a
+// launch at every update position up to `until`) and enqueues cr_adapt_kernel behind such a launch; what is adapted on, and the
+// weights themselves, stay on the device.
+extern "C" int32_t demcz_set_crossover_adapt(demcz_handle* h, int64_t every, int64_t until, int32_t min_weight)
+{
+    NOT_DERIVED(h);
+    if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
+    DEADCHK(h);
+    if (every < 0) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_crossover_adapt: every must be >= 0 (0 switches the adaptation off)");
+    if (every == 0) {
+        // (a handle that runs the ADAPT kernels keeps them for life)
+        if (h->cr_adapt_every > 0 && (h->launches > 0 || h->g_done != h->g0))
+            return fail(h, DEMCZ_ERR_STATE, "demcz_set_crossover_adapt: the handle has already run a generation: the adaptation is switched off on the "
+                                            "fresh handle only (behind `until` it has ended by itself)");
+        h->cr_adapt_every = 0; h->cr_adapt_until = 0; h->cr_adapt_started = false;
+        return DEMCZ_OK;
+    }
+    if (until < every || until % every != 0)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_crossover_adapt: until must be a multiple of every, and at least every");
+    if (min_weight < 1 || min_weight > 8192)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_crossover_adapt: min_weight must be 1 ... 8192 (of 65536)");
+    // a step adds at most 2^32 to a class's distance
+    if (until >= ((int64_t)1 << 31) || (__int128)h->cfg.N * (__int128)until >= ((__int128)1 << 31))
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_crossover_adapt: N * until must stay below 2^31 (the distance sums are 64-bit integers)");
+    if (h->cr_ncr == 0) return fail(h, DEMCZ_ERR_STATE, "demcz_set_crossover_adapt: the handle has no crossover generations (demcz_set_crossover first)");
+    if (h->launches > 0 || h->g_done != h->g0)
+        return fail(h, DEMCZ_ERR_STATE, "demcz_set_crossover_adapt: the handle has already run a generation (set the adaptation on the fresh handle; "
+                                        "demcz_set_crossover_weights changes the weights of a running one)");
+    if (h->external_append)
+        return fail(h, DEMCZ_ERR_STATE, "demcz_set_crossover_adapt: the handle appends externally (demcz_set_external_append): a shard's own chains are "
+                                        "not the population (demcz_set_crossover_weights sets a shard's weights by hand)");
+    HIPCHK(h, hipSetDevice(h->cfg.device_id));
+    if (!h->d_cr_adapt) HIPCHK(h, dev_malloc(h->cfg.device_id, (void**)&h->d_cr_adapt, cra_bytes(h)));
+    HIPCHK(h, hipMemsetAsync(h->d_cr_adapt, 0, cra_bytes(h), h->stream));
+    h->cr_adapt_every = every;
+    h->cr_adapt_until = until;
+    h->cr_adapt_min_weight = min_weight;
+    h->cr_adapt_started = false;
+    return cr_adapt_upload_weights(h);
+}
+
+extern "C" int32_t demcz_get_crossover_adapt(const demcz_handle* h, int64_t* every, int64_t* until, int32_t* min_weight, int32_t* weights,
+                                             int64_t* dist, int64_t* tried, double* rsd, int64_t* updates)
+{
+    NOT_DERIVED(h);
+    if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
+    if (every) *every = h->cr_adapt_every;
+    if (until) *until = h->cr_adapt_until;
+    if (min_weight) *min_weight = h->cr_adapt_min_weight;
+    if (h->cr_adapt_every == 0) {
+        if (updates) *updates = 0;
+        for (int k = 0; k < CR_MAX_CLASSES; ++k) {
+            if (weights) weights[k] = k < h->cr_ncr ? h->cr_weights[k] : 0;
+            if (dist) dist[k] = 0;
+            if (tried) tried[k] = 0;
+        }
+        if (rsd) for (int p = 0; p < h->cfg.d; ++p) rsd[p] = 0.0;
+        return DEMCZ_OK;
+    }
+    demcz_handle* hm = const_cast<demcz_handle*>(h);
+    HIPCHK(hm, hipSetDevice(h->cfg.device_id));
+    std::vector<unsigned char> host(cra_bytes(h));
+    HIPCHK(hm, hipMemcpyAsync(host.data(), h->d_cr_adapt, host.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hm, hipStreamSynchronize(h->stream));
+    unsigned long long sums[2 * CR_MAX_CLASSES] = {0};
+    for (size_t w = 0; w < cra_workgroups(h); ++w)
+        for (int i = 0; i < 2 * CR_MAX_CLASSES; ++i) {
+            unsigned long long v;
+            memcpy(&v, host.data() + CRA_SLOTS + (w * 2 * CR_MAX_CLASSES + i) * sizeof v, sizeof v);
+            sums[i] += v;
+        }
+    for (int k = 0; k < CR_MAX_CLASSES; ++k) {
+        if (weights) memcpy(&weights[k], host.data() + CRA_WEIGHTS + 4 * k, 4);
+        if (dist) dist[k] = (int64_t)sums[2 * k];
+        if (tried) tried[k] = (int64_t)sums[2 * k + 1];
+    }
+    if (rsd) memcpy(rsd, host.data() + CRA_RSD, sizeof(double) * (size_t)h->cfg.d);
+    if (updates) memcpy(updates, host.data() + CRA_UPDATES, sizeof(int64_t));
+    return DEMCZ_OK;
+}
+
+extern "C" int32_t demcz_set_crossover_adapt_state(demcz_handle* h, const int32_t* weights, int64_t* dist, int64_t* tried,
+                                                   const double* rsd, int64_t updates)
+{
+    NOT_DERIVED(h);
+    if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
+    DEADCHK(h);
+    if (h->cr_adapt_every == 0) return fail(h, DEMCZ_ERR_STATE, "demcz_set_crossover_adapt_state: the handle has no adaptation set (demcz_set_crossover_adapt first)");
+    if (h->launches > 0 || h->g_done != h->g0)
+        return fail(h, DEMCZ_ERR_STATE, "demcz_set_crossover_adapt_state: the handle has already run a generation: the state of a checkpoint goes "
+                                        "onto the fresh handle");
+    if (!weights || !dist || !tried || !rsd || updates < 0)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_crossover_adapt_state: weights, dist, tried and rsd are required, updates >= 0");
+    int64_t W = 0;
+    for (int k = 0; k < h->cr_ncr; ++k) {
+        if (weights[k] < 0 || dist[k] < 0 || tried[k] < 0)
+            return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_crossover_adapt_state: a weight, a distance or a count is negative");
+        W += weights[k];
+    }
+    if (W < 1 || W >= (int64_t)1 << 31)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_crossover_adapt_state: the weights must sum to a W with 1 <= W < 2^31");
+    std::vector<unsigned char> host(cra_bytes(h), 0);
+    for (int k = 0; k < h->cr_ncr; ++k) {
+        h->cr_weights[k] = weights[k];
+        const unsigned long long dv = (unsigned long long)dist[k], tv = (unsigned long long)tried[k];
+        memcpy(host.data() + CRA_SLOTS + (2 * k) * sizeof dv, &dv, sizeof dv);            // workgroup 0's slots hold the totals
+        memcpy(host.data() + CRA_SLOTS + (2 * k + 1) * sizeof tv, &tv, sizeof tv);
+    }
+    memcpy(host.data() + CRA_UPDATES, &updates, sizeof updates);
+    memcpy(host.data() + CRA_RSD, rsd, sizeof(double) * (size_t)h->cfg.d);
+    HIPCHK(h, hipSetDevice(h->cfg.device_id));
+    HIPCHK(h, hipMemcpyAsync(h->d_cr_adapt, host.data(), host.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->cr_adapt_started = true;       // the spread is the checkpoint's
+    return cr_adapt_upload_weights(h);
+}
+
+extern "C" int32_t demcz_set_crossover_weights(demcz_handle* h, const int32_t* weights)
+{
+    NOT_DERIVED(h);
+    if (!h) return DEMCZ_ERR_INVALID_ARGUMENT;
+    DEADCHK(h);
+    if (h->cr_ncr == 0) return fail(h, DEMCZ_ERR_STATE, "demcz_set_crossover_weights: the handle has no crossover generations (demcz_set_crossover)");
+    if (!weights) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_crossover_weights: weights is required");
+    int64_t W = 0;
+    for (int k = 0; k < h->cr_ncr; ++k) {
+        if (weights[k] < 0) return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_crossover_weights: a weight is negative");
+        W += weights[k];
+    }
+    if (W < 1 || W >= (int64_t)1 << 31)
+        return fail(h, DEMCZ_ERR_INVALID_ARGUMENT, "demcz_set_crossover_weights: the weights must sum to a W with 1 <= W < 2^31");
+    // (updates * every < until, said in positions: the update on `until` is the last)
+    if (h->cr_adapt_every > 0 && h->g_done + h->rng_offset < h->cr_adapt_until)
+        return fail(h, DEMCZ_ERR_STATE, "demcz_set_crossover_weights: the adaptation is still running (it sets the weights until the generation "
+                                        "`until` of demcz_set_crossover_adapt has run)");
+    for (int k = 0; k < h->cr_ncr; ++k) h->cr_weights[k] = weights[k];
+    if (h->cr_adapt_every > 0) return cr_adapt_upload_weights(h);       // (stream-ordered behind the launches that read the old ones)
     return DEMCZ_OK;
 }
 
@@ -6595,9 +6821,9 @@ extern "C" int32_t demcz_debug_kernel_name(const demcz_handle* h, char* buf, int
         else snprintf(tmp, sizeof tmp, "snooker_kernel<%s, %d>", tg, d);
         break;
     case ARM_CROSSOVER:
-        if (h->cfg.target_kind == DEMCZ_TARGET_PROGRAM) snprintf(tmp, sizeof tmp, "window_kernel_cr<%d, %d> (program)", (int)TARGET_PROGRAM, d);
-        else if (k.dyn_lds) snprintf(tmp, sizeof tmp, "window_kernel_cr_generic<%s>", tg);
-        else snprintf(tmp, sizeof tmp, "window_kernel_cr<%s, %d>", tg, d);
+        if (h->cfg.target_kind == DEMCZ_TARGET_PROGRAM) snprintf(tmp, sizeof tmp, "window_kernel_cr<%d, %d%s> (program)", (int)TARGET_PROGRAM, d, k.adapt ? ", adapt" : "");
+        else if (k.dyn_lds) snprintf(tmp, sizeof tmp, "window_kernel_cr_generic<%s%s>", tg, k.adapt ? ", adapt" : "");
+        else snprintf(tmp, sizeof tmp, "window_kernel_cr<%s, %d%s>", tg, d, k.adapt ? ", adapt" : "");
         break;
     case ARM_ONE_LANE:
         // Known misreport: a dimension with no specialisation launches window_kernel_generic<TARGET> and is still named

@@ -14,8 +14,9 @@ namespace demcz {
         *dyn_lds = (size_t)(2 * d) * WINDOW_BS * sizeof(double);                \
         return reinterpret_cast<const void*>(&window_kernel_cr_generic<T>);
 
-const void* crossover_kernel_fn(int target_kind, int d, size_t* dyn_lds)
+const void* crossover_kernel_fn(int target_kind, int d, size_t* dyn_lds, bool adapt)
 {
+    if (adapt) return crossover_adapt_kernel_fn(target_kind, d, dyn_lds);
     *dyn_lds = 0;
     if (d < 2 || d > MAX_D) return nullptr;
     switch (target_kind) {

@@ -11,6 +11,15 @@
 // chain.  The CR class, the number of pairs and the subset differ from lane to lane: the subset is a 64-bit lane-local mask applied
 // with selects, the gathers of pair j are predicated on j <= delta.  No fma in the proposal: every product and sum is rounded on
 // its own (tests/crossover_reference.py is plain Python floats).
+//
+//   window_kernel_cr<TARGET, D, true>, window_kernel_cr_generic<TARGET, true>   the same generations with the class weights adapted
+//       during burn-in (demcz_set_crossover_adapt): a third kernel argument, CrossoverAdaptParams, brings the cumulative weights
+//       from DEVICE memory -- they change between launches with no host in between -- and, while `accumulate` is set, every
+//       accepted step's squared jump distance, normalised by the population's spread and quantised to an integer, is added up per
+//       class (tests/crossover_adapt_reference.py).  The two-argument kernels are what they were: both forms are one body,
+//       and everything of the adaptation in it is behind `if constexpr (ADAPT)`.
+//   cr_adapt_kernel   the update behind the launch that ends on an update position: the new weights from jump distance per
+//       step tried, and the spread (rsd) of the chains as they stand.
 #pragma once
 
 #include "demcz_kernels.h"
@@ -29,6 +38,73 @@ struct CrossoverParams {
     uint32_t cum[CR_MAX_CLASSES];          // cum[k] = w_0 + ... + w_k for k < ncr, W = cum[ncr - 1] for k >= ncr
     unsigned long long* counts;            // [workgroup][8][2]: steps tried and accepted per class, summed over the handle's life
 };
+
+// what an ADAPT launch is told beside that (a third kernel argument: WindowParams and CrossoverParams stay the structs they are)
+struct CrossoverAdaptParams {
+    const uint32_t* cum;                   // [8] in device memory, laid out as CrossoverParams::cum: read once at launch start
+    const double* rsd;                     // [d]: reciprocal standard deviation of every parameter over the chains (0: the column does not count)
+    unsigned long long* slots;             // [workgroup][8][2]: quantised jump distance and steps tried per class, while adaptation runs
+    int32_t accumulate;                    // launch-uniform: the launch lies at or in front of `until`
+};
+
+// q of an accepted step with squared normalised jump distance J: 16.16 fixed point, clamped at 65536; NaN and negatives give 0
+__device__ __forceinline__ unsigned long long cr_quantise(double J)
+{
+    const double Jc = (J < 65536.0) ? J : 65536.0;
+    const double sc = Jc * 65536.0;
+    return (J >= 0.0) ? (unsigned long long)sc : 0ull;
+}
+
+// Per-class sums of q of a lane: eight predicated adds a step (no dynamically indexed register array), reduced over the wave at the
+// end of the launch.  The lanes that run a chain are lanes 0 .. nact - 1; what a shuffle reads from a lane beyond them is not used.
+struct CrDist {
+    unsigned long long q[CR_MAX_CLASSES];
+    __device__ __forceinline__ void clear()
+    {
+#pragma unroll
+        for (int k = 0; k < CR_MAX_CLASSES; ++k) q[k] = 0ull;
+    }
+    __device__ __forceinline__ void add(int m, unsigned long long v)
+    {
+#pragma unroll
+        for (int k = 0; k < CR_MAX_CLASSES; ++k) q[k] += (m == k) ? v : 0ull;
+    }
+    // lane 0 adds the wave's sums and the steps tried into the workgroup's own sixteen slots (plain loads and stores, as
+    // CrCounts::add_to does)
+    __device__ __forceinline__ void add_to(unsigned long long* slots, const unsigned int (&tried)[CR_MAX_CLASSES], int nact)
+    {
+        const int lane = (int)threadIdx.x;
+#pragma unroll
+        for (int k = 0; k < CR_MAX_CLASSES; ++k) {
+#pragma unroll
+            for (int sft = 32; sft >= 1; sft >>= 1) {
+                const unsigned long long o = __shfl_down(q[k], sft, 64);
+                q[k] += (lane + sft < nact) ? o : 0ull;
+            }
+        }
+        if (lane != 0) return;
+        unsigned long long* slot = slots + (size_t)blockIdx.x * (2 * CR_MAX_CLASSES);
+#pragma unroll
+        for (int k = 0; k < CR_MAX_CLASSES; ++k) {
+            slot[2 * k] = slot[2 * k] + q[k];
+            slot[2 * k + 1] = slot[2 * k + 1] + (unsigned long long)tried[k];
+        }
+    }
+};
+
+// the one element of an ADAPT kernel's trailing arguments
+__device__ __forceinline__ const CrossoverAdaptParams& cr_adapt_params(const CrossoverAdaptParams& A) { return A; }
+// C with the cumulative weights read from device memory (uniform loads, once a launch)
+__device__ __forceinline__ CrossoverParams cr_adapted(const CrossoverParams& C, const CrossoverAdaptParams& A)
+{
+    CrossoverParams Cl;
+    Cl.ncr = C.ncr;
+    Cl.delta_max = C.delta_max;
+    Cl.counts = C.counts;
+#pragma unroll
+    for (int k = 0; k < CR_MAX_CLASSES; ++k) Cl.cum[k] = A.cum[k];
+    return Cl;
+}
 
 // Philox blocks of a crossover generation: choices, delta_max pairs, ceil(d / 4) of subset words, ceil(d / 2) of normals, log u
 __host__ __device__ constexpr int64_t crossover_stride(int d, int delta_max) { return 1 + delta_max + (d + 3) / 4 + (d + 1) / 2 + 1; }
@@ -93,12 +169,25 @@ struct CrCounts {
 #define DEMCZ_CR_INFLIGHT_MAX_D 10
 #endif
 
-template <int TARGET, int D>
-__global__ void __launch_bounds__(WINDOW_BS) window_kernel_cr(const WindowParams P, const CrossoverParams C)
+// ADAPT: the kernel has a third argument, CrossoverAdaptParams -- AP is that one type, and empty otherwise, so that the kernel
+// without adaptation keeps the two kernel arguments it has
+template <int TARGET, int D, bool ADAPT = false, class... AP>
+__global__ void __launch_bounds__(WINDOW_BS) window_kernel_cr(const WindowParams P, const CrossoverParams C, const AP... adapt_args)
 {
     static_assert(D >= 1 && D <= 64, "the subset is a 64-bit mask");
+    static_assert(sizeof...(AP) == (ADAPT ? 1 : 0), "window_kernel_cr<TARGET, D> or window_kernel_cr<TARGET, D, true, CrossoverAdaptParams>");
     const int64_t c = (int64_t)blockIdx.x * WINDOW_BS + threadIdx.x;
     if (c >= P.N) return;
+    [[maybe_unused]] CrossoverParams Cl;      // ADAPT: C with the cumulative weights as device memory holds them now
+    [[maybe_unused]] CrDist cd;
+    [[maybe_unused]] double rsdc[ADAPT ? D : 1];      // the spread, launch-invariant: in scalar registers like the target's constants
+    if constexpr (ADAPT) {
+        const CrossoverAdaptParams& A = cr_adapt_params(adapt_args...);
+        Cl = cr_adapted(C, A);
+        cd.clear();
+#pragma unroll
+        for (int p = 0; p < D; ++p) rsdc[p] = uniform_double(A.rsd[p]);
+    }
 
     double x[D];
 #pragma unroll
@@ -158,7 +247,8 @@ __global__ void __launch_bounds__(WINDOW_BS) window_kernel_cr(const WindowParams
         uint64_t r1, r2;
         rng_next(st, r1, r2);
         int m, delta, pstar;
-        cr_choices(C, r1, r2, D, m, delta, pstar);
+        if constexpr (ADAPT) cr_choices(Cl, r1, r2, D, m, delta, pstar);
+        else cr_choices(C, r1, r2, D, m, delta, pstar);
         // the pairs: every block is drawn (the positions are fixed), the rows of pair j only where j <= delta
         uint64_t i1[CR_MAX_PAIRS], i2[CR_MAX_PAIRS];
         double za[NHELD][D], zb[NHELD][D];
@@ -241,6 +331,20 @@ __global__ void __launch_bounds__(WINDOW_BS) window_kernel_cr(const WindowParams
         double dlt = lpp - lp;
         if (P.temperature) dlt = dlt / P.temperature[gi];
         const bool acc = logu < dlt;
+        if constexpr (ADAPT) {
+            const CrossoverAdaptParams& A = cr_adapt_params(adapt_args...);
+            if (A.accumulate) {                 // launch-uniform
+                double J = 0.0;
+#pragma unroll
+                for (int p = 0; p < D; ++p) {
+                    const double df = xp[p] - x[p];
+                    const double tp = df * rsdc[p];
+                    const double t2 = tp * tp;
+                    J = J + t2;
+                }
+                cd.add(m, acc ? cr_quantise(J) : 0ull);
+            }
+        }
 #pragma unroll
         for (int p = 0; p < D; ++p) x[p] = acc ? xp[p] : x[p];
         lp = acc ? lpp : lp;
@@ -271,13 +375,18 @@ __global__ void __launch_bounds__(WINDOW_BS) window_kernel_cr(const WindowParams
     P.lpcur[c] = lp;
     wave_store_counts(P, blockIdx.x, cnt_total, cnt_first);
     cc.add_to(C.counts);
+    if constexpr (ADAPT) {
+        const CrossoverAdaptParams& A = cr_adapt_params(adapt_args...);
+        if (A.accumulate) cd.add_to(A.slots, cc.tried, __builtin_popcountll(speak64));
+    }
 }
 
 // run-time d: x and the proposal in LDS (2 d columns of WINDOW_BS doubles, dynamic), the rows read where they are used; the
 // normals are consumed pair by pair as they are made, so they need no column of their own
-template <int TARGET>
-__global__ void __launch_bounds__(WINDOW_BS) window_kernel_cr_generic(const WindowParams P, const CrossoverParams C)
+template <int TARGET, bool ADAPT = false, class... AP>
+__global__ void __launch_bounds__(WINDOW_BS) window_kernel_cr_generic(const WindowParams P, const CrossoverParams C, const AP... adapt_args)
 {
+    static_assert(sizeof...(AP) == (ADAPT ? 1 : 0), "window_kernel_cr_generic<TARGET> or window_kernel_cr_generic<TARGET, true, CrossoverAdaptParams>");
     extern __shared__ double lds[];
     const int d = P.d;
     double* xs = lds;                         // d x BS
@@ -285,6 +394,12 @@ __global__ void __launch_bounds__(WINDOW_BS) window_kernel_cr_generic(const Wind
     const int64_t c = (int64_t)blockIdx.x * WINDOW_BS + threadIdx.x;
     if (c >= P.N) return;
     const int tid = threadIdx.x;
+    [[maybe_unused]] CrossoverParams Cl;
+    [[maybe_unused]] CrDist cd;
+    if constexpr (ADAPT) {
+        Cl = cr_adapted(C, cr_adapt_params(adapt_args...));
+        cd.clear();
+    }
 
     for (int p = 0; p < d; ++p) xs[p * WINDOW_BS + tid] = P.Xcur[c + P.N * p];
     double lp = P.lpcur[c];
@@ -303,7 +418,8 @@ __global__ void __launch_bounds__(WINDOW_BS) window_kernel_cr_generic(const Wind
         uint64_t r1, r2;
         rng_next(st, r1, r2);
         int m, delta, pstar;
-        cr_choices(C, r1, r2, d, m, delta, pstar);
+        if constexpr (ADAPT) cr_choices(Cl, r1, r2, d, m, delta, pstar);
+        else cr_choices(C, r1, r2, d, m, delta, pstar);
         const double* ra[CR_MAX_PAIRS];
         const double* rb[CR_MAX_PAIRS];
 #pragma unroll
@@ -362,6 +478,19 @@ __global__ void __launch_bounds__(WINDOW_BS) window_kernel_cr_generic(const Wind
         double dlt = lpp - lp;
         if (P.temperature) dlt = dlt / P.temperature[gi];
         const bool acc = logu < dlt;
+        if constexpr (ADAPT) {
+            const CrossoverAdaptParams& A = cr_adapt_params(adapt_args...);
+            if (A.accumulate) {                 // launch-uniform
+                double J = 0.0;
+                for (int p = 0; p < d; ++p) {
+                    const double df = xps[p * WINDOW_BS + tid] - xs[p * WINDOW_BS + tid];
+                    const double tp = df * A.rsd[p];
+                    const double t2 = tp * tp;
+                    J = J + t2;
+                }
+                cd.add(m, acc ? cr_quantise(J) : 0ull);
+            }
+        }
         if (acc) {
             for (int p = 0; p < d; ++p) xs[p * WINDOW_BS + tid] = xps[p * WINDOW_BS + tid];
             lp = lpp;
@@ -391,12 +520,94 @@ __global__ void __launch_bounds__(WINDOW_BS) window_kernel_cr_generic(const Wind
     P.lpcur[c] = lp;
     wave_store_counts(P, blockIdx.x, cnt_total, cnt_first);
     cc.add_to(C.counts);
+    if constexpr (ADAPT) {
+        const CrossoverAdaptParams& A = cr_adapt_params(adapt_args...);
+        if (A.accumulate) cd.add_to(A.slots, cc.tried, __builtin_popcountll(speak64));
+    }
 }
 
 #ifndef DEMCZ_PROGRAM_TARGET
+// ---- the update of the adapted weights ("adaptation of the class weights") ---------------------------------------
+struct CrAdaptUpdate {
+    const double* X;                       // the chains as they stand, X[c + N p]
+    int64_t N;
+    int32_t d, ncr, min_weight, nwg;       // nwg: workgroups of a window launch (slots)
+    int32_t* weights;                      // [8]
+    uint32_t* cum;                         // [8]: what the next launch reads
+    long long* updates;
+    double* rsd;                           // [d]
+    unsigned long long* slots;             // [nwg][8][2]
+};
+
+// the sum of v over the chains of one column, in THE order of the specification: lane l adds its chains c = l, l + 64, ... in
+// increasing c onto 0.0, then a_l = a_l + a_(l + s) for s = 32 ... 1; every lane returns lane 0's sum
+template <class F>
+__device__ __forceinline__ double cr_column_sum(int64_t N, F&& v)
+{
+    double a = 0.0;
+    for (int64_t c = threadIdx.x; c < N; c += 64) a = a + v(c);
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) a = a + __shfl_down(a, s, 64);
+    return __shfl(a, 0, 64);
+}
+
+// grid d + 1 (an update) or d (the start of adaptation: the spread only), 64 lanes.  Block p < d: rsd_p.  Block d: the slots' sums,
+// the weight rule in one lane, and the totals back into workgroup 0's slots with the others zeroed.
+template <int LANES>
+__global__ void __launch_bounds__(LANES) cr_adapt_kernel(const CrAdaptUpdate U)
+{
+    static_assert(LANES == 64, "one wave");
+    const int lane = (int)threadIdx.x;
+    if ((int)blockIdx.x < U.d) {
+        const double* col = U.X + U.N * (int64_t)blockIdx.x;
+        const double sum = cr_column_sum(U.N, [&](int64_t c) { return col[c]; });
+        const double mean = sum / (double)U.N;
+        const double ss = cr_column_sum(U.N, [&](int64_t c) { const double t = col[c] - mean; return t * t; });
+        const double var = ss / (double)(U.N - 1);
+        const double r = 1.0 / sqrt(var);
+        if (lane == 0) U.rsd[blockIdx.x] = (var > 0.0 && var < __builtin_inf()) ? r : 0.0;
+        return;
+    }
+    unsigned long long tot = 0ull;
+    if (lane < 2 * CR_MAX_CLASSES) {
+        for (int w = 0; w < U.nwg; ++w) tot += U.slots[(size_t)w * (2 * CR_MAX_CLASSES) + lane];
+        U.slots[lane] = tot;
+        for (int w = 1; w < U.nwg; ++w) U.slots[(size_t)w * (2 * CR_MAX_CLASSES) + lane] = 0ull;
+    }
+    double r[CR_MAX_CLASSES];
+    double R = 0.0;
+#pragma unroll
+    for (int k = 0; k < CR_MAX_CLASSES; ++k) {
+        const unsigned long long dist = __shfl(tot, 2 * k, 64), tried = __shfl(tot, 2 * k + 1, 64);
+        r[k] = (k < U.ncr && tried > 0ull) ? (double)dist / (double)tried : 0.0;
+        if (k < U.ncr) R = R + r[k];
+    }
+    if (lane != 0) return;
+    if (R > 0.0) {
+        uint32_t sum = 0u;
+#pragma unroll
+        for (int k = 0; k < CR_MAX_CLASSES; ++k) {
+            if (k < U.ncr) {
+                const double share = r[k] / R;
+                const double sc = share * 65536.0;
+                const int32_t w = (int32_t)sc;
+                const int32_t wk = w > U.min_weight ? w : U.min_weight;
+                U.weights[k] = wk;
+                sum += (uint32_t)wk;
+            }
+            U.cum[k] = sum;
+        }
+    }
+    *U.updates = *U.updates + 1;
+}
+
 // the built-in instantiations live in demcz_crossover_inst.hip; this hands out their host symbols.  *dyn_lds: dynamic LDS bytes of
 // the launch (the run-time-d form).  nullptr: no built-in kernel for that target (program targets bring their own).
-const void* crossover_kernel_fn(int target_kind, int d, size_t* dyn_lds);
+// adapt: the ADAPT twin, which lives with cr_adapt_kernel in demcz_crossover_adapt_inst.hip (a unit of its own: the build is
+// parallel over units).
+const void* crossover_kernel_fn(int target_kind, int d, size_t* dyn_lds, bool adapt = false);
+const void* crossover_adapt_kernel_fn(int target_kind, int d, size_t* dyn_lds);
+const void* crossover_adapt_update_fn();
 #endif
 
 }  // namespace demcz

@@ -29,7 +29,8 @@ enum {
     LANE_BLOCKS,           // window_kernel<TARGET_PROGRAM, d, false>: blocks from the CSR tables
     LANE_SNOOKER,          // snooker_kernel<TARGET_PROGRAM, d> (demcz_kernels_snooker.h)
     LANE_CROSSOVER,        // window_kernel_cr<TARGET_PROGRAM, d> (demcz_kernels_crossover.h)
-    LANE_LOGP              // logp_kernel<TARGET_PROGRAM>: the initial log_objcurrent
+    LANE_LOGP,             // logp_kernel<TARGET_PROGRAM>: the initial log_objcurrent
+    LANE_CROSSOVER_ADAPT   // window_kernel_cr<TARGET_PROGRAM, d, true>: the crossover generation with adapted class weights
 };
 enum {
     WAVE_KERNEL = 0,       // + 2 * LIVE + TEMPER: window_kernel_ps (d <= 5) / _pw<TARGET_PROGRAM, d, LIVE, TEMPER>
@@ -39,7 +40,7 @@ enum { DERIVE_KERNEL = 0 };                        // derive_kernel
 enum { POINTWISE_KERNEL = 0 };                     // pointwise_kernel
 enum { BRIDGE_KERNEL = 0 };                        // bridge_proposal_program_kernel
 enum { PREDICT_KERNEL = 0, PREDICT_PPC = 1 };      // predict_kernel, ppc_kernel
-constexpr int MAX_KERNELS = 5;
+constexpr int MAX_KERNELS = 6;
 
 // One compiled program: the gfx950 code object and the mangled names of its unit's kernels.
 struct Code {

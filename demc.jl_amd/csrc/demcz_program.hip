@@ -133,7 +133,8 @@ const Kernel k_logp = {"logp_kernel", "<{T}>", "demcz::TargetParams, int, const 
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wc++20-designator"
 const Unit k_units[] = {
-    {   // UNIT_ONE_LANE: the one-lane window kernel, the snooker and the crossover generation's kernels (a program that cannot be
+    {   // UNIT_ONE_LANE: the one-lane window kernel, the snooker and the crossover generation's kernels, the latter with and without
+        // adapted class weights (a program that cannot be
         // built for them fails here) and logp_kernel
         .tag = "lane", .name = "demcz_program_unit", .who = "program target: ",
         .defines = "#define DEMCZ_PROGRAM_TARGET\n#define DEMCZ_NO_AUX_KERNELS\n",
@@ -145,8 +146,11 @@ const Unit k_units[] = {
                     {"window_kernel", "<{T}, {d}, false>", k_window_params},
                     {"snooker_kernel", "<{T}, {d}>", "const demcz::WindowParams, const demcz::SnookerParams"},
                     {"window_kernel_cr", "<{T}, {d}>", "const demcz::WindowParams, const demcz::CrossoverParams"},
-                    k_logp},
-        .instantiate = {demcz_prog::LANE_FULL, demcz_prog::LANE_BLOCKS, demcz_prog::LANE_SNOOKER, demcz_prog::LANE_LOGP, demcz_prog::LANE_CROSSOVER},
+                    k_logp,
+                    {"window_kernel_cr", "<{T}, {d}, true, demcz::CrossoverAdaptParams>",
+                     "const demcz::WindowParams, const demcz::CrossoverParams, const demcz::CrossoverAdaptParams"}},
+        .instantiate = {demcz_prog::LANE_FULL, demcz_prog::LANE_BLOCKS, demcz_prog::LANE_SNOOKER, demcz_prog::LANE_LOGP, demcz_prog::LANE_CROSSOVER,
+                        demcz_prog::LANE_CROSSOVER_ADAPT},
         .needle = "demcz_logobj", .hint = k_logobj_hint,
     },
     {   // UNIT_WAVE: the wave-per-chain consumers of the split layout, LIVE and TEMPER both ways, and logp_kernel; demcz_kernels_pw.h

@@ -79,6 +79,9 @@ struct RunFacts {
     int64_t next_hint = 0;          // generations of the launch that follows the call (0: not known -- taken to be as long as this call)
     bool force_live = false;        // diagnosis: the LIVE instantiation also for launches with no boundary inside
     int64_t snooker_every = 0;      // s >= 1: generation g is a snooker generation when (g + rng_offset) % s == 0 (0: none)
+    // adaptation of the crossover class weights (demcz_set_crossover_adapt): the weights are updated behind every generation g with
+    // (g + rng_offset) % adapt_every == 0 and g + rng_offset <= adapt_until (0: none; adapt_until % adapt_every == 0)
+    int64_t adapt_every = 0, adapt_until = 0;
 };
 
 struct LaunchPlan {
@@ -91,6 +94,7 @@ struct LaunchPlan {
     int64_t next_g_first = 0, next_ngen = 0, next_M = 0, next_rows = 0;
     int32_t next_boff = 0;
     bool snooker = false;           // the launch is one snooker generation (snooker_kernel, demcz_kernels_snooker.h)
+    bool adapt_after = false;       // the launch ends on an update position of the class weights: cr_adapt_kernel follows it
 };
 
 // ---- snooker generations -------------------------------------------------------------------------------------------------------------
@@ -101,6 +105,17 @@ inline int64_t snooker_at_or_after(const RunFacts& f, int64_t g)
 {
     const int64_t s = f.snooker_every, r = (g + f.rng_offset) % s;
     return r == 0 ? g : g + (s - r);
+}
+
+// ---- adaptation of the crossover class weights -------------------------------------------------------------------------------------
+// generation g lies at or in front of `until` (stream numbering, as the snooker rule's): its crossover steps are accumulated
+inline bool adapt_accumulates(const RunFacts& f, int64_t g) { return f.adapt_every > 0 && g + f.rng_offset <= f.adapt_until; }
+// the first update position at or after g, as a generation of the call (callers ask only where adapt_accumulates(f, g): it is
+// then at or in front of `until`, itself an update position)
+inline int64_t adapt_update_at_or_after(const RunFacts& f, int64_t g)
+{
+    const int64_t e = f.adapt_every, r = (g + f.rng_offset) % e;
+    return r == 0 ? g : g + (e - r);
 }
 
 // The launch that starts at generation g.  `span`: what live_span() says a LIVE launch may cover (0: no LIVE launches); M, M_app:
@@ -151,6 +166,13 @@ static LaunchPlan plan_launch(const RunFacts& f, int64_t g, int64_t span, int64_
     if (f.snooker_every > 0) {
         if (snooker_generation(f, g)) { w_end = g; p.snooker = true; }
         else w_end = std::min(w_end, snooker_at_or_after(f, g) - 1);
+    }
+    // The class weights change behind an update position, so a launch ends at the first one at or after g -- whatever kind of
+    // generation stands there, and K boundaries or not (a deferred-append launch over several K-windows is cut as well).
+    if (adapt_accumulates(f, g)) {
+        const int64_t u = adapt_update_at_or_after(f, g);
+        w_end = std::min(w_end, u);
+        p.adapt_after = w_end == u;
     }
     p.w_end = w_end;
     p.nbound = boundaries_in(g, w_end, K);

@@ -56,6 +56,24 @@ class Crossover(namedtuple("Crossover", "ncr delta_max weights tried accepted"))
             return self.accepted / self.tried.astype(np.float64)
 
 
+class CrossoverAdapt(namedtuple("CrossoverAdapt", "every until min_weight weights dist tried rsd updates")):
+    """HipEngine.crossover_adapt: the setting of the adaptation of the CR class weights and its state on the device -- per class
+    the weights, the quantised squared jump distance (units of 1/65536) and the steps tried since adaptation started; the
+    reciprocal standard deviation of every parameter over the chains at the last update; the updates made."""
+    __slots__ = ()
+
+    @property
+    def jump_per_try(self):
+        """normalised squared jump distance per step tried, per class (NaN where a class was never tried): what the weights follow"""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return self.dist / 65536.0 / self.tried.astype(np.float64)
+
+    @property
+    def shares(self):
+        """weights / W: the probability of each class"""
+        return self.weights / float(self.weights.sum())
+
+
 
 class PPC(namedtuple("PPC", "gt eq nan total names")):
     """A posterior predictive check (demcz_ppc): per column of the program, how many of the ``total`` draws had a value greater
@@ -906,6 +924,50 @@ class HipEngine(_HistoryStatistics):
                                               tr.ctypes.data_as(C.POINTER(C.c_int64)), ac.ctypes.data_as(C.POINTER(C.c_int64))))
         k = int(n.value)
         return Crossover(k, int(dm.value), w[:k].copy(), tr[:k].copy(), ac[:k].copy())
+
+    def set_crossover_adapt(self, every, until, min_weight=656):
+        """demcz_set_crossover_adapt: adapt the CR class weights during burn-in, on the device (DREAM's rule).  Up to the position
+        ``until`` (a multiple of ``every``; positions count as the snooker rule's, ``g + rng_offset``) every accepted crossover
+        step adds its squared jump distance, normalised by the spread of the chains, to its class; behind every ``every``-th
+        generation the weights become proportional to the jump distance per step tried, no smaller than ``min_weight`` of 65536.
+        ``every=0`` switches off.  On a fresh crossover handle that does not append externally; ``N * until < 2**31``."""
+        self._chk(self._L.demcz_set_crossover_adapt(self._h, C.c_int64(int(every)), C.c_int64(int(until)), C.c_int32(int(min_weight))))
+
+    @property
+    def crossover_adapt(self):
+        """``CrossoverAdapt(every, until, min_weight, weights, dist, tried, rsd, updates)`` -- demcz_get_crossover_adapt (arrays of
+        length ncr, ``rsd`` of length d); ``.jump_per_try`` and ``.shares``.  Synchronises the handle's stream."""
+        ev, un, mw, up = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int64(0)
+        w, di, tr = np.zeros(8, dtype=np.int32), np.zeros(8, dtype=np.int64), np.zeros(8, dtype=np.int64)
+        rsd = np.zeros(self.d, dtype=np.float64)
+        self._chk(self._L.demcz_get_crossover_adapt(self._h, C.byref(ev), C.byref(un), C.byref(mw), w.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                    di.ctypes.data_as(C.POINTER(C.c_int64)), tr.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                    rsd.ctypes.data_as(C.POINTER(C.c_double)), C.byref(up)))
+        k = self.crossover.ncr
+        return CrossoverAdapt(int(ev.value), int(un.value), int(mw.value), w[:k].copy(), di[:k].copy(), tr[:k].copy(), rsd, int(up.value))
+
+    def set_crossover_adapt_state(self, weights, dist, tried, rsd, updates):
+        """demcz_set_crossover_adapt_state: the state ``crossover_adapt`` returned, onto a fresh handle with the adaptation set --
+        the other half of a checkpoint (with ``set_rng_offset`` the run continues as the uninterrupted one)."""
+        k = self.crossover.ncr
+        w, di, tr = np.zeros(8, dtype=np.int32), np.zeros(8, dtype=np.int64), np.zeros(8, dtype=np.int64)
+        if not (len(weights) == len(dist) == len(tried) == k):
+            raise ValueError("weights, dist, tried: one value per CR class")
+        w[:k], di[:k], tr[:k] = weights, dist, tried
+        r = np.ascontiguousarray(rsd, dtype=np.float64)
+        if r.shape != (self.d,):
+            raise ValueError("rsd: one value per parameter")
+        self._chk(self._L.demcz_set_crossover_adapt_state(self._h, w.ctypes.data_as(C.POINTER(C.c_int32)), di.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                          tr.ctypes.data_as(C.POINTER(C.c_int64)), r.ctypes.data_as(C.POINTER(C.c_double)),
+                                                          C.c_int64(int(updates))))
+
+    def set_crossover_weights(self, weights):
+        """demcz_set_crossover_weights: new class weights for a crossover handle in mid-life (from the next launch on); refused
+        while the adaptation is still running."""
+        w = np.ascontiguousarray(weights, dtype=np.int32)
+        if w.shape != (self.crossover.ncr,):
+            raise ValueError("weights: one integer per CR class")
+        self._chk(self._L.demcz_set_crossover_weights(self._h, w.ctypes.data_as(C.POINTER(C.c_int32))))
 
     def set_history_origin(self, g0):
         self._chk(self._L.demcz_set_history_origin(self._h, int(g0)))

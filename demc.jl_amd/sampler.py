@@ -536,7 +536,8 @@ class _DerivedRunner(_Runner):
 
 
 def make_runner(logobj, Zmat, N, K, Ngeneration, blockindex, eps_scale, X, logp, *, seed, sharding, device_id,
-                 engine_factory, lanes_per_chain, stream, rng_offset=0, append_lag=0, snooker_every=0, snooker_gamma=(1.2, 2.2), crossover=None):
+                 engine_factory, lanes_per_chain, stream, rng_offset=0, append_lag=0, snooker_every=0, snooker_gamma=(1.2, 2.2), crossover=None,
+                 crossover_adapt=None):
     M0, d = Zmat.shape
     if M0 < 2:
         raise ValueError("Zmat needs at least 2 rows (two distinct archive rows per proposal, demcz.jl:176-179)")
@@ -544,6 +545,7 @@ def make_runner(logobj, Zmat, N, K, Ngeneration, blockindex, eps_scale, X, logp,
     crossover = _crossover_option(crossover)
     if crossover:
         lanes_per_chain = _crossover_layout(logobj, lanes_per_chain, blockindex, d)
+    crossover_adapt = _crossover_adapt_option(crossover_adapt, crossover, sharding)
     if snooker_every and M0 < 3:
         raise ValueError("Zmat needs at least 3 rows with snooker generations (three distinct archive rows per snooker step)")
     sh = sharding
@@ -566,6 +568,10 @@ def make_runner(logobj, Zmat, N, K, Ngeneration, blockindex, eps_scale, X, logp,
             if not hasattr(e, "set_crossover"):
                 raise ValueError("crossover: the engine_factory's engine has no set_crossover")
             e.set_crossover(*crossover)
+            if crossover_adapt:
+                if not hasattr(e, "set_crossover_adapt"):
+                    raise ValueError("crossover_adapt: the engine_factory's engine has no set_crossover_adapt")
+                e.set_crossover_adapt(*crossover_adapt)
         if rng_offset:
             e.set_rng_offset(rng_offset)
         if snooker_every:
@@ -610,6 +616,27 @@ def _crossover_option(crossover):
     if ncr == 0:
         return None
     return ncr, delta_max, (None if len(c) == 2 or c[2] is None else [int(v) for v in c[2]])
+
+
+def _crossover_adapt_option(crossover_adapt, crossover, sharding):
+    """None / (every, until) / (every, until, min_weight) -> None (off) or (every, until, min_weight)"""
+    if crossover_adapt is None:
+        return None
+    a = tuple(crossover_adapt)
+    if len(a) not in (2, 3):
+        raise ValueError("crossover_adapt: (every, until) or (every, until, min_weight)")
+    every, until, min_weight = int(a[0]), int(a[1]), (656 if len(a) == 2 else int(a[2]))
+    if every == 0:
+        return None
+    if not crossover:
+        raise ValueError("crossover_adapt adapts the weights of crossover generations: pass crossover=(ncr, delta_max) as well")
+    if every < 1 or until < every or until % every:
+        raise ValueError("crossover_adapt: every >= 1 and until a multiple of every, at least every")
+    if not 1 <= min_weight <= 8192:
+        raise ValueError("crossover_adapt: min_weight must be 1 ... 8192 (of 65536)")
+    if sharding and sharding.total_shards > 1:
+        raise ValueError("crossover_adapt: a shard's own chains are not the population: sharded runs do not adapt")
+    return every, until, min_weight
 
 
 def _crossover_layout(logobj, lanes_per_chain, blockindex, d):
@@ -760,11 +787,14 @@ def demcz_sample(logobj, Zmat, N=4, K=10, Ngeneration=5000, Nblocks=1, blockinde
                  prevrun=None, verbose=True, print_step=100, autostop="no", autostop_Rhat=1.01,
                  autostop_every=1000, seed=0, init="last_rows", padded_Z=False, sharding=None, device_id=0,
                  lanes_per_chain=0, stream=None, engine_factory=None, return_runner=False, rng_offset=None,
-                 append_lag=0, snooker_every=0, snooker_gamma=(1.2, 2.2), crossover=None):
+                 append_lag=0, snooker_every=0, snooker_gamma=(1.2, 2.2), crossover=None, crossover_adapt=None):
     """``snooker_every=s > 0``: every s-th generation is a snooker generation of DE-MCzs with gamma_s ~ U(*snooker_gamma)
     (``HipEngine.set_snooker``; the paper's choice is 10 and (1.2, 2.2)).
     ``crossover=(ncr, delta_max)`` or ``(ncr, delta_max, weights)``: every other generation is a crossover generation of
     DREAM(ZS) (``HipEngine.set_crossover``): one block, a device target, the one-lane layout.
+    ``crossover_adapt=(every, until)`` or ``(every, until, min_weight)``: the class weights are adapted on the device up to
+    generation ``until``, behind every ``every``-th generation (``HipEngine.set_crossover_adapt``); needs ``crossover``, one
+    shard.  (A resumed run that is to continue an adaptation restores its state through ``HipEngine.set_crossover_adapt_state``.)
 
     Serial-driver surface of src/demcz.jl: pass a ``DEMCopt`` as the third argument
     (``demcz_sample(logobj, Zmat, opts; prevrun)``, :1-3) or the positional arguments with
@@ -789,7 +819,8 @@ def demcz_sample(logobj, Zmat, N=4, K=10, Ngeneration=5000, Nblocks=1, blockinde
     runner = make_runner(logobj, Zmat, N, K, Ngeneration, blockindex, eps_scale, X, logp, seed=seed,
                           sharding=sharding, device_id=device_id, engine_factory=engine_factory,
                           lanes_per_chain=lanes_per_chain, stream=stream, rng_offset=rng_offset, append_lag=append_lag,
-                          snooker_every=snooker_every, snooker_gamma=snooker_gamma, crossover=crossover)
+                          snooker_every=snooker_every, snooker_gamma=snooker_gamma, crossover=crossover,
+                          crossover_adapt=crossover_adapt)
     if prevrun is None:
         if not (is_device_target(logobj) and runner.stream_history()):
             runner.prepare_result_arrays(Ngeneration)
@@ -841,7 +872,7 @@ def demcz_anneal(logobj, Zmat, N=4, K=10, Ngeneration=5000, Nblocks=1, blockinde
                  prevrun=None, verbose=True, print_step=100, temperaturefun=tempbaseline, T0=3, TN=0.0,
                  adaptγ=None, seed=0, init="last_rows", padded_Z=False, compat_serial_temp=False, sharding=None,
                  device_id=0, lanes_per_chain=0, stream=None, engine_factory=None, rng_offset=None, append_lag=0,
-                 snooker_every=0, snooker_gamma=(1.2, 2.2), crossover=None):
+                 snooker_every=0, snooker_gamma=(1.2, 2.2), crossover=None, crossover_adapt=None):
     """``snooker_every`` / ``snooker_gamma`` / ``crossover``: as in ``demcz_sample`` (the Jacobian term of a snooker step is
     not tempered).
 
@@ -870,7 +901,8 @@ def demcz_anneal(logobj, Zmat, N=4, K=10, Ngeneration=5000, Nblocks=1, blockinde
     runner = make_runner(logobj, Zmat, N, K, Ngeneration, blockindex, eps_scale, X, logp, seed=seed,
                           sharding=sharding, device_id=device_id, engine_factory=engine_factory,
                           lanes_per_chain=lanes_per_chain, stream=stream, rng_offset=rng_offset, append_lag=append_lag,
-                          snooker_every=snooker_every, snooker_gamma=snooker_gamma, crossover=crossover)
+                          snooker_every=snooker_every, snooker_gamma=snooker_gamma, crossover=crossover,
+                          crossover_adapt=crossover_adapt)
     if prevrun is None:
         if not (is_device_target(logobj) and runner.stream_history()):
             runner.prepare_result_arrays(Ngeneration)

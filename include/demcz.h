@@ -459,8 +459,41 @@ int32_t demcz_get_snooker(const demcz_handle* h, int32_t* every, double* gamma_l
 int32_t demcz_set_crossover(demcz_handle* h, int32_t ncr, const int32_t* weights, int32_t delta_max);
 /* What was set, and per CR class the steps tried and those whose accept test was true, summed over the handle's life (snooker
  * generations are not counted).  weights: ncr values; tried, accepted: 8 values each.  Any pointer may be NULL.  Synchronises
- * the handle's stream when counts are asked for. */
+ * the handle's stream when counts are asked for -- and, on a handle with demcz_set_crossover_adapt, when the weights are: they are
+ * the device's then. */
 int32_t demcz_get_crossover(const demcz_handle* h, int32_t* ncr, int32_t* weights, int32_t* delta_max, int64_t* tried, int64_t* accepted);
+
+/* Adaptation of the CR class weights during burn-in, on the device (DREAM's rule, Vrugt et al. 2009 section 3; DESIGN.md section
+ * 3).  Off by default (every = 0 switches off), and with it off nothing changes.  With it on, every crossover step at a position
+ * g + rng_offset <= until adds 1 to its class's `tried` and, when accepted, the squared jump distance -- every parameter's move
+ * times the reciprocal standard deviation of that parameter over the handle's chains (rsd), summed -- to its class's `dist`,
+ * quantised to 1/65536 and clamped at 65536.  Behind every generation with (g + rng_offset) % every == 0 up to `until` the weights
+ * become w_k = max(min_weight, (int32)(r_k / R * 65536)) with r_k = dist_k / tried_k and R their sum (unchanged while R = 0), and rsd
+ * is computed again; the sums are cumulative from the start of adaptation.  Behind `until` the weights are frozen.  The positions are
+ * in the stream numbering, as the snooker rule's: a resumed run adapts where an uninterrupted one would.  Nothing here synchronises:
+ * the weights live on the device and launches are cut at the update positions.  demcz_get_crossover then reports the device's weights.
+ * until: a multiple of every; min_weight: 1 ... 8192 (656 is 1 % of 65536); N * until < 2^31 (else DEMCZ_ERR_INVALID_ARGUMENT).
+ * DEMCZ_ERR_STATE: crossover is off; the handle has already run a generation; the handle appends externally
+ * (demcz_set_external_append: a shard's own chains are not the population -- such drivers set weights by hand with
+ * demcz_set_crossover_weights; demcz_set_external_append in turn refuses an adapting handle).  demcz_set_crossover with ncr = 0 or a
+ * changed ncr clears the adaptation. */
+int32_t demcz_set_crossover_adapt(demcz_handle* h, int64_t every, int64_t until, int32_t min_weight);
+/* The setting and the state: weights, dist, tried: 8 values each (dist in units of 1/65536); rsd: d values; updates made so far.
+ * Any pointer may be NULL.  Synchronises the handle's stream. */
+int32_t demcz_get_crossover_adapt(const demcz_handle* h, int64_t* every, int64_t* until, int32_t* min_weight, int32_t* weights,
+                                  int64_t* dist, int64_t* tried, double* rsd, int64_t* updates);
+/* The other half of a checkpoint: what demcz_get_crossover_adapt returned, onto a fresh handle with the adaptation set (after
+ * demcz_set_crossover and demcz_set_crossover_adapt; with demcz_set_rng_offset the run then continues as the uninterrupted one).
+ * The spread is then not computed at the first demcz_run.  The arrays are read, not written (dist and tried are `int64_t*` as
+ * demcz_get_crossover_adapt's are, so that one pair of buffers serves both calls from any binding). */
+int32_t demcz_set_crossover_adapt_state(demcz_handle* h, const int32_t* weights, int64_t* dist, int64_t* tried, const double* rsd,
+                                        int64_t updates);
+/* New weights for a crossover handle in mid-life (ncr values, as demcz_set_crossover's: >= 0, 1 <= W < 2^31): the stride of the
+ * streams does not depend on them.  They hold from the next launch on.  DEMCZ_ERR_STATE on a handle without crossover, and while the
+ * adaptation is still running: as long as the last generation run lies in front of `until`, g_done + rng_offset < until.  (In an
+ * uninterrupted run, and in one resumed with demcz_set_crossover_adapt_state, that is updates * every < until; a handle resumed
+ * behind `until` without the state is past its adaptation by position and is not refused.) */
+int32_t demcz_set_crossover_weights(demcz_handle* h, const int32_t* weights);
 
 /* Stateless diagnostics on caller (host) arrays, for code that post-processes returned histories
  * the way the reference's examples do (test/example_normpdf.jl:35-47): the array is uploaded, reduced

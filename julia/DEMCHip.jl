@@ -132,6 +132,27 @@ function get_crossover(h)
     k = Int(n[])
     k, Int(dm[]), Int.(w[1:k]), tr[1:k], ac[1:k]
 end
+# adaptation of the CR class weights during burn-in, on the device (fresh crossover handles that do not append externally): up to
+# position `until` (a multiple of `every`, counted as g + rng_offset) the weights follow the jump distance per step tried of each
+# class; every = 0 switches off
+set_crossover_adapt!(h, every, until, min_weight=656) =
+    chk(ccall((:demcz_set_crossover_adapt, libdemcz), Int32, (Ptr{Cvoid}, Int64, Int64, Int32), h, every, until, min_weight), h)
+# (every, until, min_weight, weights, dist, tried, rsd, updates); d: the handle's dimension
+function get_crossover_adapt(h, d)
+    ev = Ref{Int64}(0); un = Ref{Int64}(0); mw = Ref{Int32}(0); up = Ref{Int64}(0)
+    w = zeros(Int32, 8); di = zeros(Int64, 8); tr = zeros(Int64, 8); rsd = zeros(Float64, d)
+    chk(ccall((:demcz_get_crossover_adapt, libdemcz), Int32,
+              (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int32}, Ptr{Int32}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ref{Int64}),
+              h, ev, un, mw, w, di, tr, rsd, up), h)
+    Int(ev[]), Int(un[]), Int(mw[]), w, di, tr, rsd, Int(up[])
+end
+# the other half of a checkpoint: the arrays get_crossover_adapt returned (8, 8, 8 and d values), onto a fresh handle with adaptation set
+set_crossover_adapt_state!(h, weights::Vector{Int32}, dist::Vector{Int64}, tried::Vector{Int64}, rsd::Vector{Float64}, updates) =
+    chk(ccall((:demcz_set_crossover_adapt_state, libdemcz), Int32, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64),
+              h, weights, dist, tried, rsd, updates), h)
+# new class weights for a crossover handle in mid-life (refused while the adaptation is still running)
+set_crossover_weights!(h, weights) =
+    chk(ccall((:demcz_set_crossover_weights, libdemcz), Int32, (Ptr{Cvoid}, Ptr{Int32}), h, Int32.(weights)), h)
 # the loop demcz.jl:30-55 (generations + the R-hat test every `every`) as ONE call; returns the generation it stopped at
 function run_checked!(h, g_from, g_to, γ, every, threshold)
     g_stop = Ref{Int64}(0); n = Ref{Int32}(0)
